@@ -556,6 +556,7 @@ def other_configs(args):
     return res
 
 
+MAX_BATCHES = 32  # distinct batches of reads resident in HBM (1.2 GB each at the default workload)
 LINE_LIMIT = 6000  # bytes of the final stdout line: the driver keeps the last 8 KB of stdout, and a line it cannot see whole it cannot parse (round 5: 33.6 KB, `parsed: null`)
 
 
@@ -659,6 +660,10 @@ def emit(out, args):
     print(line, flush=True)
 
 
+# the legs beyond the headline figure: their values under --full (all of them 0 without it)
+LEG_DEFAULTS = {"cpu_pairs": -1, "second_genome": 1, "native_boundary": 1, "pcie_steps": 36, "other_configs": 1, "file_steps": 1, "vcf_reduce": 1}
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -673,37 +678,49 @@ def parse():
     ap.add_argument("--dele", type=float, default=0.001, help="per-base deletion rate")
     ap.add_argument("--alg", default="ksw2", choices=["nw", "ksw2"])
     ap.add_argument("--full-sa", type=int, default=2, help="1: every suffix-array entry, the jump table and the rank records in HBM; 2: the pair records too (two bases per step of the seeding walk)")
-    ap.add_argument("--cpu-pairs", type=int, default=-1,
-                    help="pairs of the CPU-baseline sample (0 = skip, -1 = about 20 s of work for this host's core count)")
+    ap.add_argument("--cpu-pairs", type=int, default=None,
+                    help="pairs of the CPU-baseline sample (0 = skip, -1 = about 20 s of work for this host's core count; default: -1 with --full, 0 without)")
     ap.add_argument("--cpu-t1-pairs", type=int, default=-1, help="pairs of the -t 1 run of the CPU baseline (-1: about 20 s of its clock)")
     ap.add_argument("--cpu-level", default="full", choices=["sam", "two", "full"],
                     help="runs of the CPU baseline: with -sam only | and without any output (mapping_only) | and at -t 1")
     ap.add_argument("--repeats", type=int, default=2000, help="--genome uniform: planted dispersed repeat families")
     ap.add_argument("--genome", default="human", choices=["human", "uniform"],
                     help="repeat content of the synthetic genome: a human-like landscape (default) or round 1's nearly repeat-free one")
-    ap.add_argument("--second-genome", type=int, default=1,
-                    help="1: after the main run, map 2 steps against the other kind of genome as well and report them under `other_genome`")
-    ap.add_argument("--native-boundary", type=int, default=1, help="the host-buffer leg once more from a process on the system's HIP runtime (mapcaller_amd/boundary.py: no torch in it), "
-                                                                   "after this one has let go of the GPU's memory; N = 1 only; 0 = skip")
-    ap.add_argument("--pcie-steps", type=int, default=36, help="steps of the host-buffer leg (value_pcie_inclusive), over the timed region's batches in turn; 0 = skip")
+    ap.add_argument("--second-genome", type=int, default=None,
+                    help="1: after the main run, map 2 steps against the other kind of genome as well and report them under `other_genome` (default: 1 with --full, 0 without)")
+    ap.add_argument("--native-boundary", type=int, default=None, help="the host-buffer leg once more from a process on the system's HIP runtime (mapcaller_amd/boundary.py: no torch in it), "
+                                                                      "after this one has let go of the GPU's memory; N = 1 only; 0 = skip (default: 1 with --full, 0 without)")
+    ap.add_argument("--pcie-steps", type=int, default=None, help="steps of the host-buffer leg (value_pcie_inclusive), over the timed region's batches in turn; 0 = skip "
+                                                                "(default: 36 with --full, 0 without)")
     ap.add_argument("--single-end", type=int, default=0, help="1: single-end reads (--batch-pairs then counts reads)")
-    ap.add_argument("--other-configs", type=int, default=1,
+    ap.add_argument("--other-configs", type=int, default=None,
                     help="1: after the main run, BASELINE.json's configs 5 (250 bp PE at 5 %% indels, -alg nw) and 2 (E. coli-sized genome, 1 M x 100 bp SE) "
-                         "as child processes, reported under `other_configs` with their stage times, DP GCUPS and CPU baselines")
-    ap.add_argument("--file-steps", type=int, default=1, help="1: the file-to-file leg (value_file_to_file): one batch as FASTQ files in tmpfs -> SAM; 0 = skip")
+                         "as child processes, reported under `other_configs` with their stage times, DP GCUPS and CPU baselines (default: 1 with --full, 0 without)")
+    ap.add_argument("--file-steps", type=int, default=None, help="1: the file-to-file leg (value_file_to_file): one batch as FASTQ files in tmpfs -> SAM; 0 = skip "
+                                                                "(default: 1 with --full, 0 without)")
     ap.add_argument("--file-batches", type=int, default=2, help="batches of the timed region whose reads the file-to-file leg maps (2 x 8 M reads: eight batches of the file pipeline)")
     ap.add_argument("--file-batch-reads", type=int, default=1 << 21, help="reads per batch of the file front end's pipeline")
     ap.add_argument("--file-threads", type=int, default=0, help="host threads per pool of the file front end (0 = pick)")
     ap.add_argument("--vcf-slice-reads", type=int, default=8_000_000, help="reads per mapping call in the -vcf leg")
     ap.add_argument("--vcf-tier1-gb", type=int, default=8, help="HBM for the large tier's pair records in the -vcf leg (MCX_TIER1_GB)")
-    ap.add_argument("--vcf-reduce", type=int, default=1,
+    ap.add_argument("--vcf-reduce", type=int, default=None,
                     help="after the timed region: accumulate the -vcf alignment profile of one batch and sum it over the "
-                         "ranks with RCCL (1 = yes, 0 = no, -1 = only when more than one GPU)")
+                         "ranks with RCCL (1 = yes, 0 = no, -1 = only when more than one GPU; default: 1 with --full, 0 without)")
     ap.add_argument("--detail-dir", default=os.path.join(ROOT, "gpurun_out"), help="where the detail record (every section in full) is written; the final line names it")
     ap.add_argument("--detail-tag", default="", help="suffix of the detail record's file name")
     ap.add_argument("--detail-stdout", type=int, default=0, help="1: the detail record also as an earlier stdout line (`BENCH_DETAIL {...}`); off by default — nothing but the final line goes to stdout")
     ap.add_argument("--full-line", type=int, default=0, help="1: the final line is the detail record itself (what the child processes of this script read)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the CPU baseline, the host-buffer, file-to-file and -vcf legs, the other genome "
+                         "and BASELINE.json's configs 5 and 2.  Without it a run sets up, warms up, times its steps and prints the line; a leg asked "
+                         "for by its own option runs either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: what the last step computed — a fixed, seeded sample of its alignment records and their CIGARs — as DIR/<name>.npy")
+    args = ap.parse_args()
+    for k, full in LEG_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, full if args.full else 0)
+    return args
 
 
 def _put_last(codes, idx, val, stamp):
@@ -1003,6 +1020,43 @@ def launch_ranks(args):
     sys.exit(subprocess.run(cmd).returncode)
 
 
+DUMP_READS = 1 << 16  # records of the last step written by --dump-outputs: a fixed, seeded sample of the batch's reads
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(where, d_aln, d_cig, n_reads):
+    """What the last timed step handed its caller — one alignment record per read and the batch's CIGAR pool, both in HBM — as
+    DIR/<name>.npy: for DUMP_READS reads drawn with a fixed seed, every field of the record (read_index: which reads) in float64, and
+    their CIGAR words (len << 4 | op) one read after the other in float32, cigar_n of them per read.  Where a read's words lie in the
+    pool (cigar_off) is the pool's business and is left out: the words themselves are compared."""
+    import numpy as np
+    from mapcaller_amd import api
+    os.makedirs(where, exist_ok=True)
+    k = min(DUMP_READS, n_reads)
+    pick = np.sort(np.random.default_rng(20240611).choice(n_reads, size=k, replace=False))
+    idx = torch.from_numpy(pick).to(d_aln.device)
+    rec = d_aln.view(n_reads, 64).index_select(0, idx).cpu().numpy().view(api.ALN_DTYPE).reshape(k)
+    lo, hi = rec["cigar_off"].astype(np.int64), rec["cigar_off"].astype(np.int64) + rec["n_cigar"]
+    has = rec["n_cigar"] > 0
+    if (rec["n_cigar"] < 0).any() or (has & ((lo < 0) | (hi > d_cig.numel()))).any():  # (checked here: an index out of the pool is a device fault below)
+        raise RuntimeError("--dump-outputs: a record's CIGAR lies outside the batch's pool")
+    n_cig = torch.from_numpy(rec["n_cigar"].astype(np.int64)).to(d_aln.device)
+    start = torch.from_numpy(rec["cigar_off"].astype(np.int64)).to(d_aln.device)
+    first = torch.cumsum(n_cig, 0) - n_cig
+    words = torch.repeat_interleave(start - first, n_cig) + torch.arange(int(n_cig.sum()), device=d_aln.device)
+    cigar = d_cig.index_select(0, words).cpu().numpy()
+    out = {"read_index": pick.astype(np.float64)}
+    for f in api.ALN_DTYPE.names:
+        if f not in ("cigar_off", "pad"):
+            out["cigar_n" if f == "n_cigar" else f] = rec[f].astype(np.float64)
+    out["cigar"] = cigar.astype(np.float32)  # (< 2^24: exact)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_BYTES}")
+    for name, a in out.items():
+        np.save(os.path.join(where, name + ".npy"), a)
+
+
 class Trajectory:
     """The run's insert-size state across the ranks (N > 1): every step is one round of the input stream — rank r maps
     batch N*step + r — and the ranks walk ONE avgDist trajectory over the round (ReadMapping.cpp:462, :538-539), as
@@ -1107,7 +1161,7 @@ def main():
     reads_per_step = (2 if paired else 1) * args.batch_pairs
     mapper = api.Mapper(index, alg=args.alg, max_read_len=max(256, args.rlen), max_batch_reads=reads_per_step)
     batches = []
-    for s in range(n_steps):
+    for s in range(min(n_steps, MAX_BATCHES)):  # (more steps than that: the batches come round again)
         b = make_reads(codes, lens, args.batch_pairs, args.rlen, seed=1000 * (rank + 1) + s, device=dev, sub=args.sub, ins=args.ins, dele=args.dele, paired=paired)
         batches.append(b.reshape(-1).contiguous())
     off = (torch.arange(reads_per_step + 1, device=dev, dtype=torch.int64) * args.rlen).to(torch.uint32)
@@ -1134,10 +1188,11 @@ def main():
     traj = Trajectory(dist, dev, world, rank, (args.batch_pairs + 99) // 100) if (world > 1 and paired) else None
 
     def step(i):
+        b = batches[i % len(batches)]
         if traj:
-            traj.step(mapper, batches[i].data_ptr(), off.data_ptr(), reads_per_step, d_aln.data_ptr(), d_cig.data_ptr())
+            traj.step(mapper, b.data_ptr(), off.data_ptr(), reads_per_step, d_aln.data_ptr(), d_cig.data_ptr())
         else:
-            mapper.map_batch_dev(batches[i].data_ptr(), off.data_ptr(), reads_per_step, paired, d_aln.data_ptr(), d_cig.data_ptr())
+            mapper.map_batch_dev(b.data_ptr(), off.data_ptr(), reads_per_step, paired, d_aln.data_ptr(), d_cig.data_ptr())
 
     # (the set-up above leaves host threads behind that still spin — torch's CPU pool after the .cpu() copies — and the box gives the process a CPU-time SHARE:
     #  a group that has spent it sleeps until the next 100 ms period, this thread with it; let the period turn before the clock starts)
@@ -1160,6 +1215,14 @@ def main():
         dt = mdist_.max_over_ranks(dt, dev)
     after = mapper.stats.as_dict()
     d = {k: after[k] - before[k] for k in after}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_aln, d_cig, reads_per_step)
+
+    # (the legs below read the first six batches and five from the warm-up's end, no others: with many steps the rest would leave the streams of
+    #  the host-buffer leg no HBM for their scratch, and the first kernel that needs it aborts its queue)
+    need = set(range(6)) | set(range(args.warmup, args.warmup + max(5, args.file_batches))) | {min(args.warmup, len(batches) - 1)}
+    batches[:] = [b if i in need else None for i, b in enumerate(batches)]
+    torch.cuda.empty_cache()
 
     # ---- the same batches from pinned host memory, records back to pinned host memory (not `value`) ----------
     pcie = None

@@ -94,3 +94,56 @@ def test_emit_prints_one_json_line_last(tmp_path, capsys):
     line = json.loads(lines[0])
     detail = json.load(open(os.path.join(str(tmp_path), "bench_detail.json")))
     assert "per_kernel" in detail["roofline"] and line["value"] == detail["value"]
+
+
+def test_a_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    """`bench.py --steps N --warmup W` sets up, times its steps and prints the line; `--full` brings back every other leg at the
+    values a plain run had before the option existed; a leg asked for by its own option runs either way."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert all(getattr(a, k) == 0 for k in bench.LEG_DEFAULTS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert (a.cpu_pairs, a.second_genome, a.native_boundary, a.pcie_steps, a.other_configs, a.file_steps, a.vcf_reduce) == (-1, 1, 1, 36, 1, 1, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--vcf-reduce", "1", "--pcie-steps", "4", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.vcf_reduce, a.pcie_steps, a.file_steps, a.dump_outputs) == (1, 4, 0, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--other-configs", "0"])
+    assert bench.parse().other_configs == 0
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_the_records(tmp_path):
+    """--dump-outputs on records laid out as the library writes them (mcx_aln, a CIGAR pool filled in no particular order): the
+    sampled reads' fields and CIGAR words, in float64 / float32, the same sample every time, within 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    from mapcaller_amd import api
+    n = 300_000
+    rng = np.random.default_rng(5)
+    rec = np.zeros(n, dtype=api.ALN_DTYPE)
+    rec["pos"] = rng.integers(1, 3_100_000_000, n)
+    rec["mapq"] = rng.integers(0, 61, n)
+    rec["n_cigar"] = rng.integers(0, 5, n)
+    order = rng.permutation(n)  # (the pool in another order than the reads)
+    start = np.zeros(n, dtype=np.int64)
+    start[order] = np.cumsum(rec["n_cigar"][order]) - rec["n_cigar"][order]
+    rec["cigar_off"] = start
+    pool = torch.from_numpy(rng.integers(0, 1 << 14, api.cigar_pool_words(n)).astype(np.int32))
+    d_aln = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), d_aln, pool, n)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "cigar.npy" in names and "pos.npy" in names and "read_index.npy" in names and "cigar_off.npy" not in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    load = lambda sub, f: np.load(tmp_path / sub / (f + ".npy"))
+    for f in names:
+        a = load("a", f[:-4])
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, load("b", f[:-4]))
+    idx = load("a", "read_index").astype(np.int64)
+    assert len(idx) == bench.DUMP_READS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(load("a", "pos"), rec["pos"][idx]) and np.array_equal(load("a", "mapq"), rec["mapq"][idx])
+    want = np.concatenate([pool.numpy()[start[r]:start[r] + rec["n_cigar"][r]] for r in idx])
+    assert np.array_equal(load("a", "cigar"), want) and np.array_equal(load("a", "cigar_n"), rec["n_cigar"][idx])
