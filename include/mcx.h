@@ -197,6 +197,21 @@ int mcx_cigar_words(mcx_ctx *, uint32_t *n_words);
 int mcx_map_batch(mcx_ctx *, const uint8_t *bases, const uint32_t *off, uint32_t n_reads, int paired,
                   int64_t avg_state[4], mcx_aln *aln, uint32_t *cigar, mcx_stats *stats);
 
+/* -m (MapCaller's bUnique = false): a read whose best score is held by several candidates gets a SAM line for
+ * each of them, in candidate order.  The first is the record above, as in unique mode; the others ("extras")
+ * come apart from the fixed one-record-per-read output.  on: the mode for the context's following batches.
+ * extra_cap: the initial capacity of the device's extras pool in lines (0: a default); a batch that needs
+ * more makes the pool grow (MCX_ALLOC_LOG says so) and no line is ever dropped.  The profile (-vcf) does not
+ * change.  A batch that maps single-end reads gives the later lines FLAG 0 or 16 by strand. */
+int mcx_ctx_set_multi(mcx_ctx *, int on, uint32_t extra_cap);
+/* The extras of the batch the last mapping call mapped (mcx_map_batch_dev / mcx_map_batch / mcx_stream_map*
+ * / mcx_batch_end*), in HBM and in read order: the lines of read r are d_recs[d_index[r] .. d_index[r + 1])
+ * (d_index has n_reads + 1 entries); a record's cigar_off points into d_cigar.  Valid until the next batch
+ * of the context begins. */
+int mcx_multi_lines(mcx_ctx *, const uint32_t **d_index, const mcx_aln **d_recs, const uint32_t **d_cigar, uint32_t *n_recs, uint32_t *n_words);
+/* the same copied to host memory: index[n_reads + 1], recs[n_recs], cigar[n_words] (sizes from mcx_multi_lines) */
+int mcx_multi_copy(mcx_ctx *, uint32_t *index, mcx_aln *recs, uint32_t *cigar);
+
 /* ---- batches from host memory with the copies overlapped with the kernels -------------------------
  * The device boundary of the drop-in: reads arrive in (pinned) host memory, records leave to (pinned)
  * host memory.  Three batches are in flight, each in a slot of HBM of its own: one being copied in on a
@@ -235,6 +250,12 @@ uint32_t mcx_host_cpus(void);
 int64_t mcx_gz_inflate(const char *path, int threads, uint64_t stretch_bytes, uint8_t *out, uint64_t cap, uint64_t *n_out);
 int mcx_stream_map(mcx_ctx *, int paired, int64_t avg_state[4], mcx_aln *aln, uint32_t *cigar, mcx_stats *stats);
 int mcx_stream_collect(mcx_ctx *, uint64_t *bytes_in, uint64_t *bytes_out);
+/* -m (mcx_ctx_set_multi): the extras of the batch the last mcx_stream_collect handed over, which came to host memory with its
+ * records (packed to mcx_aln32 on the device, counted in bytes_out): index[n_reads + 1], recs[n_recs] (cigar_off into cigar),
+ * cigar[n_words], as mcx_multi_lines describes them.  The buffers are the slot's, page-locked, and hold until a batch is mapped in
+ * that slot again (at the earliest by the second mcx_stream_map* / mcx_stream_mapped* call after the collect).  n_reads = 0: the
+ * batch carried none. */
+int mcx_stream_multi(mcx_ctx *, const uint32_t **index, const mcx_aln32 **recs, const uint32_t **cigar, uint32_t *n_reads, uint32_t *n_recs, uint32_t *n_words);
 int mcx_stream_next(mcx_ctx *, const uint8_t **d_bases, const uint32_t **d_off, uint32_t *n_reads, mcx_aln **d_aln, uint32_t **d_cigar);
 int mcx_stream_mapped(mcx_ctx *, mcx_aln *aln, uint32_t *cigar);
 /* mcx_stream_map / mcx_stream_mapped with the records leaving HBM in 32 bytes each (packed on the device, half the bytes across PCIe) */

@@ -68,6 +68,7 @@ SYMBOLS = [
     "mcx_profile_sparse_shard", "mcx_batch_end_keys", "mcx_batch_accumulate",
     "mcx_stream_submit", "mcx_stream_submit_packed", "mcx_stream_map", "mcx_stream_collect", "mcx_stream_next", "mcx_stream_mapped",
     "mcx_stream_map32", "mcx_stream_mapped32",
+    "mcx_ctx_set_multi", "mcx_multi_lines", "mcx_multi_copy", "mcx_stream_multi",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -324,6 +325,10 @@ def lib() -> C.CDLL:
     L.mcx_stream_map32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_mapped32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mcx_stream_collect.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mcx_ctx_set_multi.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+    L.mcx_multi_lines.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint32)] * 2
+    L.mcx_multi_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mcx_stream_multi.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_uint32)] * 3
     L.mcx_planes_alloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.mcx_planes_free.argtypes = [C.c_void_p]
     L.mcx_planes_free.restype = None
@@ -453,10 +458,14 @@ class Mapper:
     """One mapping context (mcx_ctx): a GPU, its scratch and the reference's tunables."""
 
     def __init__(self, index: Index, alg: str = "nw", max_read_len: int = 256, max_batch_reads: int = 1 << 20,
-                 max_pos_diff: int = 30, max_mismatch_rate: float = 0.05):
+                 max_pos_diff: int = 30, max_mismatch_rate: float = 0.05, multi: bool = False, multi_cap: int = 0):
+        """``multi``: -m — a SAM line for every candidate with a read's best score (map_batch returns them as a third element, map_files
+        writes them behind the read's first line); ``multi_cap``: the initial capacity of the extras pool in lines (0: a default; it grows)."""
         if alg not in ("nw", "ksw2"):
             raise ValueError("alg must be 'nw' or 'ksw2'")
         self.index = index
+        self.multi = bool(multi)
+        self.stream_multi = []  # (multi) map_stream*: every collected batch's extras, in input order (stream_multi_collected)
         o = Opts()
         lib().mcx_opts_default(C.byref(o))
         o.alg = 0 if alg == "nw" else 1
@@ -466,6 +475,8 @@ class Mapper:
         o.max_mismatch_rate = max_mismatch_rate
         self._h = C.c_void_p()
         _check(lib().mcx_ctx_create(index._h, C.byref(o), C.byref(self._h)), "mcx_ctx_create")
+        if self.multi:
+            _check(lib().mcx_ctx_set_multi(self._h, 1, int(multi_cap)), "mcx_ctx_set_multi")
         self.avg = (C.c_int64 * 4)()
         lib().mcx_avg_init(self.avg)
         self.stats = Stats()
@@ -526,7 +537,23 @@ class Mapper:
         pool = np.zeros(cigar_pool_words(n), dtype=np.uint32)
         _check(lib().mcx_map_batch(self._h, bases.ctypes.data, off.ctypes.data, n, int(paired), self.avg,
                                    aln.ctypes.data, pool.ctypes.data, C.byref(self.stats)), "mcx_map_batch")
-        return aln, [pool[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["n_cigar"])] for a in aln]
+        cigars = [pool[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["n_cigar"])] for a in aln]
+        if not self.multi:
+            return aln, cigars
+        return aln, cigars, self.multi_lines(n)
+
+    def multi_lines(self, n_reads: int):
+        """(multi) the last batch's extra lines: (index uint32 [n_reads + 1], records ALN_DTYPE, their CIGAR words per record) — read r's
+        lines after its first are records[index[r]:index[r + 1]], in the order the reference prints them (mcx_multi_lines / mcx_multi_copy)."""
+        if n_reads == 0:
+            return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=ALN_DTYPE), []
+        nl, nw = C.c_uint32(), C.c_uint32()
+        _check(lib().mcx_multi_lines(self._h, None, None, None, C.byref(nl), C.byref(nw)), "mcx_multi_lines")
+        index = np.zeros(n_reads + 1, dtype=np.uint32)
+        recs = np.zeros(nl.value, dtype=ALN_DTYPE)
+        words = np.zeros(max(1, nw.value), dtype=np.uint32)
+        _check(lib().mcx_multi_copy(self._h, index.ctypes.data, recs.ctypes.data, words.ctypes.data), "mcx_multi_copy")
+        return index, recs, [words[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["n_cigar"])] for a in recs]
 
     @staticmethod
     def stream_outputs(n_reads: int, slots: int = 3, record_bytes: int = 64):
@@ -553,6 +580,8 @@ class Mapper:
                 _check(L.mcx_stream_map(self._h, int(paired), self.avg, a.data_ptr(), g.data_ptr(), C.byref(self.stats)), "mcx_stream_map")
             if i >= 2:
                 _check(L.mcx_stream_collect(self._h, C.byref(h2d), C.byref(d2h)), "mcx_stream_collect")
+                if self.multi:
+                    self.stream_multi.append(self.stream_multi_collected())
         return h2d.value, d2h.value
 
     def map_stream_packed(self, packed, n_reads: int, paired: bool, outputs=None, out32: bool = False):
@@ -573,7 +602,23 @@ class Mapper:
                 _check(stream_map(self._h, int(paired), self.avg, a.data_ptr(), g.data_ptr(), C.byref(self.stats)), "mcx_stream_map")
             if i >= 2:
                 _check(L.mcx_stream_collect(self._h, C.byref(h2d), C.byref(d2h)), "mcx_stream_collect")
+                if self.multi:
+                    self.stream_multi.append(self.stream_multi_collected())
         return h2d.value, d2h.value
+
+    def stream_multi_collected(self):
+        """(multi) the extras of the batch the last mcx_stream_collect handed over, copied out of the slot's page-locked buffers:
+        (index uint32 [n_reads + 1], records ALN_DTYPE, their CIGAR words per record) as multi_lines gives them."""
+        idx, recs, cig = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nr, nl, nw = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().mcx_stream_multi(self._h, C.byref(idx), C.byref(recs), C.byref(cig), C.byref(nr), C.byref(nl), C.byref(nw)), "mcx_stream_multi")
+        if nr.value == 0:
+            return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=ALN_DTYPE), []
+        index = np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_uint32)), (nr.value + 1,)).copy()
+        a32 = np.frombuffer(C.string_at(recs, nl.value * ALN32_DTYPE.itemsize), dtype=ALN32_DTYPE) if nl.value else np.zeros(0, dtype=ALN32_DTYPE)
+        words = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_uint32)), (nw.value,)).copy() if nw.value else np.zeros(1, dtype=np.uint32)
+        out = aln32_unpack(a32)
+        return index, out, [words[int(a["cigar_off"]):int(a["cigar_off"]) + int(a["n_cigar"])] for a in out]
 
     def map_batch_dev(self, d_bases_ptr: int, d_off_ptr: int, n_reads: int, paired: bool, d_aln_ptr: int, d_cigar_ptr: int):
         """Device pointers (e.g. torch.Tensor.data_ptr()); results stay in HBM."""

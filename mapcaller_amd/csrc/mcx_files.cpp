@@ -676,6 +676,11 @@ struct Batch {
     uint32_t n_pair_reads = 0;       // reads [0, n_pair_reads) are mapped as pairs, the rest one by one: two parts, two CIGAR pools
     std::vector<Text> slices;        // the batch's SAM text
     uint64_t sam_bytes = 0;
+    // -m: each part's extra lines, arrived with its records (mcx_stream_collect -> mcx_stream_multi): those of the part's read r are
+    // recs[index[r] .. index[r + 1]), their cigar_off into cig
+    struct Extras { std::vector<uint32_t> index, cig; std::vector<mcx_aln> recs; } mx[2];
+    bool has_mx = false;
+    std::deque<bool> parts_out; // the parts on their way out, oldest first (true: the single-read part)
     bool reserve(size_t reads, size_t words_per_read)
     {
         if (reads > cap_reads) {
@@ -710,15 +715,12 @@ inline size_t sam_bound(const HostIndex &ix, size_t name_len, size_t rlen, int c
     return name_len + 2 * rlen + (chr >= 0 ? ix.chr_name[chr].size() : 1) + 11 * (size_t)(n_cigar > 0 ? n_cigar : 0) + 160;
 }
 
-void sam_record(const HostIndex &ix, const Batch &bt, uint32_t r, Text &o)
+// one SAM line of read r: `rec` with its operations at `cigar`
+void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx_aln &rec, const uint32_t *cigar, Text &o)
 {
     static const char opc[8] = {'M', 'I', 'D', 'N', 'S', 'H', 'P', '='};
     const char *base;
     const Rec &e = bt.rec(r, base);
-    mcx_aln rec;
-    mcx_aln_unpack(&bt.recs[r], &rec);
-    // the batch's CIGAR pool (the single-read part of a batch has one of its own behind the pairs'), cigar_off = the read's place in it
-    const uint32_t *cigar = bt.cig + (r < bt.n_pair_reads ? 0 : MCX_CIGAR_POOL_WORDS(bt.n_pair_reads)) + (size_t)(uint32_t)rec.cigar_off;
     const char *seq = base + e.seq;
     const int rlen = (int)e.rlen;
     const char *qual = bt.fastq ? base + e.qual : nullptr;
@@ -754,6 +756,39 @@ void sam_record(const HostIndex &ix, const Batch &bt, uint32_t r, Text &o)
     }
     if (!mapped) o.lit("\tAS:i:0\tXS:i:0\n");
     else { o.lit("\tNM:i:"); o.num(rec.nm); o.lit("\tAS:i:"); o.num(rec.as); o.lit("\tXS:i:"); o.num(rec.xs); o.put('\n'); }
+}
+
+// -m: read r's extra lines (none without -m) — where they lie in its part's extras
+inline void extra_range(const Batch &bt, uint32_t r, const Batch::Extras *&x, uint32_t &lo, uint32_t &hi)
+{
+    const int part = r < bt.n_pair_reads ? 0 : 1;
+    const uint32_t k = part ? r - bt.n_pair_reads : r;
+    x = &bt.mx[part];
+    lo = hi = 0;
+    if (bt.has_mx && (size_t)k + 1 < x->index.size()) { lo = x->index[k]; hi = x->index[k + 1]; }
+}
+
+// read r's line(s): the record of unique mode, then (-m) every further candidate with the best score (SamReport.cpp:364-488)
+void sam_record(const HostIndex &ix, const Batch &bt, uint32_t r, Text &o)
+{
+    mcx_aln rec;
+    mcx_aln_unpack(&bt.recs[r], &rec);
+    // the batch's CIGAR pool (the single-read part of a batch has one of its own behind the pairs'), cigar_off = the read's place in it
+    const uint32_t *cigar = bt.cig + (r < bt.n_pair_reads ? 0 : MCX_CIGAR_POOL_WORDS(bt.n_pair_reads)) + (size_t)(uint32_t)rec.cigar_off;
+    sam_line(ix, bt, r, rec, cigar, o);
+    const Batch::Extras *x; uint32_t lo, hi;
+    extra_range(bt, r, x, lo, hi);
+    for (uint32_t i = lo; i < hi; i++) sam_line(ix, bt, r, x->recs[i], x->cig.data() + (uint32_t)x->recs[i].cigar_off, o);
+}
+
+// bytes read r's line(s) can take at most
+inline size_t sam_bound_read(const HostIndex &ix, const Batch &bt, uint32_t r, size_t name_len, size_t rlen)
+{
+    size_t b = sam_bound(ix, name_len, rlen, bt.recs[r].chr == 0xFFFFu ? -1 : (int)bt.recs[r].chr, bt.recs[r].n_cigar);
+    const Batch::Extras *x; uint32_t lo, hi;
+    extra_range(bt, r, x, lo, hi);
+    for (uint32_t i = lo; i < hi; i++) b += sam_bound(ix, name_len, rlen, x->recs[i].chr, x->recs[i].n_cigar);
+    return b;
 }
 
 } // namespace
@@ -1352,7 +1387,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                     for (uint32_t r = lo; r < hi; r++) {
                         const char *base;
                         const Rec &e = b->rec(r, base);
-                        bound += sam_bound(hix, e.name_len, e.rlen, b->recs[r].chr == 0xFFFFu ? -1 : (int)b->recs[r].chr, b->recs[r].n_cigar);
+                        bound += sam_bound_read(hix, *b, r, e.name_len, e.rlen);
                     }
                     t.start(bound);
                     for (uint32_t r = lo; r < hi; r++) sam_record(hix, *b, r, t);
@@ -1369,6 +1404,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
 
     // ---- stage 2 (this thread): copy in | map | copy out, three parts of batches on the device at a time ------------------
     const bool profile = mcx_ctx_has_profile(c);
+    const bool multi = mcx_ctx_multi(c);
     int in_flight = 0;             // parts submitted and not collected yet
     std::deque<BatchPtr> leaving;  // mapped, their last part on its way out (oldest first), with the number of parts each still waits for
     std::deque<int> leaving_parts;
@@ -1392,6 +1428,18 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     auto collect_oldest = [&]() -> int { // the oldest mapped part has arrived in host memory
         const Tick tq = now();
         const int e = mcx_stream_collect(c, nullptr, nullptr);
+        if (!leaving.empty() && !leaving.front()->parts_out.empty()) { // (-m) the part's extras came with it
+            Batch *b = leaving.front().get();
+            const bool second = b->parts_out.front();
+            b->parts_out.pop_front();
+            Batch::Extras &x = b->mx[second ? 1 : 0];
+            x.index.clear(); x.recs.clear(); x.cig.clear();
+            const uint32_t *idx = nullptr, *cg = nullptr; const mcx_aln32 *rs = nullptr; uint32_t nr = 0, nl = 0, nw = 0;
+            if (e == 0 && multi && mcx_stream_multi(c, &idx, &rs, &cg, &nr, &nl, &nw) == 0 && nr) {
+                x.index.assign(idx, idx + nr + 1); x.cig.assign(cg, cg + nw); x.recs.resize(nl);
+                for (uint32_t i = 0; i < nl; i++) mcx_aln_unpack(&rs[i], &x.recs[i]);
+            }
+        }
         t_m_collect += secs(tq, now());
         in_flight--;
         if (!leaving.empty() && --leaving_parts.front() == 0) { mapped.push(std::move(leaving.front())); leaving.pop_front(); leaving_parts.pop_front(); }
@@ -1448,12 +1496,15 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         int parts_out = 0;
         const uint8_t *d_bases = nullptr; const uint32_t *d_off = nullptr; mcx_aln *d_aln = nullptr; uint32_t *d_cig = nullptr; uint32_t n_dev = 0;
         auto part_in = [&]() { const Tick tq = now(); const int e = mcx_stream_next(c, &d_bases, &d_off, &n_dev, &d_aln, &d_cig); t_m_in += secs(tq, now()); if (e && rc == 0) rc = e; return e == 0; };
+        p->has_mx = multi;
+        for (Batch::Extras &x : p->mx) { x.index.clear(); x.recs.clear(); x.cig.clear(); }
+        p->parts_out.clear();
         auto part_out = [&](bool second) {
             const Tick tq = now();
             const int e = second ? mcx_stream_mapped32(c, p->recs + p->n_pair_reads, p->cig + MCX_CIGAR_POOL_WORDS(p->n_pair_reads)) : mcx_stream_mapped32(c, p->recs, p->cig);
             t_m_out += secs(tq, now());
             if (e && rc == 0) rc = e;
-            if (e == 0) parts_out++;
+            if (e == 0) { parts_out++; p->parts_out.push_back(second); }
         };
         if (!sharded) {
             if (n_pr && part_in()) { const Tick tq = now(); if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_pr, 1, avg, d_aln, d_cig, stats); t_m_dev += secs(tq, now()); each_dev.push_back(secs(tq, now())); part_out(false); }

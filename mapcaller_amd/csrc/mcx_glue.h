@@ -1285,11 +1285,12 @@ static inline MCX_HD void pair_stats(const Ctx &cx, PairState &st, DetailHdr *dh
     }
 }
 
-// one output record: the line GeneratePairedSamStream / GenerateSingleSamStream print for this
-// read in unique mode (SamReport.cpp:324-488).  cig: where the read's n_cig operations go (counted by
-// finish_scores, reserved in the batch's pool by the caller), cig_off: that place as a pool offset.
+// one output record: the line GeneratePairedSamStream / GenerateSingleSamStream print for candidate
+// `cand` of this read (SamReport.cpp:324-488; cand < 0: candidate `best`, the line of unique mode; -m prints
+// every later candidate that holds the best score too).  cig: where the read's n_cig operations go (counted
+// by finish_scores, reserved in the batch's pool by the caller), cig_off: that place as a pool offset.
 static inline MCX_HD void emit_record(const Ctx &cx, PairState &st, int s, const ReadRef *rd, AlnRec &dst,
-                                      uint32_t *cig, int n_cig, uint32_t cig_off, const uint32_t *staged = nullptr, int stage_stride = 1)
+                                      uint32_t *cig, int n_cig, uint32_t cig_off, const uint32_t *staged = nullptr, int stage_stride = 1, int cand = -1)
 {
     PairHdr &h = *st.hdr;
     const ReadSum me = h.sum[s];
@@ -1307,13 +1308,14 @@ static inline MCX_HD void emit_record(const Ctx &cx, PairState &st, int s, const
         dst = out;
         return;
     }
-    Cand c = st.cands[s][me.best];
+    Cand c = st.cands[s][cand < 0 ? me.best : cand];
     if (paired) {
         const Cand *oc = st.cands[1 - s];
         // flags are set for every surviving candidate when the best score is tied; the line
         // printed in unique mode is the first one, candidate `best`
         c.flag = paired_flag(c, oc, s == 0, me.score > me.sub);
-    } else c.flag = c.fwd ? 0 : 0x10; // SetSingledAlignmentFlag, SamReport.cpp:7-24
+    } else c.flag = c.fwd ? 0 : 0x10; // SetSingledAlignmentFlag, SamReport.cpp:7-24 (-m: the reference leaves the later tied lines' flag
+                                      // unset — DESIGN §6, deviation 4 —; they print the one its tie branch gives in unique mode)
     out.flag = c.flag;
     out.mapq = mapq_of(cx, me);
     Coord km = aln_coord(cx.ix, c, st.frags);
@@ -1340,6 +1342,36 @@ static inline MCX_HD void emit_record(const Ctx &cx, PairState &st, int s, const
         }
     }
     dst = out;
+}
+
+// -m (SamReport.cpp:364, :430, :478 with bUnique false): read s's lines after the first are the candidates behind
+// `best` that hold the best score, in candidate order.  Returns how many, and their CIGAR words in *words.
+static inline MCX_HD int extra_lines(const PairState &st, int s, const ReadRef *rd, int *words)
+{
+    const PairHdr &h = *st.hdr;
+    const ReadSum me = h.sum[s];
+    int n = 0, w = 0;
+    *words = 0;
+    if (me.score <= 0) return 0;
+    for (int k = me.best + 1; k < h.n_cands[s]; k++)
+        if (st.cands[s][k].score == me.score) { n++; w += cigar_of(rd[s].rlen, st.cands[s][k], st.frags, st.ops, nullptr, 0); }
+    *words = w;
+    return n;
+}
+
+// writes them: n records at ext[0..n), their CIGAR words at cig (pool offset cig_off on)
+static inline MCX_HD void emit_extra(const Ctx &cx, PairState &st, int s, const ReadRef *rd, AlnRec *ext, uint32_t *cig, uint32_t cig_off)
+{
+    const PairHdr &h = *st.hdr;
+    const ReadSum me = h.sum[s];
+    int at = 0;
+    uint32_t w = 0;
+    for (int k = me.best + 1; k < h.n_cands[s]; k++) {
+        if (st.cands[s][k].score != me.score) continue;
+        const int n_cig = cigar_of(rd[s].rlen, st.cands[s][k], st.frags, st.ops, nullptr, 0);
+        emit_record(cx, st, s, rd, ext[at++], cig + w, n_cig, cig_off + w, nullptr, 1, k);
+        w += (uint32_t)n_cig;
+    }
 }
 
 // copies what the profile stage needs of one read out of the pair state (which is reused by the

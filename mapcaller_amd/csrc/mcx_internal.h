@@ -31,6 +31,7 @@ int mcx_stage_in(mcx_ctx *, const uint8_t *bases, const uint32_t *off, uint32_t 
                  mcx_aln **d_aln, uint32_t **d_cigar);
 int mcx_stage_out(mcx_ctx *, uint32_t n_reads, mcx_aln *aln, uint32_t *cigar);
 bool mcx_ctx_has_profile(const mcx_ctx *);
+bool mcx_ctx_multi(const mcx_ctx *); // -m is on (mcx_ctx_set_multi)
 // something the file front end keeps with the context from call to call (its page-locked batch buffers): *slot, freed with
 // `drop` when the context goes
 void **mcx_ctx_files_slot(mcx_ctx *, void (*drop)(void *));

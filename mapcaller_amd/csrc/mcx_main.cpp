@@ -50,6 +50,7 @@ static void usage(const char *prog)
             "         -maxmm FLOAT  maximal mismatch rate in read alignment [0.05]\n"
             "         -vcf          VCF output filename [output.vcf]\n"
             "         -no_vcf       No VCF output\n"
+            "         -m            output multiple alignments: a SAM line for every alignment with the best score\n"
             "         -gvcf         GVCF mode\n"
             "         -monomorphic  report all loci which do not have any potential alternates\n"
             "         -ploidy INT   number of sets of chromosomes in a cell (1:monoploid, 2:diploid) [2]\n"
@@ -93,6 +94,7 @@ int main(int argc, char **argv)
     mcx_file_opts fo;
     mcx_file_opts_default(&fo);
     bool want_vcf = true; // bVCFoutput, main.cpp:171
+    bool multi = false;   // -m: a SAM line for every alignment with the best score
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -145,7 +147,8 @@ int main(int argc, char **argv)
         else if ((p == "-id" || p == "-label") && i + 1 < argc) vo.sample_id = argv[++i];
         else if (p == "-log" && i + 1 < argc) ++i;
         else if (p == "-v" || p == "--version") { fprintf(stderr, "MapCaller v0.9.9.41 (mapcaller-mi355x)\n\n"); return 0; } // main.cpp:310-314
-        else if (p == "-m" || p == "-bam") { fprintf(stderr, "Error! %s is not supported by mapcaller-mi355x (DESIGN.md, deliberate deviations)\n", argv[i]); return 1; }
+        else if (p == "-m") multi = true; // bUnique = false, main.cpp:308
+        else if (p == "-bam") { fprintf(stderr, "Error! %s is not supported by mapcaller-mi355x (DESIGN.md, deliberate deviations)\n", argv[i]); return 1; }
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
     }
     if (f1.empty()) { fprintf(stderr, "Warning! Please specify a valid read input!\n"); usage(argv[0]); return 0; }
@@ -210,6 +213,7 @@ int main(int argc, char **argv)
             if (want_vcf && r == 0) fprintf(stderr, "Initialize the alignment profile...\n");
             rc = mcx_ctx_create_fit(sh.ix, &o, want_vcf ? 1 : 0, paired_run ? 1 : 0, vo.max_dup, vo.max_clip, &sh.cx, want_vcf ? &sh.planes : nullptr, &fit);
         }
+        if (rc == 0 && multi) rc = mcx_ctx_set_multi(sh.cx, 1, 0);
         if (rc) bad(rc);
         if (n_gpus > 1) { // the shards cut ONE input stream into batches: they must agree on the batch
             int64_t mine = sh.rc ? -1 : fit.max_batch_reads;

@@ -2012,11 +2012,24 @@ __global__ void __launch_bounds__(256) k_dp_small(Ctx cx, JobSink sink, ReadBatc
     }
 }
 
+// -m: the lines of a read after its first (emit_extra) go to an extras pool that the finish kernel fills in no particular order; per read
+// {record offset, records, word offset, words} says where its lines went.  A re-run pair writes a fresh entry (what it took before is left
+// unreferenced); a pair that did not fit says so with kMxOver in its count and is mapped again once the pool has grown (multi_close).
+constexpr uint32_t kMxOver = 0x80000000u;
+struct MultiOut {
+    AlnRec *recs = nullptr; uint32_t *cig = nullptr; // the pool
+    uint32_t *cnt = nullptr;                          // [0] records taken, [1] CIGAR words taken (both count on past the capacity)
+    uint32_t rec_cap = 0, word_cap = 0;
+    uint4 *ref = nullptr;                             // per batch read
+};
+
 #ifndef MCX_FINISH_WAVES
 #define MCX_FINISH_WAVES 4 // (109 registers, no spills; five waves at 96 spilled 16)
 #endif
+// kMulti: -m — a read's lines after the first are counted and written in the same pass (the default instantiation never looks at mo)
+template <bool kMulti>
 __global__ void __launch_bounds__(256, MCX_FINISH_WAVES) k_finish(Ctx cx, ReadBatch rb, PairSel sel, AlnRec *recs, PairOut *pout, uint32_t *ov_ids, uint32_t *n_ov,
-                                                uint32_t ov_cap, uint32_t *pool_over, const uint32_t *order, const uint32_t *order_cnt)
+                                                uint32_t ov_cap, uint32_t *pool_over, const uint32_t *order, const uint32_t *order_cnt, MultiOut mo)
 {
     __shared__ EndsLds ends;
     __shared__ uint32_t cig_stage[256 * 2 * kCigStage]; // the first operations of every read, word-major: word k of thread t at [k * 256 + t] (neighbouring lanes, neighbouring banks)
@@ -2045,11 +2058,28 @@ __global__ void __launch_bounds__(256, MCX_FINISH_WAVES) k_finish(Ctx cx, ReadBa
     }
     const uint32_t want = (uint32_t)(n_cig[0] + n_cig[1]);
     const uint32_t at = wave_reserve(cx.cig_pool_n, want);
+    // (-m) the extra lines of the pair's reads: counted here, reserved like the CIGAR words — one atomic per wavefront for each count
+    const bool own = active && !(h.flags & (kDispatched | kOvAny));
+    int n_ext[2] = {0, 0}, n_extw[2] = {0, 0};
+    uint32_t at_ext = 0, at_extw = 0;
+    if (kMulti) {
+        if (own) for (int s = 0; s < nr; s++) n_ext[s] = extra_lines(st, s, rd, &n_extw[s]);
+        at_ext = wave_reserve(mo.cnt, (uint32_t)(n_ext[0] + n_ext[1]));
+        at_extw = wave_reserve(mo.cnt + 1, (uint32_t)(n_extw[0] + n_extw[1]));
+    }
     if (!active || (h.flags & kDispatched)) return; // (a dispatched pair is the large tier's: its records and summary come from there)
     const bool fits = at + want <= cx.cig_pool_cap;
     if (!fits) atomicOr(pool_over, 1u);
     const uint32_t off[2] = {at, at + (uint32_t)n_cig[0]};
     finish_records(cx, st, rd, recs + (int64_t)pair * nr, fits ? cx.cig_pool : nullptr, off, n_cig, detail2, stage, 256);
+    if (kMulti && own) {
+        const bool room = at_ext + (uint32_t)(n_ext[0] + n_ext[1]) <= mo.rec_cap && at_extw + (uint32_t)(n_extw[0] + n_extw[1]) <= mo.word_cap;
+        for (int s = 0; s < nr; s++) {
+            const uint32_t ro = at_ext + (s ? (uint32_t)n_ext[0] : 0u), wo = at_extw + (s ? (uint32_t)n_extw[0] : 0u);
+            mo.ref[(int64_t)pair * nr + s] = room || n_ext[0] + n_ext[1] == 0 ? make_uint4(ro, (uint32_t)n_ext[s], wo, (uint32_t)n_extw[s]) : make_uint4(0u, (uint32_t)n_ext[s] | kMxOver, 0u, 0u);
+            if (room && n_ext[s]) emit_extra(cx, st, s, rd, mo.recs + ro, mo.cig + wo, wo);
+        }
+    }
     PairOut o;
     o.flags = h.flags; o.est = h.est; o.est_lo = h.est_lo; o.est_hi = h.est_hi;
     o.pair_dist = h.pair_dist; o.pair_ok = (int16_t)h.pair_ok; o.mapped = (int16_t)h.mapped;
@@ -2242,7 +2272,14 @@ struct mcx_ctx {
         uint32_t *h_err = nullptr; // pinned: d_err's word on its way out with the batch's records (mcx_stream_mapped / _mapped32 -> mcx_stream_collect)
         uint32_t *d_prepack = nullptr, *d_any_n = nullptr; bool prepacked = false; int pre_paired = 0; // k_pack_reads' output made on the way in
         hipEvent_t in_ready = nullptr, mapped = nullptr, out_done = nullptr;
+        // -m: the batch's extras on their way out with its records (slot_multi_out): in read order, the records as mcx_aln32
+        struct Extras {
+            bool have = false; uint32_t n_reads = 0, n_recs = 0, n_words = 0;
+            uint32_t *d_index = nullptr, *d_cig = nullptr; mcx_aln32 *d_recs = nullptr; uint32_t rec_cap = 0, word_cap = 0;
+            uint32_t *h_index = nullptr, *h_cig = nullptr; mcx_aln32 *h_recs = nullptr; uint32_t h_rec_cap = 0, h_word_cap = 0;
+        } mx;
     } slot[3];
+    const Slot *collected = nullptr; // the slot mcx_stream_collect handed over last (mcx_stream_multi)
     hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
     uint64_t stream_seq = 0, stream_bytes_in = 0, stream_bytes_out = 0;
     void *d_scan_tmp = nullptr; size_t scan_tmp_bytes = 0; // the prefix sum of the read lengths (mcx_stream_submit_packed)
@@ -2250,7 +2287,25 @@ struct mcx_ctx {
     // staging for the host-buffer entry point
     uint8_t *d_bases = nullptr; uint32_t *d_off = nullptr; AlnRec *d_recs = nullptr; uint32_t *d_cig = nullptr;
     hipEvent_t ev[12];
+    // -m (mcx_ctx_set_multi): the extras pool k_finish<true> fills, and the last batch's extras in read order (multi_close)
+    struct Multi {
+        bool on = false, ready = false;
+        uint32_t rec_cap = 0, word_cap = 0;            // the pool's
+        AlnRec *d_pool = nullptr; uint32_t *d_pool_cig = nullptr; uint32_t *d_cnt = nullptr; uint4 *d_ref = nullptr;
+        uint32_t *d_counts = nullptr;                  // records | words per read, [2][max_reads + 1], scanned into d_index | d_windex
+        uint32_t *d_index = nullptr, *d_windex = nullptr;
+        AlnRec *d_out = nullptr; uint32_t *d_out_cig = nullptr; uint32_t out_cap = 0, out_wcap = 0;
+        void *d_tmp = nullptr; size_t tmp_bytes = 0;
+        uint32_t n_reads = 0, n_recs = 0, n_words = 0;  // the last batch's
+    } mx;
 };
+
+static MultiOut multi_out(const mcx_ctx *c)
+{
+    MultiOut m;
+    m.recs = c->mx.d_pool; m.cig = c->mx.d_pool_cig; m.cnt = c->mx.d_cnt; m.rec_cap = c->mx.rec_cap; m.word_cap = c->mx.word_cap; m.ref = c->mx.d_ref;
+    return m;
+}
 
 extern "C" void mcx_opts_default(mcx_opts *o)
 {
@@ -2530,11 +2585,15 @@ extern "C" void mcx_ctx_free(mcx_ctx *c)
         if (L.keep_stream) (void)hipStreamDestroy(L.keep_stream);
     }
     if (c->h_early) (void)hipHostFree((void *)c->h_early);
+    for (void *q : {(void *)c->mx.d_pool, (void *)c->mx.d_pool_cig, (void *)c->mx.d_cnt, (void *)c->mx.d_ref, (void *)c->mx.d_counts, (void *)c->mx.d_index,
+                    (void *)c->mx.d_windex, (void *)c->mx.d_out, (void *)c->mx.d_out_cig, c->mx.d_tmp}) if (q) (void)hipFree(q);
     if (c->tail.d) (void)hipFree(c->tail.d);
     if (c->tail.h) (void)hipHostFree(c->tail.h);
     for (auto &sl : c->slot) {
-        void *q[] = {sl.d_bases, sl.d_off, sl.d_recs, sl.d_cig, sl.d_codes, sl.d_len, sl.d_odd, sl.d_err, sl.d_recs32, sl.d_prepack, sl.d_any_n};
+        void *q[] = {sl.d_bases, sl.d_off, sl.d_recs, sl.d_cig, sl.d_codes, sl.d_len, sl.d_odd, sl.d_err, sl.d_recs32, sl.d_prepack, sl.d_any_n,
+                     sl.mx.d_index, sl.mx.d_cig, sl.mx.d_recs};
         for (void *x : q) if (x) (void)hipFree(x);
+        mcx_pinned_free(sl.mx.h_index); mcx_pinned_free(sl.mx.h_cig); mcx_pinned_free(sl.mx.h_recs);
         if (sl.h_err) (void)hipHostFree(sl.h_err);
         for (hipEvent_t e : {sl.in_ready, sl.mapped, sl.out_done}) if (e) (void)hipEventDestroy(e);
     }
@@ -2889,7 +2948,8 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
     if (timing) HIP_TRY(hipEventRecord(R.ev[e++], s));
     if ((rc2 = launch_dp(kn, R, cx, sinks, rb, sel, c->rlen_max))) return rc2;
     if (timing) HIP_TRY(hipEventRecord(R.ev[e++], s));
-    k_finish<<<pb, 256, 0, s>>>(cx, rb, sel, d_recs, c->d_pout, R.d_ov, R.d_cnt + CNT_OV, R.ov_cap, c->d_batch_flags + 2, order, order_cnt);
+    if (c->mx.on) k_finish<true><<<pb, 256, 0, s>>>(cx, rb, sel, d_recs, c->d_pout, R.d_ov, R.d_cnt + CNT_OV, R.ov_cap, c->d_batch_flags + 2, order, order_cnt, multi_out(c));
+    else k_finish<false><<<pb, 256, 0, s>>>(cx, rb, sel, d_recs, c->d_pout, R.d_ov, R.d_cnt + CNT_OV, R.ov_cap, c->d_batch_flags + 2, order, order_cnt, MultiOut());
     if (timing) HIP_TRY(hipEventRecord(R.ev[e++], s));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(R.h_cnt, R.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -3111,6 +3171,13 @@ __global__ void k_chunk_sums(const PairOut *po, const uint32_t *off, uint32_t n_
 }
 
 // pairs whose chunk estimate lies outside their validity interval -> redo list (avg_replay's test)
+// (-m) the reads of listed pairs have no extra lines (yet)
+__global__ void __launch_bounds__(256) k_mx_clear(const uint32_t *ids, uint32_t n, int nr, uint4 *ref)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        for (int s = 0; s < nr; s++) ref[(int64_t)ids[i] * nr + s] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 __global__ void k_check_est(const PairOut *po, uint32_t n_pairs, uint32_t chunk, const int32_t *est_chunk, uint32_t *redo_ids,
                             int32_t *redo_est, uint32_t *n_redo, uint32_t cap)
 {
@@ -3248,6 +3315,11 @@ static int run_selection(mcx_ctx *c, const ReadBatch &rb, int paired, const std:
     }
     if (est) HIP_TRY(hipMemcpyAsync(c->d_est, est->data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     else k_fill_i32<<<(n + 255) / 256, 256, 0, s>>>(c->d_est, est_all, n);
+    if (c->mx.on) { // (-m) the selection's reads have no extra lines until k_finish<true> says otherwise: a pair that k_simple finishes this time keeps none from an earlier pass
+        const int nr = paired ? 2 : 1;
+        if (ids) k_mx_clear<<<(n + 255) / 256, 256, 0, s>>>(c->d_sel_ids, n, nr, c->mx.d_ref);
+        else HIP_TRY(hipMemsetAsync(c->mx.d_ref, 0, (size_t)n * nr * sizeof(uint4), s));
+    }
     const PassRes R0 = res_tier0(c);
     int rc = run_pairs(c, 0, R0, rb, paired, sel, d_recs, d_cig, stats, timing, true);
     // (the batch's tail, if the pass queued it, stands only when the pass is all there was: no halves, no pairs left for the large tier)
@@ -3382,6 +3454,8 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     br.mapped = 0; br.sums_valid = false; br.d_ok = br.d_ds = nullptr;
     c->tail.queued = c->tail.ran = false;
     HIP_TRY(hipMemsetAsync(c->d_batch_flags, 0, 4 * sizeof(uint32_t), s));
+    c->mx.ready = false;
+    if (c->mx.on) HIP_TRY(hipMemsetAsync(c->mx.d_cnt, 0, 4 * sizeof(uint32_t), s)); // (-m: the extras pool starts empty with every batch)
     c->last_paired = paired ? 1 : 0;
     if (vouched) c->h_cnt[1] = (uint32_t)c->rlen_max; // (vouched for: no kernel, no wait at the start of the step — under the copies of the neighbouring batches such a wait takes milliseconds)
     else { // every read must fit the slots the context was sized for
@@ -3560,11 +3634,177 @@ extern "C" void mcx_avg_advance(int64_t st[3], int64_t pairs, int64_t dist, int6
     if (n_chunks > 0 && st[1] > 1000) st[0] = (int64_t)(uint32_t)(int)(1. * (double)st[2] / (double)st[1] + .5);
 }
 
+// ---- -m: the extras of a batch in read order --------------------------------------------------------
+// The finish kernel filled the pool in whatever order its wavefronts ran; per read it left {record offset, records, word offset, words}.
+// count -> exclusive scan -> gather (the way k_dp_sort_count / _scan / _place order the DP lists) puts every read's lines behind the
+// lines of the reads before it, and its CIGAR words likewise: the result does not depend on the order the pool was filled in.
+__global__ void __launch_bounds__(256) k_mx_count(const uint4 *ref, uint32_t n_reads, uint32_t *recs, uint32_t *words)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += gridDim.x * blockDim.x) {
+        const uint4 e = r < n_reads ? ref[r] : make_uint4(0u, 0u, 0u, 0u);
+        recs[r] = e.y; words[r] = e.w;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_mx_gather(const uint4 *ref, uint32_t n_reads, const uint32_t *index, const uint32_t *windex, const AlnRec *pool,
+                                                   const uint32_t *pool_cig, AlnRec *out, uint32_t *out_cig)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += gridDim.x * blockDim.x) {
+        const uint4 e = ref[r];
+        const uint32_t at = index[r], wat = windex[r];
+        for (uint32_t i = 0; i < e.y; i++) {
+            AlnRec a = pool[e.x + i];
+            a.pad[0] = (int32_t)(wat + ((uint32_t)a.pad[0] - e.z)); // cigar_off: into the ordered words
+            out[at + i] = a;
+        }
+        for (uint32_t j = 0; j < e.w; j++) out_cig[wat + j] = pool_cig[e.z + j];
+    }
+}
+
+// the pairs whose extras did not fit the pool, with the estimate they were mapped with (they are mapped again as they were)
+__global__ void __launch_bounds__(256) k_mx_over(const uint4 *ref, uint32_t n_pairs, int nr, const PairOut *po, uint32_t *ids, int32_t *est, uint32_t *n, uint32_t cap)
+{
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pairs; p += gridDim.x * blockDim.x) {
+        bool over = false;
+        for (int s = 0; s < nr; s++) over |= (ref[(int64_t)p * nr + s].y & kMxOver) != 0;
+        if (over) { const uint32_t at = atomicAdd(n, 1u); if (at < cap) { ids[at] = p; est[at] = po[p].est; } }
+    }
+}
+
+static int mx_alloc_pool(mcx_ctx *c, uint32_t recs, uint32_t words, bool keep)
+{
+    auto &m = c->mx;
+    AlnRec *p = nullptr; uint32_t *w = nullptr;
+    int rc;
+    if ((rc = dmalloc(&p, recs))) return rc;
+    if ((rc = dmalloc(&w, words))) { (void)hipFree(p); return rc; }
+    if (keep && m.d_pool) { // (what the batch's pairs wrote so far stays where their entries point)
+        HIP_TRY(hipMemcpyAsync(p, m.d_pool, (size_t)std::min(m.rec_cap, recs) * sizeof(AlnRec), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(w, m.d_pool_cig, (size_t)std::min(m.word_cap, words) * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (m.d_pool) (void)hipFree(m.d_pool);
+    if (m.d_pool_cig) (void)hipFree(m.d_pool_cig);
+    m.d_pool = p; m.d_pool_cig = w; m.rec_cap = recs; m.word_cap = words;
+    return 0;
+}
+
+extern "C" int mcx_ctx_set_multi(mcx_ctx *c, int on, uint32_t extra_cap)
+{
+    if (!c) return fail(MCX_ERR_ARG, "mcx_ctx_set_multi: null argument");
+    if (c->run.open) return fail(MCX_ERR_ARG, "mcx_ctx_set_multi: a batch is in flight");
+    HIP_TRY(hipSetDevice(c->idx->device));
+    auto &m = c->mx;
+    m.on = on != 0; m.ready = false;
+    if (!m.on) return 0;
+    int rc;
+    const uint64_t nr1 = c->max_reads + 1;
+    if (!m.d_ref) {
+        if ((rc = dmalloc(&m.d_ref, c->max_reads))) return rc;
+        if ((rc = dmalloc(&m.d_cnt, 4))) return rc;
+        if ((rc = dmalloc(&m.d_counts, 2 * nr1))) return rc;
+        if ((rc = dmalloc(&m.d_index, nr1))) return rc;
+        if ((rc = dmalloc(&m.d_windex, nr1))) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, m.tmp_bytes, m.d_counts, m.d_index, (int64_t)nr1));
+        if ((rc = dmalloc((uint8_t **)&m.d_tmp, m.tmp_bytes))) return rc;
+    }
+    // (default: a line for every 16th read — the bench genome's batches need far fewer —, eight CIGAR words a line; a batch that needs more makes it grow)
+    const uint32_t recs = std::min<uint32_t>(extra_cap ? extra_cap : (uint32_t)std::max<uint64_t>(4096, c->max_reads / 16), 1u << 28);
+    const uint32_t words = recs * 8u; // (below 2^31)
+    if (recs != m.rec_cap || words != m.word_cap) return mx_alloc_pool(c, recs, words, false);
+    return 0;
+}
+
+// (-m, at the close of a batch) pairs whose extras did not fit are mapped again into a grown pool; then the extras are put in read order
+static int multi_close(mcx_ctx *c)
+{
+    auto &m = c->mx;
+    BatchRun &br = c->run;
+    hipStream_t s = c->stream;
+    const uint32_t n_reads = br.rb.n_reads, nr = br.paired ? 2 : 1;
+    int rc;
+    for (int round = 0;; round++) {
+        uint32_t h[4];
+        HIP_TRY(hipMemcpyAsync(h, m.d_cnt, sizeof h, hipMemcpyDeviceToHost, s)); // (behind the batch's last finish kernel)
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h[0] <= m.rec_cap && h[1] <= m.word_cap) break;
+        if (round == 4) return fail(MCX_ERR_CAPACITY, "-m: the extras pool did not settle");
+        // everything taken so far (stale entries of re-run pairs included) plus as much again for the pairs that are mapped again
+        const uint32_t recs = std::max(m.rec_cap, 2 * h[0] + 1024), words = std::max(m.word_cap, 2 * h[1] + 8192);
+        if (c->kn.timing || getenv("MCX_ALLOC_LOG")) fprintf(stderr, "[mcx] the -m extras pool grows from %u to %u lines (%u to %u CIGAR words): the batch asked for %u lines, %u words\n",
+                                                             m.rec_cap, recs, m.word_cap, words, h[0], h[1]);
+        if ((rc = mx_alloc_pool(c, recs, words, true))) return rc;
+        HIP_TRY(hipMemsetAsync(m.d_cnt + 2, 0, 4, s));
+        k_mx_over<<<(br.n_pairs + 255) / 256, 256, 0, s>>>(m.d_ref, br.n_pairs, (int)nr, c->d_pout, c->d_sel_ids, c->d_est, m.d_cnt + 2, c->ov_cap);
+        HIP_TRY(hipGetLastError());
+        uint32_t n_over = 0;
+        HIP_TRY(hipMemcpyAsync(&n_over, m.d_cnt + 2, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n_over && (rc = replay_listed(c, n_over, nullptr))) return rc;
+    }
+    if ((uint64_t)n_reads + 1 > c->max_reads + 1) return fail(MCX_ERR_ARG, "-m: batch larger than the context");
+    uint32_t *cr = m.d_counts, *cw = m.d_counts + c->max_reads + 1;
+    const unsigned gb = std::min<uint32_t>(4096u, (n_reads + 256) / 256);
+    k_mx_count<<<gb, 256, 0, s>>>(m.d_ref, n_reads, cr, cw);
+    HIP_TRY(hipGetLastError());
+    size_t tb = m.tmp_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(m.d_tmp, tb, cr, m.d_index, (int64_t)n_reads + 1, s));
+    tb = m.tmp_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(m.d_tmp, tb, cw, m.d_windex, (int64_t)n_reads + 1, s));
+    uint32_t tot[2];
+    HIP_TRY(hipMemcpyAsync(&tot[0], m.d_index + n_reads, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&tot[1], m.d_windex + n_reads, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (tot[0] > m.out_cap || tot[1] > m.out_wcap) {
+        if (m.d_out) (void)hipFree(m.d_out);
+        if (m.d_out_cig) (void)hipFree(m.d_out_cig);
+        m.d_out = nullptr; m.d_out_cig = nullptr; m.out_cap = m.out_wcap = 0;
+        const uint32_t want = std::max(tot[0], m.rec_cap / 4), wwant = std::max(tot[1], m.word_cap / 4);
+        if ((rc = dmalloc(&m.d_out, (size_t)want + 1))) return rc;
+        if ((rc = dmalloc(&m.d_out_cig, (size_t)wwant + 1))) return rc;
+        m.out_cap = want; m.out_wcap = wwant;
+    }
+    if (tot[0]) k_mx_gather<<<gb, 256, 0, s>>>(m.d_ref, n_reads, m.d_index, m.d_windex, m.d_pool, m.d_pool_cig, m.d_out, m.d_out_cig);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    m.n_reads = n_reads; m.n_recs = tot[0]; m.n_words = tot[1]; m.ready = true;
+    return 0;
+}
+
+extern "C" int mcx_multi_lines(mcx_ctx *c, const uint32_t **d_index, const mcx_aln **d_recs, const uint32_t **d_cigar, uint32_t *n_recs, uint32_t *n_words)
+{
+    if (!c) return fail(MCX_ERR_ARG, "mcx_multi_lines: null argument");
+    if (!c->mx.on || !c->mx.ready) return fail(MCX_ERR_ARG, "mcx_multi_lines: no batch was mapped with -m on (mcx_ctx_set_multi)");
+    if (d_index) *d_index = c->mx.d_index;
+    if (d_recs) *d_recs = (const mcx_aln *)c->mx.d_out;
+    if (d_cigar) *d_cigar = c->mx.d_out_cig;
+    if (n_recs) *n_recs = c->mx.n_recs;
+    if (n_words) *n_words = c->mx.n_words;
+    return 0;
+}
+
+extern "C" int mcx_multi_copy(mcx_ctx *c, uint32_t *index, mcx_aln *recs, uint32_t *cigar)
+{
+    if (!c || !index) return fail(MCX_ERR_ARG, "mcx_multi_copy: null argument");
+    if (!c->mx.on || !c->mx.ready) return fail(MCX_ERR_ARG, "mcx_multi_copy: no batch was mapped with -m on (mcx_ctx_set_multi)");
+    const auto &m = c->mx;
+    if ((m.n_recs && !recs) || (m.n_words && !cigar)) return fail(MCX_ERR_ARG, "mcx_multi_copy: null argument");
+    HIP_TRY(hipSetDevice(c->idx->device));
+    HIP_TRY(hipMemcpyAsync(index, m.d_index, ((size_t)m.n_reads + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (m.n_recs) HIP_TRY(hipMemcpyAsync(recs, m.d_out, (size_t)m.n_recs * sizeof(AlnRec), hipMemcpyDeviceToHost, c->stream));
+    if (m.n_words) HIP_TRY(hipMemcpyAsync(cigar, m.d_out_cig, (size_t)m.n_words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+bool mcx_ctx_multi(const mcx_ctx *c) { return c->mx.on; }
+
 // what both ways of closing a batch share: the long-CIGAR pool, statistics
 static int batch_close(mcx_ctx *c, mcx_stats *stats)
 {
     BatchRun &br = c->run;
     int rc = 0;
+    if (c->mx.on && (rc = multi_close(c))) return rc; // (-m: before the sums — pairs it maps again mark them stale)
     if (!br.sums_valid && (rc = mcx_batch_sums(c, nullptr, nullptr, nullptr, nullptr))) return rc;
     {
         uint32_t fl[4] = {0, 0, 0, 0};
@@ -3950,6 +4190,7 @@ extern "C" int mcx_stream_submit(mcx_ctx *c, const uint8_t *bases, const uint32_
 // the oldest submitted batch, in HBM once the context's stream gets there
 extern "C" int mcx_stream_next(mcx_ctx *c, const uint8_t **d_bases, const uint32_t **d_off, uint32_t *n_reads, mcx_aln **d_aln, uint32_t **d_cigar)
 {
+    if (c) c->mx.ready = false; // (-m: the extras in the context are of a batch before this one)
     if (!c || !d_bases || !d_off || !d_aln || !d_cigar) return fail(MCX_ERR_ARG, "mcx_stream_next: null argument");
     HIP_TRY(hipSetDevice(c->idx->device));
     if (oldest_slot(c, 2)) return fail(MCX_ERR_ARG, "mcx_stream_next: the previous batch was not handed back (mcx_stream_mapped)");
@@ -3966,6 +4207,75 @@ extern "C" int mcx_stream_next(mcx_ctx *c, const uint8_t **d_bases, const uint32
     return 0;
 }
 
+__global__ void __launch_bounds__(256) k_pack_recs(const AlnRec *recs, uint32_t n, mcx_aln32 *out);
+
+// (-m) the batch's extras, in read order in the context's buffers until its next batch begins, go into the slot's own on the
+// mapping stream (packed to mcx_aln32 like the records) — behind its `mapped` event their copy out joins the records'
+static int slot_multi_pack(mcx_ctx *c, mcx_ctx::Slot *sl)
+{
+    auto &o = sl->mx;
+    const auto &m = c->mx;
+    o.have = m.on && m.ready && m.n_reads == sl->n_reads;
+    if (!o.have) { o.n_reads = o.n_recs = o.n_words = 0; return 0; }
+    int rc;
+    if (!o.d_index && (rc = dmalloc(&o.d_index, c->max_reads + 1))) return rc;
+    if (m.n_recs > o.rec_cap) {
+        if (o.d_recs) (void)hipFree(o.d_recs);
+        o.d_recs = nullptr; o.rec_cap = 0;
+        if ((rc = dmalloc(&o.d_recs, (size_t)m.n_recs + m.n_recs / 2 + 1024))) return rc;
+        o.rec_cap = m.n_recs + m.n_recs / 2 + 1024;
+    }
+    if (m.n_words > o.word_cap) {
+        if (o.d_cig) (void)hipFree(o.d_cig);
+        o.d_cig = nullptr; o.word_cap = 0;
+        if ((rc = dmalloc(&o.d_cig, (size_t)m.n_words + m.n_words / 2 + 4096))) return rc;
+        o.word_cap = m.n_words + m.n_words / 2 + 4096;
+    }
+    o.n_reads = m.n_reads; o.n_recs = m.n_recs; o.n_words = m.n_words;
+    HIP_TRY(hipMemcpyAsync(o.d_index, m.d_index, ((size_t)o.n_reads + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (o.n_words) HIP_TRY(hipMemcpyAsync(o.d_cig, m.d_out_cig, (size_t)o.n_words * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (o.n_recs) k_pack_recs<<<(o.n_recs + 255) / 256, 256, 0, c->stream>>>(m.d_out, o.n_recs, o.d_recs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ... and their copy to the slot's page-locked buffers on the copy-out stream (counted in bytes_out)
+static int slot_multi_out(mcx_ctx *c, mcx_ctx::Slot *sl)
+{
+    auto &o = sl->mx;
+    if (!o.have) return 0;
+    if (!o.h_index) { o.h_index = (uint32_t *)mcx_pinned_alloc((c->max_reads + 1) * 4); if (!o.h_index) return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
+    if (o.n_recs > o.h_rec_cap) {
+        mcx_pinned_free(o.h_recs); o.h_rec_cap = o.rec_cap;
+        if (!(o.h_recs = (mcx_aln32 *)mcx_pinned_alloc((size_t)o.h_rec_cap * sizeof(mcx_aln32)))) { o.h_rec_cap = 0; return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
+    }
+    if (o.n_words > o.h_word_cap) {
+        mcx_pinned_free(o.h_cig); o.h_word_cap = o.word_cap;
+        if (!(o.h_cig = (uint32_t *)mcx_pinned_alloc((size_t)o.h_word_cap * 4))) { o.h_word_cap = 0; return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
+    }
+    const size_t b_index = ((size_t)o.n_reads + 1) * 4, b_recs = (size_t)o.n_recs * sizeof(mcx_aln32), b_cig = (size_t)o.n_words * 4;
+    HIP_TRY(hipMemcpyAsync(o.h_index, o.d_index, b_index, hipMemcpyDeviceToHost, c->d2h_stream));
+    if (b_recs) HIP_TRY(hipMemcpyAsync(o.h_recs, o.d_recs, b_recs, hipMemcpyDeviceToHost, c->d2h_stream));
+    if (b_cig) HIP_TRY(hipMemcpyAsync(o.h_cig, o.d_cig, b_cig, hipMemcpyDeviceToHost, c->d2h_stream));
+    c->stream_bytes_out += b_index + b_recs + b_cig;
+    return 0;
+}
+
+extern "C" int mcx_stream_multi(mcx_ctx *c, const uint32_t **index, const mcx_aln32 **recs, const uint32_t **cigar, uint32_t *n_reads, uint32_t *n_recs, uint32_t *n_words)
+{
+    if (!c) return fail(MCX_ERR_ARG, "mcx_stream_multi: null argument");
+    if (!c->mx.on) return fail(MCX_ERR_ARG, "mcx_stream_multi: -m is off (mcx_ctx_set_multi)");
+    const mcx_ctx::Slot *sl = c->collected;
+    const bool have = sl && sl->mx.have;
+    if (index) *index = have ? sl->mx.h_index : nullptr;
+    if (recs) *recs = have ? sl->mx.h_recs : nullptr;
+    if (cigar) *cigar = have ? sl->mx.h_cig : nullptr;
+    if (n_reads) *n_reads = have ? sl->mx.n_reads : 0;
+    if (n_recs) *n_recs = have ? sl->mx.n_recs : 0;
+    if (n_words) *n_words = have ? sl->mx.n_words : 0;
+    return 0;
+}
+
 // the batch mcx_stream_next gave out is mapped: its results start their way to host memory
 extern "C" int mcx_stream_mapped(mcx_ctx *c, mcx_aln *aln, uint32_t *cigar)
 {
@@ -3973,10 +4283,12 @@ extern "C" int mcx_stream_mapped(mcx_ctx *c, mcx_aln *aln, uint32_t *cigar)
     HIP_TRY(hipSetDevice(c->idx->device));
     mcx_ctx::Slot *sl = oldest_slot(c, 2);
     if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_mapped: no batch is being mapped");
+    int rc;
+    if ((rc = slot_multi_pack(c, sl))) return rc;
     HIP_TRY(hipEventRecord(sl->mapped, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl->mapped, 0));
     const size_t rec_bytes = (size_t)sl->n_reads * sizeof(AlnRec), cig_bytes = (size_t)c->run.cig_words * 4; // (the pool's used words only)
-    int rc;
+    if ((rc = slot_multi_out(c, sl))) return rc;
     if ((rc = bulk_copy(c, aln, sl->d_recs, rec_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
     if ((rc = bulk_copy(c, cigar, sl->d_cig, cig_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
     if (sl->lens_checked) HIP_TRY(hipMemcpyAsync(sl->h_err, sl->d_err, 4, hipMemcpyDeviceToHost, c->d2h_stream)); // what k_unpack_reads thought of the caller's lengths: mcx_stream_collect reads it
@@ -4012,9 +4324,11 @@ extern "C" int mcx_stream_mapped32(mcx_ctx *c, mcx_aln32 *aln, uint32_t *cigar)
     if (!sl->d_recs32 && (rc = dmalloc(&sl->d_recs32, c->max_reads))) return rc;
     k_pack_recs<<<(sl->n_reads + 255) / 256, 256, 0, c->stream>>>(sl->d_recs, sl->n_reads, sl->d_recs32); // (a read's operations are at most MCX_CIGAR_STRIDE x the pool's slack: far below 2^16)
     HIP_TRY(hipGetLastError());
+    if ((rc = slot_multi_pack(c, sl))) return rc;
     HIP_TRY(hipEventRecord(sl->mapped, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl->mapped, 0));
     const size_t rec_bytes = (size_t)sl->n_reads * sizeof(mcx_aln32), cig_bytes = (size_t)c->run.cig_words * 4; // (the pool's used words only)
+    if ((rc = slot_multi_out(c, sl))) return rc;
     if ((rc = bulk_copy(c, aln, sl->d_recs32, rec_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
     if ((rc = bulk_copy(c, cigar, sl->d_cig, cig_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
     if (sl->lens_checked) HIP_TRY(hipMemcpyAsync(sl->h_err, sl->d_err, 4, hipMemcpyDeviceToHost, c->d2h_stream));
@@ -4051,6 +4365,7 @@ extern "C" int mcx_stream_collect(mcx_ctx *c, uint64_t *bytes_in, uint64_t *byte
     if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_collect: no mapped batch is on its way out");
     HIP_TRY(hipEventSynchronize(sl->out_done));
     sl->state = 0;
+    c->collected = sl;
     if (bytes_in) *bytes_in = c->stream_bytes_in;
     if (bytes_out) *bytes_out = c->stream_bytes_out;
     if (sl->lens_checked && sl->h_err && *sl->h_err) { // the two-half form (mcx_stream_next + mcx_map_batch_dev / mcx_batch_* + mcx_stream_mapped): the refusal arrives with the records

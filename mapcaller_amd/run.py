@@ -36,6 +36,7 @@ def parse(argv):
     ap.add_argument("-sam", default=None)
     ap.add_argument("-vcf", default="output.vcf")
     ap.add_argument("-no_vcf", action="store_true")
+    ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
     ap.add_argument("-t", dest="threads", type=int, default=0, help="host threads per process for parsing / SAM text")
     ap.add_argument("-batch", type=int, default=1 << 20, help="reads per batch (the unit dealt to the ranks)")
     ap.add_argument("-maxlen", type=int, default=0, help="longest read the contexts are sized for [sampled from the first reads, 256..1000]")
@@ -92,7 +93,7 @@ def main(argv=None):
     if a.maxlen <= 0:
         a.maxlen = min(1000, max(256, (max(sample_read_length(f) for f in a.f1 + a.f2) + 63) // 64 * 64))
     index = api.Index(a.index, device=device, full_sa=True)
-    mapper = api.Mapper(index, alg=a.alg, max_read_len=a.maxlen, max_batch_reads=max(200, a.batch // 200 * 200))
+    mapper = api.Mapper(index, alg=a.alg, max_read_len=a.maxlen, max_batch_reads=max(200, a.batch // 200 * 200), multi=a.multi)
     want_vcf = not a.no_vcf
     planes = None
     if want_vcf:
