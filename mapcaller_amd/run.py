@@ -37,6 +37,8 @@ def parse(argv):
     ap.add_argument("-vcf", default="output.vcf")
     ap.add_argument("-no_vcf", action="store_true")
     ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
+    ap.add_argument("-indel", type=int, default=30, help="maximal indel size (MaxPosDiff), at most 100")
+    ap.add_argument("-maxmm", type=float, default=0.05, help="maximal mismatch rate in read alignment (MaxMisMatchRate)")
     ap.add_argument("-t", dest="threads", type=int, default=0, help="host threads per process for parsing / SAM text")
     ap.add_argument("-batch", type=int, default=1 << 20, help="reads per batch (the unit dealt to the ranks)")
     ap.add_argument("-maxlen", type=int, default=0, help="longest read the contexts are sized for [sampled from the first reads, 256..1000]")
@@ -54,7 +56,16 @@ def parse(argv):
     a = ap.parse_args(argv)
     if a.f2 and len(a.f2) != len(a.f1):
         ap.error("Paired-end reads input numbers do not match!")
+    if a.indel > 100:  # main.cpp:251-253
+        print("Warning! The maximal indel size is 100!", file=sys.stderr)
+        a.indel = 100
     return a
+
+
+def mapper_kwargs(a):
+    """What of the command line goes into every mapping context (api.Mapper)."""
+    return dict(alg=a.alg, max_read_len=a.maxlen, max_batch_reads=max(200, a.batch // 200 * 200), multi=a.multi,
+                max_pos_diff=a.indel, max_mismatch_rate=a.maxmm)
 
 
 def sample_read_length(path, lines=40000):
@@ -93,7 +104,7 @@ def main(argv=None):
     if a.maxlen <= 0:
         a.maxlen = min(1000, max(256, (max(sample_read_length(f) for f in a.f1 + a.f2) + 63) // 64 * 64))
     index = api.Index(a.index, device=device, full_sa=True)
-    mapper = api.Mapper(index, alg=a.alg, max_read_len=a.maxlen, max_batch_reads=max(200, a.batch // 200 * 200), multi=a.multi)
+    mapper = api.Mapper(index, **mapper_kwargs(a))
     want_vcf = not a.no_vcf
     planes = None
     if want_vcf:

@@ -8,7 +8,7 @@
 // Parity status: PINNED.  The restatement is validated against the real reference compiled from
 // its own sources into oracle/_ref (oracle/Makefile `make ref`): function level through
 // oracle/ref_shim.cpp (BWT_Search, bwt_sa, nw_alignment, ksw2_alignment, ksw_extz2_sse) and end
-// to end through `_ref/MapCaller -t 1 -sam` (tests/test_oracle_vs_ref.py, tests/golden/*).
+// to end through `_ref/MapCaller -t 1 -sam` (tests/test_oracle_golden.py, tests/test_options.py, tests/golden/*).
 //
 // Each function names the reference lines it restates.  Data structures are our own
 // (value-typed candidates holding index ranges, integer-scaled nw scores, a scalar per-cell
@@ -1809,6 +1809,15 @@ int mcxo_ksw2_extz(const uint8_t *q, int qlen, const uint8_t *t, int tlen, int *
 }
 
 static thread_local bool g_interleaved = false;
+// -indel / -maxmm of the runs that follow (mcxo_set_mapping_opts); every run kind goes through map_files_impl and takes them there
+static int g_max_pos_diff = 30;
+static float g_max_mm_rate = 0.05f;
+
+void mcxo_set_mapping_opts(int max_pos_diff, float max_mm_rate)
+{
+    g_max_pos_diff = max_pos_diff > 100 ? 100 : max_pos_diff; // main.cpp:251-253
+    g_max_mm_rate = max_mm_rate;
+}
 static int64_t map_files_impl(const mcxo_index *ix, const char *fq1, const char *fq2, int alg, const char *sam_path,
                               int threads, int64_t *stats, Profile *pf, int64_t *pair_stats = nullptr);
 
@@ -1910,6 +1919,7 @@ static int64_t map_files_impl(const mcxo_index *ix, const char *fq1, const char 
     sh.ix = ix;
     sh.pf = pf;
     sh.pm.use_nw = (alg == 0);
+    sh.pm.max_pos_diff = g_max_pos_diff; sh.pm.max_mm_rate = g_max_mm_rate;
     if (!sh.in1.open(fq1)) return -1;
     sh.fastq = sh.in1.fastq;
     if (fq2 && fq2[0]) { if (!sh.in2.open(fq2)) return -1; sh.paired = sh.two_files = true; }

@@ -3,7 +3,7 @@
 // C surface of the CPU restatement of MapCaller's seed-and-extend path (oracle/mcx_oracle.cpp).
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
 // Parity status: PINNED — every function below is checked against the real reference compiled
-// into oracle/_ref (tests/test_oracle_vs_ref.py) and against the golden vectors in tests/golden.
+// into oracle/_ref (tests/test_oracle_golden.py, tests/test_options.py, scripts/fuzz_parity.py --ref) through the golden vectors in tests/golden.
 #ifndef MCX_ORACLE_H
 #define MCX_ORACLE_H
 #include <stdint.h>
@@ -46,6 +46,11 @@ int64_t mcxo_map_files(const mcxo_index *, const char *fq1, const char *fq2, int
 
 // The run totals VariantCalling() takes over from Mapping() (reference src/ReadMapping.cpp:782-790):
 // out = {iTotalPairedNum, TotalPairedDistance, ReadLengthSum}.  Returns reads processed.
+// -indel / -maxmm (MaxPosDiff, clamped to 100 as main.cpp:251-253 does, and MaxMisMatchRate) of every run started after the
+// call: the SAM run, the interleaved run, the profile run, the VCF run and the pair totals.  Defaults 30 and 0.05; the
+// setting is the process's, so a test sets it back when it is done.
+void mcxo_set_mapping_opts(int max_pos_diff, float max_mm_rate);
+
 int64_t mcxo_pair_totals(const mcxo_index *, const char *fq1, const char *fq2, int alg, int64_t out[3]);
 
 // MapCaller -p: both mates alternate in one file (reference src/main.cpp:300, src/GetData.cpp:85-99)

@@ -164,6 +164,7 @@ void mcref_vc_hook()
 //   R <nw|ksw2> <out prefix> <index prefix> <sam> <vcf> <fq1> [fq2] -> the reference's whole main() at -t 1 with -sam / -vcf, <out>.prof.nz / <out>.maps dumped
 //                                 between Mapping() and VariantCalling() (a process of its own: main() loads and frees the index itself)
 //   L <prefix>                 -> "ok <genome size>"
+//   O <indel> <maxmm>          -> "ok": MaxPosDiff (clamped to 100 like main.cpp:251-253) and MaxMisMatchRate of the P / Q requests that follow (after L)
 //   S <start> <codes 0-4>      -> "<len> <freq> <loc>..."            BWT_Search(seq, start, strlen)
 //   D <q ascii> <t ascii>      -> "<nw a1> <nw a2> <ksw2 a1> <ksw2 a2> <ez.score> <ops reversed>"
 int main()
@@ -176,6 +177,10 @@ int main()
         if (line[0] == 'L') {
             int rc = mcref_load_index(line + 2);
             printf("%s %lld\n", rc == 0 ? "ok" : "fail", mcref_genome_size());
+        } else if (line[0] == 'O') {
+            int indel = 30; float mm = 0.05f;
+            if (sscanf(line + 2, "%d %f", &indel, &mm) == 2) { MaxPosDiff = indel > 100 ? 100 : indel; MaxMisMatchRate = mm; printf("ok\n"); }
+            else printf("bad\n");
         } else if (line[0] == 'S') {
             int start = 0, used = 0;
             sscanf(line + 2, "%d %n", &start, &used);

@@ -635,14 +635,23 @@ int hostemu_lane_dp2(int use_nw, const char *qa, int qlen_a, const char *ta, int
 
 // tier0 = {hit_cap, cand_cap, frag_cap, ops_cap, job_cap} or null for the product defaults.
 // stats[12]: 0 reads 1 mapped 2 pairs 3 E 4 H 5 LF 6 dp jobs 7 dp cells 8 blocks 9 tier-1 pairs 10 replayed pairs
+int64_t hostemu_map_files_opts(const char *prefix, const char *fq1, const char *fq2, int alg, const char *sam_path,
+                               int batch_reads, const int *tier0, int rlen_max, int max_pos_diff, float max_mm_rate, int64_t *stats);
 int64_t hostemu_map_files(const char *prefix, const char *fq1, const char *fq2, int alg, const char *sam_path,
                           int batch_reads, const int *tier0, int rlen_max, int64_t *stats)
+{
+    return hostemu_map_files_opts(prefix, fq1, fq2, alg, sam_path, batch_reads, tier0, rlen_max, 30, 0.05f, stats);
+}
+
+// The same with -indel / -maxmm (MapParams::max_pos_diff, max_mm_rate) as the caller says; no clamp here, the command lines clamp.
+int64_t hostemu_map_files_opts(const char *prefix, const char *fq1, const char *fq2, int alg, const char *sam_path,
+                               int batch_reads, const int *tier0, int rlen_max, int max_pos_diff, float max_mm_rate, int64_t *stats)
 {
     Emu e;
     std::string err;
     if (!host_index_load(prefix, e.hix, err)) { fprintf(stderr, "%s\n", err.c_str()); return -1; }
     set_view(e);
-    e.pm.max_pos_diff = 30; e.pm.max_mm_rate = 0.05f; e.pm.use_nw = alg == 0; e.pm.paired = 1;
+    e.pm.max_pos_diff = max_pos_diff; e.pm.max_mm_rate = max_mm_rate; e.pm.use_nw = alg == 0; e.pm.paired = 1;
     e.caps[0].hit_cap = 48; e.caps[0].cand_cap = 12; e.caps[0].frag_cap = 96; e.caps[0].ops_cap = 1024; e.caps[0].job_cap = 16;
     e.caps[0].cig_cap = 32; e.caps[0].kmer_cap = 2048;
     if (tier0) { e.caps[0].hit_cap = tier0[0]; e.caps[0].cand_cap = tier0[1]; e.caps[0].frag_cap = tier0[2]; e.caps[0].ops_cap = tier0[3]; e.caps[0].job_cap = tier0[4]; }
