@@ -405,6 +405,34 @@ int mcx_call_variants(const mcx_index *, const uint32_t *d_planes, const mcx_spa
                       int64_t paired_pairs, int64_t pair_dist_sum, int64_t pair_len_sum,
                       const mcx_vcf_opts *, const char *vcf_path, mcx_vcf_stats *stats);
 
+/* ---- SAM text ----------------------------------------------------------------------------------
+ * Replaces GenerateSingleSamStream / GeneratePairedSamStream (reference src/SamReport.cpp:324-488) and the -m lines
+ * (:364-488) for a whole batch: the text is made in HBM from what mcx_map_batch[_dev] was given and gave back.  Read r's
+ * line(s) — its record's, then those of its extras x_recs[x_index[r] .. x_index[r + 1]) — follow one another in read order.
+ * paired: the batch was mapped as pairs; SEQ/QUAL of every second read are then printed the way the reference prints mate 2,
+ * which it reverse-complements before mapping (ReadMapping.cpp:451): as they are for a reverse-strand hit, turned otherwise,
+ * bytes other than ACGTacgt as N whenever a complement is taken.  qual: read r's rlen bytes at off[r], the bytes of the quality
+ * line the reference takes (the first min(line, rlen), GetData.cpp:51-52) with NUL behind them up to rlen: QUAL is printed up to
+ * the first NUL, or — reversed — from the last byte backwards up to the first NUL (empty when the line was short). */
+typedef struct mcx_sam_in {
+    const uint8_t *bases; const uint32_t *off;        /* as given to mcx_map_batch[_dev]: n_reads + 1 offsets */
+    const uint8_t *qual;                               /* NULL: '*'.  Else read r's rlen bytes at off[r], NUL-padded (see above) */
+    const uint8_t *names; const uint32_t *name_off;    /* QNAMEs back to back; n_reads + 1 offsets */
+    const mcx_aln *aln; const uint32_t *cigar;         /* the batch's records and CIGAR pool */
+    const uint32_t *x_index; const mcx_aln *x_recs; const uint32_t *x_cigar; /* -m extras as mcx_multi_lines hands them out; NULL: none */
+    uint32_t n_reads; int32_t paired;
+} mcx_sam_in;
+/* d_in: the struct in host memory, every pointer in it a device pointer.  d_text[0 .. cap) receives the text, d_line_off (device, may be
+ * NULL) n_reads + 1 byte offsets of the reads' first lines, the last one the total; *n_bytes is always the exact size of the batch's
+ * text.  cap smaller than that: nothing is written to d_text and the call returns MCX_ERR_CAPACITY — allocate and call again (a call
+ * with cap = 0 asks for the size).  Runs on the context's stream and returns when the text is there. */
+int mcx_sam_format_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_text, uint64_t cap, uint64_t *d_line_off, uint64_t *n_bytes);
+/* same with host buffers (staged inside) */
+int mcx_sam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *text, uint64_t cap, uint64_t *line_off, uint64_t *n_bytes);
+/* OutputSamHeaders (reference src/ReadMapping.cpp:101-123): the @PG / @SQ lines the file front end writes ahead of the first
+ * batch; *n_bytes their size, MCX_ERR_CAPACITY (nothing written) when cap is smaller. */
+int mcx_sam_header(const mcx_index *, char *out, uint64_t cap, uint64_t *n_bytes);
+
 /* ---- files: MapCaller -i <prefix> -f A [-f2 B] -alg nw|ksw2 -sam out (src/main.cpp:212-321) */
 int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_path, mcx_stats *stats);
 /* The same with the remaining switches of the reference's file loop (src/ReadMapping.cpp:689-760):
@@ -417,9 +445,13 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * place in sam_path — the same path on every shard: shard 0 creates the file and writes the header,
  * the shards learn where their batches' text goes from one another (mcx_file_opts.exchange).  avg_state
  * must be the same on every shard when the run starts; it is again when it ends (avg_state[3] = reads
- * of the whole input). */
+ * of the whole input).
+ * device_sam (mapcaller-mi355x -gpu_sam): the names and NUL-padded qualities of a batch part follow its reads to HBM, the part's text is
+ * made there from the records, the CIGAR pool and the -m extras still in the slot, and comes back as text for the one writer; the
+ * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then. */
 typedef struct mcx_file_opts {
-    int32_t interleaved_pairs, host_threads, append_sam, reserved0;
+    int32_t interleaved_pairs, host_threads, append_sam;
+    int32_t device_sam; /* 1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
     int64_t *avg_state; /* int64_t[4], see mcx_avg_init */
     int32_t shard_rank, shard_count; /* 0, 0: the whole input */
     const char *reserved1;

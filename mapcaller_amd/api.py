@@ -69,6 +69,7 @@ SYMBOLS = [
     "mcx_stream_submit", "mcx_stream_submit_packed", "mcx_stream_map", "mcx_stream_collect", "mcx_stream_next", "mcx_stream_mapped",
     "mcx_stream_map32", "mcx_stream_mapped32",
     "mcx_ctx_set_multi", "mcx_multi_lines", "mcx_multi_copy", "mcx_stream_multi",
+    "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -229,10 +230,19 @@ def dist_exchange(device=None) -> Exchange:
 
 
 class FileOpts(C.Structure):
-    """mcx_file_opts: -p, -t, library append, insert-size state across libraries, sharding."""
-    _fields_ = [("interleaved_pairs", C.c_int32), ("host_threads", C.c_int32), ("append_sam", C.c_int32), ("reserved0", C.c_int32),
+    """mcx_file_opts: -p, -t, library append, -gpu_sam, insert-size state across libraries, sharding."""
+    _fields_ = [("interleaved_pairs", C.c_int32), ("host_threads", C.c_int32), ("append_sam", C.c_int32), ("device_sam", C.c_int32),
                 ("avg_state", C.POINTER(C.c_int64)), ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("reserved1", C.c_char_p),
                 ("exchange", C.POINTER(Exchange))]
+
+
+class SamIn(C.Structure):
+    """mcx_sam_in: what mcx_sam_format[_dev] makes a batch's SAM text from (pointers as integers: host or device)."""
+    _fields_ = [(n, C.c_void_p) for n in ("bases", "off", "qual", "names", "name_off", "aln", "cigar", "x_index", "x_recs", "x_cigar")] + \
+               [("n_reads", C.c_uint32), ("paired", C.c_int32)]
+
+
+ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
 
 
 class VcfOpts(C.Structure):
@@ -338,6 +348,13 @@ def lib() -> C.CDLL:
     L.mcx_vcf_defaults.restype = None
     L.mcx_call_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64,
                                     C.POINTER(VcfOpts), C.c_char_p, C.POINTER(VcfStats)]
+    L.mcx_gz_inflate.restype = C.c_int64
+    L.mcx_gz_inflate.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    for f in (L.mcx_sam_format_dev, L.mcx_sam_format):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_sam_header.restype = C.c_int
+    L.mcx_sam_header.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -503,18 +520,21 @@ class Mapper:
 
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
-                  shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False) -> dict:
+                  shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
+                  device_sam: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
         final place in ``sam`` (the same path on every shard; shard 0 creates it).  The insert-size state
         (self.avg) carries over from call to call like the reference's globals (a new library starts a
-        new 200-read chunk); ``append_sam``: a further library of the same run."""
+        new 200-read chunk); ``append_sam``: a further library of the same run; ``device_sam`` = -gpu_sam: the
+        SAM text is made on the device (the same bytes)."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
+        fo.device_sam = int(device_sam)
         if self.avg[3] % 200:
             self.avg[3] += 200 - self.avg[3] % 200
         fo.avg_state = C.cast(self.avg, C.POINTER(C.c_int64))
@@ -541,6 +561,43 @@ class Mapper:
         if not self.multi:
             return aln, cigars
         return aln, cigars, self.multi_lines(n)
+
+    def sam_text(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
+                 pool: np.ndarray, extras=None) -> bytes:
+        """The SAM lines of a mapped batch, made on the device (mcx_sam_format).  ``bases`` / ``off`` as given to map_batch, ``names`` the
+        QNAMEs, ``quals`` per read the bytes of its quality line that count (at most the read's length; shorter ones are NUL-padded here;
+        None: QUAL is '*'), ``aln`` the records and ``pool`` CIGAR words such that read r's are pool[aln[r].cigar_off:][:n_cigar] — map_batch's
+        list of per-read arrays is accepted too —, ``extras`` what multi_lines returns."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = off.size - 1
+        aln, pool = _pool_of(aln, pool)
+        name_off = np.zeros(n + 1, dtype=np.uint32)
+        name_off[1:] = np.cumsum([len(x) for x in names])
+        name_buf = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+        si = SamIn()
+        si.bases, si.off, si.names, si.name_off = bases.ctypes.data, off.ctypes.data, name_buf.ctypes.data, name_off.ctypes.data
+        si.aln, si.cigar, si.n_reads, si.paired = aln.ctypes.data, pool.ctypes.data, n, int(paired)
+        keep = []
+        if quals is not None:
+            q = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
+            for r, b in enumerate(quals):
+                b = b[:int(off[r + 1]) - int(off[r])]
+                q[int(off[r]):int(off[r]) + len(b)] = np.frombuffer(b, dtype=np.uint8)
+            keep.append(q)
+            si.qual = q.ctypes.data
+        if extras is not None:
+            index = np.ascontiguousarray(extras[0], dtype=np.uint32)
+            x_recs, x_pool = _pool_of(extras[1], extras[2])
+            keep += [index, x_recs, x_pool]
+            si.x_index, si.x_recs, si.x_cigar = index.ctypes.data, x_recs.ctypes.data, x_pool.ctypes.data
+        nb = C.c_uint64()
+        rc = lib().mcx_sam_format(self._h, C.byref(si), None, 0, None, C.byref(nb))
+        if rc not in (0, ERR_CAPACITY):
+            _check(rc, "mcx_sam_format")
+        text = np.zeros(max(1, nb.value), dtype=np.uint8)
+        _check(lib().mcx_sam_format(self._h, C.byref(si), text.ctypes.data, nb.value, None, C.byref(nb)), "mcx_sam_format")
+        return text[:nb.value].tobytes()
 
     def multi_lines(self, n_reads: int):
         """(multi) the last batch's extra lines: (index uint32 [n_reads + 1], records ALN_DTYPE, their CIGAR words per record) — read r's
@@ -753,6 +810,30 @@ class Mapper:
             self.close()
         except Exception:
             pass
+
+
+def _pool_of(aln: np.ndarray, cigars):
+    """(records, pool): ``cigars`` a pool the records' cigar_off point into, or a list of per-record word arrays (map_batch's form),
+    which are put back to back with the records' offsets rewritten."""
+    aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    if isinstance(cigars, np.ndarray):
+        return aln, np.ascontiguousarray(cigars, dtype=np.uint32)
+    aln = aln.copy()
+    sizes = np.array([len(c) for c in cigars], dtype=np.int64)
+    aln["cigar_off"] = np.concatenate([[0], np.cumsum(sizes)[:-1]]) if len(sizes) else 0
+    pool = np.concatenate([np.asarray(c, dtype=np.uint32) for c in cigars] + [np.zeros(1, dtype=np.uint32)])
+    return aln, pool
+
+
+def sam_header(index: "Index") -> bytes:
+    """The @PG / @SQ lines the file front end writes ahead of the first batch (mcx_sam_header)."""
+    nb = C.c_uint64()
+    rc = lib().mcx_sam_header(index._h, None, 0, C.byref(nb))
+    if rc not in (0, ERR_CAPACITY):
+        _check(rc, "mcx_sam_header")
+    buf = C.create_string_buffer(max(1, nb.value))
+    _check(lib().mcx_sam_header(index._h, buf, nb.value, C.byref(nb)), "mcx_sam_header")
+    return buf.raw[:nb.value]
 
 
 def avg_advance(state, pairs: int, dist: int, n_chunks: int):

@@ -681,6 +681,19 @@ struct Batch {
     struct Extras { std::vector<uint32_t> index, cig; std::vector<mcx_aln> recs; } mx[2];
     bool has_mx = false;
     std::deque<bool> parts_out; // the parts on their way out, oldest first (true: the single-read part)
+    // device_sam: the names and NUL-padded qualities of the batch's two parts on their way to the device (page-locked; a part's names back to back with
+    // offsets that start at 0: the pairs' are sam_name_off[0 .. n_pair_reads], the single reads' sam_name_off[n_pair_reads + 1 .. n + 1]), and the text that came back
+    uint8_t *sam_names = nullptr, *sam_qual = nullptr, *dev_text = nullptr; uint32_t *sam_name_off = nullptr;
+    uint64_t cap_sam_names = 0, cap_sam_qual = 0, cap_sam_off = 0, dev_text_cap = 0, dev_bytes = 0;
+    uint64_t sam_part_names[2] = {0, 0}, sam_part_qual[2] = {0, 0};
+    std::vector<uint64_t> sam_qual_at;
+    bool reserve_sam(uint64_t reads, uint64_t names, uint64_t qual)
+    {
+        if (reads + 2 > cap_sam_off) { mcx_pinned_free(sam_name_off); cap_sam_off = reads + 2; sam_name_off = (uint32_t *)mcx_pinned_alloc(cap_sam_off * sizeof(uint32_t)); }
+        if (names > cap_sam_names) { mcx_pinned_free(sam_names); cap_sam_names = names + names / 8 + 4096; sam_names = (uint8_t *)mcx_pinned_alloc(cap_sam_names); }
+        if (qual > cap_sam_qual) { mcx_pinned_free(sam_qual); cap_sam_qual = qual + qual / 8 + 4096; sam_qual = (uint8_t *)mcx_pinned_alloc(cap_sam_qual); }
+        return sam_name_off && (sam_names || !names) && (sam_qual || !qual);
+    }
     bool reserve(size_t reads, size_t words_per_read)
     {
         if (reads > cap_reads) {
@@ -698,7 +711,7 @@ struct Batch {
         if (n > cap_odd) { mcx_pinned_free(odd); cap_odd = n + n / 2 + 1024; odd = (uint64_t *)mcx_pinned_alloc(cap_odd * sizeof(uint64_t)); }
         return odd != nullptr;
     }
-    ~Batch() { mcx_pinned_free(rows); mcx_pinned_free(lens); mcx_pinned_free(odd); mcx_pinned_free(recs); mcx_pinned_free(cig); }
+    ~Batch() { mcx_pinned_free(rows); mcx_pinned_free(lens); mcx_pinned_free(odd); mcx_pinned_free(recs); mcx_pinned_free(cig); mcx_pinned_free(sam_names); mcx_pinned_free(sam_qual); mcx_pinned_free(sam_name_off); mcx_pinned_free(dev_text); }
     // read r of the batch -> (file, index in that file's records)
     const Rec &rec(uint32_t r, const char *&base) const
     {
@@ -1127,13 +1140,14 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         if (rc) { if (sam_fd >= 0 && !sam_stream) close(sam_fd); return rc; }
     }
 
+    const bool dev_sam = opt.device_sam != 0 && sam_fd >= 0; // the text is made on the device (mcx_sam.hip); without a SAM file there is none to make
     int64_t local_avg[4];
     mcx_avg_init(local_avg);
     int64_t *avg = opt.avg_state ? opt.avg_state : local_avg;
     w_open = secs(t_begin, now());
 
     // busy seconds per stage (MCX_TIMING=1 prints them)
-    double t_parse = 0, t_map = 0, t_format = 0, t_write = 0, t_p_lines = 0, t_p_pack = 0, t_p_wait = 0, t_p_push = 0, t_m_take = 0, t_m_collect = 0, t_f_push = 0, t_m_in = 0, t_m_dev = 0, t_m_out = 0, t_m_submit = 0;
+    double t_parse = 0, t_map = 0, t_format = 0, t_write = 0, t_p_lines = 0, t_p_pack = 0, t_p_wait = 0, t_p_push = 0, t_m_take = 0, t_m_collect = 0, t_f_push = 0, t_m_in = 0, t_m_dev = 0, t_m_out = 0, t_m_submit = 0, t_m_sam = 0;
     std::vector<double> each_dev; // (MCX_TIMING) mcx_map_batch_dev, batch by batch
     typedef std::unique_ptr<Batch> BatchPtr;
     // batch objects circulate: their buffers (page-locked: slow to get) are allocated once and stay with the context from call to call
@@ -1279,6 +1293,43 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 }
                 b->is_mate2.assign(n, 0);
                 for (uint32_t r = 1; r < npr; r += 2) b->is_mate2[r] = 1;
+                // device_sam: names and qualities as mcx_sam_in takes them, a part's qualities where the device's offsets (the running sum of the lengths) put its reads
+                if (dev_sam && b->error.empty()) {
+                    uint64_t names = 0, quals[2] = {0, 0};
+                    for (uint32_t r = 0; r < n; r++) { const char *base; names += b->rec(r, base).name_len; }
+                    b->sam_qual_at.resize(n);
+                    if (!b->reserve_sam(n, names, 0)) b->error = "cannot allocate pinned host memory";
+                    else {
+                        uint32_t *no = b->sam_name_off;
+                        for (uint32_t r = 0; r < n; r++) {
+                            const uint32_t part = r >= npr ? 1u : 0u;
+                            const char *base;
+                            const Rec &e = b->rec(r, base);
+                            if (r == 0 || r == npr) no[r + part] = 0;
+                            no[r + part + 1] = no[r + part] + e.name_len;
+                            b->sam_qual_at[r] = quals[part]; quals[part] += e.rlen;
+                        }
+                        b->sam_part_names[0] = npr ? no[npr] : 0; b->sam_part_names[1] = npr < n ? no[n + 1] : 0;
+                        b->sam_part_qual[0] = quals[0]; b->sam_part_qual[1] = quals[1];
+                        if (!b->reserve_sam(n, names, b->fastq ? quals[0] + quals[1] : 0)) b->error = "cannot allocate pinned host memory";
+                    }
+                    if (b->error.empty()) {
+                        const int slices = (int)std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)pool.size(), n / 4096));
+                        pool.run(slices, [&](int k) {
+                            for (uint32_t r = (uint32_t)((uint64_t)n * k / slices); r < (uint32_t)((uint64_t)n * (k + 1) / slices); r++) {
+                                const uint32_t part = r >= npr ? 1u : 0u;
+                                const char *base;
+                                const Rec &e = b->rec(r, base);
+                                memcpy(b->sam_names + (part ? b->sam_part_names[0] : 0) + b->sam_name_off[r + part], base + e.name, e.name_len);
+                                if (b->fastq) {
+                                    uint8_t *q = b->sam_qual + (part ? b->sam_part_qual[0] : 0) + b->sam_qual_at[r];
+                                    memcpy(q, base + e.qual, e.q_take);
+                                    memset(q + e.q_take, 0, e.rlen - e.q_take); // (what strncpy leaves behind a short quality line)
+                                }
+                            }
+                        });
+                    }
+                }
             }
             if (!b->error.empty()) done = true;
             b->last = done;
@@ -1301,7 +1352,14 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         bool stop = false;
         auto write_out = [&](BatchPtr &b, uint64_t at) {
             const Tick t1 = now();
-            if (sam_stream) { for (Text &t : b->slices) if (t.size() && write(sam_fd, t.b.data(), t.size()) != (ssize_t)t.size()) write_rc = MCX_ERR_IO; }
+            if (dev_sam) { // the batch's text is one piece, as it came from the device
+                size_t done_b = 0;
+                while (done_b < b->sam_bytes && write_rc == 0) {
+                    const ssize_t w = sam_stream ? write(sam_fd, b->dev_text + done_b, b->sam_bytes - done_b) : pwrite(sam_fd, b->dev_text + done_b, b->sam_bytes - done_b, (off_t)(at + done_b));
+                    if (w <= 0) { write_rc = MCX_ERR_IO; break; }
+                    done_b += (size_t)w;
+                }
+            } else if (sam_stream) { for (Text &t : b->slices) if (t.size() && write(sam_fd, t.b.data(), t.size()) != (ssize_t)t.size()) write_rc = MCX_ERR_IO; }
             else if (b->sam_bytes) {
                 std::vector<uint64_t> off(b->slices.size() + 1, at);
                 for (size_t k = 0; k < b->slices.size(); k++) off[k + 1] = off[k] + b->slices[k].size();
@@ -1376,7 +1434,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             BatchPtr b = mapped.pop();
             if (b->last) stop = true;
             b->sam_bytes = 0;
-            if (sam_fd >= 0 && b->n && write_rc == 0) {
+            if (dev_sam) { if (b->n && write_rc == 0) b->sam_bytes = b->dev_bytes; } // (made in HBM behind the batch's kernels: nothing to do here)
+            else if (sam_fd >= 0 && b->n && write_rc == 0) {
                 const Tick t0 = now();
                 const int parts = (int)std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)fpool.size(), b->n / 2048));
                 b->slices.resize((size_t)parts);
@@ -1506,9 +1565,21 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             if (e && rc == 0) rc = e;
             if (e == 0) { parts_out++; p->parts_out.push_back(second); }
         };
+        p->dev_bytes = 0;
+        auto part_text = [&](bool second, uint32_t cnt) { // device_sam: the mapped part's text, made where its records lie and brought to the batch's page-locked buffer
+            if (!dev_sam || rc || !cnt) return;
+            const Tick tq = now();
+            const uint32_t npr = p->n_pair_reads;
+            uint64_t got = 0;
+            const int e = mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
+                                       p->fastq ? p->sam_qual + (second ? p->sam_part_qual[0] : 0) : nullptr, p->sam_part_qual[second ? 1 : 0], d_aln, d_cig,
+                                       &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got);
+            if (e) rc = e; else p->dev_bytes += got;
+            t_m_sam += secs(tq, now());
+        };
         if (!sharded) {
-            if (n_pr && part_in()) { const Tick tq = now(); if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_pr, 1, avg, d_aln, d_cig, stats); t_m_dev += secs(tq, now()); each_dev.push_back(secs(tq, now())); part_out(false); }
-            if (n_sg && part_in()) { if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_sg, 0, avg, d_aln, d_cig, stats); part_out(true); }
+            if (n_pr && part_in()) { const Tick tq = now(); if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_pr, 1, avg, d_aln, d_cig, stats); t_m_dev += secs(tq, now()); each_dev.push_back(secs(tq, now())); part_text(false, n_pr); part_out(false); }
+            if (n_sg && part_in()) { if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_sg, 0, avg, d_aln, d_cig, stats); part_text(true, n_sg); part_out(true); }
         } else if (!dead && !ended && p->number / shard_count >= rounds_done) {
             rounds_done = p->number / shard_count + 1;
             Shards::Head h = {rc, rc ? 0u : n_pr, rc ? 0u : n_sg, p->last ? 1u : 0u};
@@ -1536,10 +1607,10 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             // (a part that was copied in but does not count any more — the input ended in a batch before this one — still leaves the device)
             const bool in1 = n_pr && part_in();
             if (rc == 0 && any_pair) rc = sh.pairs(c, d_bases, d_off, in1 ? my_pr : 0u, round_base + (int64_t)before, avg, profile, d_aln, d_cig, stats);
-            if (in1) part_out(false);
+            if (in1) { part_text(false, my_pr); part_out(false); }
             const bool in2 = n_sg && part_in();
             if (rc == 0 && any_single) rc = sh.singles(c, d_bases, d_off, in2 ? my_sg : 0u, round_base + (int64_t)before + my_pr, profile, d_aln, d_cig, stats);
-            if (in2) part_out(true);
+            if (in2) { part_text(true, my_sg); part_out(true); }
             if (my_pr == 0 && my_sg == 0) p->n = 0; // (nothing of this batch counts)
             avg[3] = round_base + (int64_t)round_total;
             if (rc) dead = true;
@@ -1580,6 +1651,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         for (size_t k = 0; k < each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
     }
+    if (getenv("MCX_TIMING") && dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t_m_sam);
     if (getenv("MCX_TIMING"))
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t_parse, t_p_lines, t_p_pack, t_p_wait, t_map, t_format, t_write, threads, threads, mapped_input ? "mapped" : "sequential"),

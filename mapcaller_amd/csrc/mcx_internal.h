@@ -35,6 +35,12 @@ bool mcx_ctx_multi(const mcx_ctx *); // -m is on (mcx_ctx_set_multi)
 // something the file front end keeps with the context from call to call (its page-locked batch buffers): *slot, freed with
 // `drop` when the context goes
 void **mcx_ctx_files_slot(mcx_ctx *, void (*drop)(void *));
+// the same for mcx_sam.hip's device buffers, and the stream (a hipStream_t) the context's kernels run on
+void **mcx_ctx_sam_slot(mcx_ctx *, void (*drop)(void *));
+void *mcx_ctx_stream(mcx_ctx *);
+// -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory
+int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
+                 const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
 void *mcx_pinned_alloc(size_t bytes); // page-locked host memory (null on failure); mcx_pinned_free accepts null
 void mcx_pinned_free(void *);
 

@@ -1,0 +1,178 @@
+// mapcaller_amd/csrc/mcx_sam.h — one read's SAM line(s) from its record, for the device and (tests/hostemu) for the host.
+//
+// GenerateSingleSamStream / GeneratePairedSamStream (reference src/SamReport.cpp:324-488) restated from sam_line(), sam_record()
+// and comp_char() of mcx_files.cpp, which every golden SAM pins to the reference byte for byte:
+//   QNAME \t FLAG \t  then  "*\t0\t0\t*\t*\t0\t0\t"  for an unmapped read, or
+//                           RNAME \t POS \t MAPQ \t CIGAR  and  "\t=\t" PNEXT \t TLEN \t  (has_mate)  |  "\t*\t0\t0\t"
+//   SEQ \t QUAL  then  "\tNM:i:" nm "\tAS:i:" as "\tXS:i:" xs "\n"  |  "\tAS:i:0\tXS:i:0\n"  (unmapped)
+// SEQ: the reference reverse-complements mate 2 in place before mapping (ReadMapping.cpp:451) and prints that string for
+// forward-strand hits and unmapped reads, its reverse complement otherwise — flipped = mate 2, again = mapped && !fwd; one of the
+// two: reverse complement (anything but ACGTacgt gives N); both: complemented twice in forward order (upper case, N for the rest).
+// QUAL: rlen bytes, NUL from where the reference stopped taking the quality line (GetData.cpp:51-52: strncpy); printed with %s —
+// forward up to the first NUL, reversed from the last byte backwards up to the first NUL (empty when the line was short).
+// The pieces (sam_head_*, sam_tags_*, sam_seq_byte, sam_qual_len) are what k_sam_write (mcx_sam.hip) spreads over a wavefront;
+// sam_line_len / sam_line_put put them together for one lane: the length kernel, the lines too long for the LDS staging, the host.
+#ifndef MCX_SAM_H
+#define MCX_SAM_H
+#include "mcx_types.h"
+#include "../../include/mcx.h"
+
+namespace mcx {
+
+struct SamContigs { const char *text; const uint32_t *off; }; // the contigs' names back to back; name i is text[off[i] .. off[i + 1])
+
+// what of read r does not depend on the record
+struct SamRead {
+    const uint8_t *name, *seq, *qual; // qual null: '*'
+    uint32_t name_len, rlen;
+    bool flipped;                     // mapped as the second read of a pair
+};
+static inline MCX_HD SamRead sam_read_of(const mcx_sam_in &in, uint32_t r)
+{
+    SamRead d;
+    d.name = in.names + in.name_off[r]; d.name_len = in.name_off[r + 1] - in.name_off[r];
+    d.seq = in.bases + in.off[r]; d.rlen = in.off[r + 1] - in.off[r];
+    d.qual = in.qual ? in.qual + in.off[r] : nullptr;
+    d.flipped = in.paired && (r & 1u);
+    return d;
+}
+
+static inline MCX_HD uint8_t sam_comp(uint8_t c) // GetComplementaryBase, tools.cpp:3-18
+{
+    switch (c) {
+    case 'A': case 'a': return 'T';
+    case 'C': case 'c': return 'G';
+    case 'G': case 'g': return 'C';
+    case 'T': case 't': return 'A';
+    default: return 'N';
+    }
+}
+
+static inline MCX_HD uint32_t sam_num_len(int64_t v)
+{
+    uint64_t u = v < 0 ? 0ull - (uint64_t)v : (uint64_t)v;
+    uint32_t n = v < 0 ? 2u : 1u;
+    while (u >= 10) { u /= 10; n++; }
+    return n;
+}
+static inline MCX_HD uint8_t *sam_num(uint8_t *o, int64_t v)
+{
+    const uint32_t n = sam_num_len(v);
+    uint64_t u = v < 0 ? 0ull - (uint64_t)v : (uint64_t)v;
+    for (uint32_t k = n; k-- > (v < 0 ? 1u : 0u);) { o[k] = (uint8_t)('0' + u % 10); u /= 10; }
+    if (v < 0) o[0] = '-';
+    return o + n;
+}
+static inline MCX_HD uint8_t *sam_lit(uint8_t *o, const char *s) { while (*s) *o++ = (uint8_t)*s++; return o; }
+
+// the fields between QNAME and SEQ, with the tabs around them
+static inline MCX_HD uint32_t sam_head_len(const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn)
+{
+    uint32_t n = 1 + sam_num_len(rec.flag) + 1;
+    if (rec.chr < 0) return n + 14;
+    n += cn.off[rec.chr + 1] - cn.off[rec.chr] + 1 + sam_num_len(rec.pos) + 1 + sam_num_len(rec.mapq) + 1;
+    for (int k = 0; k < rec.n_cigar; k++) n += sam_num_len((int64_t)(cigar[k] >> 4)) + 1;
+    return n + (rec.has_mate ? 3 + sam_num_len(rec.mate_pos) + 1 + sam_num_len(rec.tlen) + 1 : 7);
+}
+static inline MCX_HD uint8_t *sam_head_put(const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o)
+{
+    *o++ = '\t'; o = sam_num(o, rec.flag); *o++ = '\t';
+    if (rec.chr < 0) return sam_lit(o, "*\t0\t0\t*\t*\t0\t0\t");
+    for (uint32_t k = cn.off[rec.chr]; k < cn.off[rec.chr + 1]; k++) *o++ = (uint8_t)cn.text[k];
+    *o++ = '\t'; o = sam_num(o, rec.pos); *o++ = '\t'; o = sam_num(o, rec.mapq); *o++ = '\t';
+    for (int k = 0; k < rec.n_cigar; k++) {
+        const uint32_t w = cigar[k];
+        o = sam_num(o, (int64_t)(w >> 4)); *o++ = (uint8_t)"MIDNSHP="[w & 7];
+    }
+    if (!rec.has_mate) return sam_lit(o, "\t*\t0\t0\t");
+    o = sam_lit(o, "\t=\t"); o = sam_num(o, rec.mate_pos); *o++ = '\t'; o = sam_num(o, rec.tlen); *o++ = '\t';
+    return o;
+}
+
+static inline MCX_HD uint32_t sam_tags_len(const mcx_aln &rec)
+{
+    return rec.chr < 0 ? 15u : 6 + sam_num_len(rec.nm) + 6 + sam_num_len(rec.as) + 6 + sam_num_len(rec.xs) + 1;
+}
+static inline MCX_HD uint8_t *sam_tags_put(const mcx_aln &rec, uint8_t *o)
+{
+    if (rec.chr < 0) return sam_lit(o, "\tAS:i:0\tXS:i:0\n");
+    o = sam_lit(o, "\tNM:i:"); o = sam_num(o, rec.nm); o = sam_lit(o, "\tAS:i:"); o = sam_num(o, rec.as); o = sam_lit(o, "\tXS:i:"); o = sam_num(o, rec.xs);
+    *o++ = '\n';
+    return o;
+}
+
+// how SEQ and QUAL of a line are turned
+struct SamTurn { bool reverse, twice, qual_forward; };
+static inline MCX_HD SamTurn sam_turn(const SamRead &d, const mcx_aln &rec)
+{
+    const bool again = rec.chr >= 0 && rec.fwd == 0; // a second reverse complement for the output
+    SamTurn t;
+    t.reverse = d.flipped != again; t.twice = d.flipped && again; t.qual_forward = d.flipped == again;
+    return t;
+}
+static inline MCX_HD uint8_t sam_seq_byte(const SamRead &d, const SamTurn &t, uint32_t k) // byte k of SEQ
+{
+    if (t.reverse) return sam_comp(d.seq[d.rlen - 1 - k]);
+    return t.twice ? sam_comp(sam_comp(d.seq[k])) : d.seq[k];
+}
+static inline MCX_HD uint32_t sam_qual_len(const SamRead &d, const SamTurn &t) // bytes of QUAL
+{
+    if (!d.qual) return 1;
+    uint32_t n = 0;
+    if (t.qual_forward) while (n < d.rlen && d.qual[n]) n++;
+    else while (n < d.rlen && d.qual[d.rlen - 1 - n]) n++;
+    return n;
+}
+static inline MCX_HD uint8_t sam_qual_byte(const SamRead &d, const SamTurn &t, uint32_t k) // byte k of QUAL, k < sam_qual_len
+{
+    return !d.qual ? (uint8_t)'*' : t.qual_forward ? d.qual[k] : d.qual[d.rlen - 1 - k];
+}
+
+// one line: its bytes; the same written at o (returns the end)
+static inline MCX_HD uint64_t sam_one_len(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn)
+{
+    return (uint64_t)d.name_len + sam_head_len(rec, cigar, cn) + d.rlen + 1 + sam_qual_len(d, sam_turn(d, rec)) + sam_tags_len(rec);
+}
+static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o)
+{
+    for (uint32_t k = 0; k < d.name_len; k++) *o++ = d.name[k];
+    o = sam_head_put(rec, cigar, cn, o);
+    const SamTurn t = sam_turn(d, rec);
+    for (uint32_t k = 0; k < d.rlen; k++) *o++ = sam_seq_byte(d, t, k);
+    *o++ = '\t';
+    const uint32_t ql = sam_qual_len(d, t);
+    for (uint32_t k = 0; k < ql; k++) *o++ = sam_qual_byte(d, t, k);
+    return sam_tags_put(rec, o);
+}
+
+// -m: read r's extra lines (SamReport.cpp:364-488: every further candidate with the best score), none without x_index
+static inline MCX_HD void sam_extras_of(const mcx_sam_in &in, uint32_t r, uint32_t &lo, uint32_t &hi)
+{
+    lo = hi = 0;
+    if (in.x_index) { lo = in.x_index[r]; hi = in.x_index[r + 1]; }
+}
+
+// read r's line(s): the record of unique mode, then its extras with the same name, bases and quality
+static inline MCX_HD uint64_t sam_line_len(const mcx_sam_in &in, const SamContigs &cn, uint32_t r)
+{
+    const SamRead d = sam_read_of(in, r);
+    const mcx_aln rec = in.aln[r];
+    uint64_t n = sam_one_len(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn);
+    uint32_t lo, hi;
+    sam_extras_of(in, r, lo, hi);
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; n += sam_one_len(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn); }
+    return n;
+}
+static inline MCX_HD uint64_t sam_line_put(const mcx_sam_in &in, const SamContigs &cn, uint32_t r, uint8_t *out)
+{
+    const SamRead d = sam_read_of(in, r);
+    const mcx_aln rec = in.aln[r];
+    uint8_t *o = sam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, out);
+    uint32_t lo, hi;
+    sam_extras_of(in, r, lo, hi);
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; o = sam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, o); }
+    return (uint64_t)(o - out);
+}
+
+} // namespace mcx
+#endif
