@@ -115,6 +115,16 @@ int mcx_bwt_search_batch(mcx_ctx *, const uint8_t *seqs, const uint32_t *seq_off
  * ez.score of ksw_extz2_sse for ksw2 and 2x the final s for nw. */
 int mcx_extend_batch(mcx_ctx *, int alg, const uint8_t *q, const uint32_t *q_off, const uint8_t *t,
                      const uint32_t *t_off, uint32_t n, uint8_t *ops, int32_t *ops_len, int32_t *score);
+/* The same problems through the forms the batch pipeline runs its long DP lists on, in the caller's order: form 1 = one problem per
+ * lane (lane l of group g takes problem 64 g + l), form 2 = two per lane in 16-bit halves (problem 128 g + 2 l in the low half,
+ * 128 g + 2 l + 1 in the high one); strip = 8 or 16 target columns per strip; blocks = wavefronts launched (0: one per group; fewer
+ * than there are groups: a wavefront takes several groups one after the other in the same scratch).  alg: 0 nw, 1 ksw2.  ops, ops_len
+ * as mcx_extend_batch; score[i] is 2x the final s for nw and 0 for ksw2; summaries: null, or room for n records of 64 bytes (the
+ * pipeline's per-problem summary of the column string: csrc/mcx_types.h DpSummary, with cols_off = the two lengths' sum less
+ * cols_len).  MCX_ERR_UNSUPPORTED for a target letter outside ACGT, a target longer than 256 bases (64 with strips of 8), a query longer
+ * than 2048, an empty string, another form or strip. */
+int mcx_extend_lanes(mcx_ctx *, int alg, int form, int strip, uint32_t blocks, const uint8_t *q, const uint32_t *q_off, const uint8_t *t,
+                     const uint32_t *t_off, uint32_t n, uint8_t *ops, int32_t *ops_len, int32_t *score, void *summaries);
 
 /* ---- the whole path -----------------------------------------------------------------------
  * One record per read: what GeneratePairedSamStream / GenerateSingleSamStream print

@@ -60,7 +60,7 @@ def pack_reads(bases, lens=None):
 SYMBOLS = [
     "mcx_last_error", "mcx_device_count", "mcx_pack_row", "mcx_host_cpus", "mcx_gz_inflate", "mcx_index_load", "mcx_index_build", "mcx_index_from_codes", "mcx_index_save", "mcx_index_free", "mcx_index_trim",
     "mcx_index_genome_size", "mcx_index_n_chr", "mcx_index_chr_name", "mcx_index_chr_len", "mcx_index_hbm_bytes",
-    "mcx_opts_default", "mcx_ctx_create", "mcx_ctx_create_fit", "mcx_ctx_free", "mcx_bwt_search_batch", "mcx_extend_batch",
+    "mcx_opts_default", "mcx_ctx_create", "mcx_ctx_create_fit", "mcx_ctx_free", "mcx_bwt_search_batch", "mcx_extend_batch", "mcx_extend_lanes",
     "mcx_avg_init", "mcx_map_batch_dev", "mcx_map_batch", "mcx_cigar_words", "mcx_map_files", "mcx_map_files_ex", "mcx_file_opts_default",
     "mcx_profile_attach", "mcx_profile_settle", "mcx_profile_finalize", "mcx_profile_sparse", "mcx_planes_alloc", "mcx_planes_free", "mcx_planes_bytes",
     "mcx_vcf_defaults", "mcx_call_variants",
@@ -117,6 +117,13 @@ def aln32_unpack(a32: np.ndarray) -> np.ndarray:
 ALN_DTYPE = np.dtype([("pos", "<i8"), ("mate_pos", "<i8"), ("chr", "<i4"), ("flag", "<i4"), ("mapq", "<i4"),
                       ("tlen", "<i4"), ("nm", "<i4"), ("as", "<i4"), ("xs", "<i4"), ("n_cigar", "<i4"),
                       ("fwd", "<i4"), ("has_mate", "<i4"), ("cigar_off", "<i4"), ("pad", "<i4")])
+
+
+# csrc/mcx_types.h DpSummary: what the lane that walked a DP problem's traceback leaves about its column string
+DP_SUMMARY_DTYPE = np.dtype([("cols_off", "<u4"), ("cols_len", "<u2"), ("n", "<u2"), ("mis", "<u2"), ("switches", "<u2"), ("lead_d", "<u2"), ("lead_i", "<u2"),
+                             ("lead_runs", "<u2"), ("tail_d", "<u2"), ("tail_i", "<u2"), ("tail_runs", "<u2"), ("n_rle", "<u2"), ("pad", "<u2"), ("rle", "<u4", (8,)),
+                             ("pad2", "<u4")])
+assert DP_SUMMARY_DTYPE.itemsize == 64
 
 
 class SparseRec(C.Structure):
@@ -300,6 +307,7 @@ def lib() -> C.CDLL:
     L.mcx_ctx_create_fit.argtypes = [C.c_void_p, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Fit)]
     L.mcx_bwt_search_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
     L.mcx_extend_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 3
+    L.mcx_extend_lanes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 4
     L.mcx_avg_init.argtypes = [C.POINTER(C.c_int64)]
     L.mcx_avg_init.restype = None
     for f in (L.mcx_map_batch_dev, L.mcx_map_batch):
@@ -799,6 +807,30 @@ class Mapper:
             b = int(qo[i]) + int(to[i])
             out.append(ops[b:b + int(ol[i])].tobytes().decode())
         return out, sc
+
+    def extend_lanes(self, alg: str, form: int, strip: int, qs: List[bytes], ts: List[bytes], blocks: int = 0, summaries: bool = False):
+        """The same problems through the lane forms of the DP (mcx_extend_lanes), in the order given: form 1 = one problem per lane,
+        2 = two per lane; strips of 8 or 16 target columns; blocks = wavefronts launched (0: one per group of 64 / 128 problems).
+        Returns (op strings, their lengths as the kernel reports them, scores, DP_SUMMARY_DTYPE records or None)."""
+        n = len(qs)
+        qo = np.zeros(n + 1, dtype=np.uint32)
+        to = np.zeros(n + 1, dtype=np.uint32)
+        qo[1:] = np.cumsum([len(s) for s in qs])
+        to[1:] = np.cumsum([len(s) for s in ts])
+        qb = np.frombuffer(b"".join(qs) + b"\0", dtype=np.uint8).copy()
+        tb = np.frombuffer(b"".join(ts) + b"\0", dtype=np.uint8).copy()
+        ops = np.zeros(int(qo[-1]) + int(to[-1]) + 16, dtype=np.uint8)
+        ol = np.zeros(n, dtype=np.int32)
+        sc = np.zeros(n, dtype=np.int32)
+        sm = np.zeros(n, dtype=DP_SUMMARY_DTYPE) if summaries else None
+        _check(lib().mcx_extend_lanes(self._h, 0 if alg == "nw" else 1, form, strip, blocks, qb.ctypes.data, qo.ctypes.data, tb.ctypes.data,
+                                      to.ctypes.data, n, ops.ctypes.data, ol.ctypes.data, sc.ctypes.data, sm.ctypes.data if summaries else None),
+               "mcx_extend_lanes")
+        out = []
+        for i in range(n):
+            b = int(qo[i]) + int(to[i])
+            out.append(ops[b:b + int(ol[i])].tobytes().decode())
+        return out, ol, sc, sm
 
     def close(self):
         if self._h:

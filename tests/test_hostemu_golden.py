@@ -162,6 +162,42 @@ def test_two_problems_per_lane_dp_equals_one_per_lane_on_random_shapes(hostemu_l
                 assert sc[k] == r[1]
 
 
+@pytest.mark.parametrize("K", [8, 16])
+@pytest.mark.parametrize("alg", ["nw", "ksw2"])
+def test_lane_dp_forms_equal_the_oracle_on_the_seeded_shapes(hostemu_lib, oracle_lib, alg, K):
+    """The seeded problems of tests/dp_problems.py — the boundary grid, the extremes of the 16-bit argument (2048 x 256 all-mismatch, all-N
+    queries, homopolymers), 600 random descents; targets of at most 64 bases for strips of 8 — through the one-problem-per-lane form and
+    through the two-per-lane form, every problem once in the low half and once in the high one beside a problem a third of the list away:
+    the column strings are the oracle's (mcxo_nw / mcxo_ksw2), the lengths theirs, and nw's doubled score is the score of the oracle's
+    alignment counted from its gapped strings.  tests/test_dp_device.py gives the GPU the same problems; this is where the oracle and the
+    host build are shown to agree on them first."""
+    import dp_problems as dp
+    L = hostemu_lib
+    L.hostemu_lane_dp2.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    L.hostemu_lane_dp.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    use_nw = 1 if alg == "nw" else 0
+    probs = dp.for_strip(dp.problem_set(), K)
+    assert len(probs) == (1149 if K == 16 else 509)
+    want = [dp.oracle_columns(oracle_lib, alg, q, t) for q, t in probs]
+    want_sc = [dp.nw_score2(*dp.oracle_gapped(oracle_lib, "nw", q, t)) if use_nw else 0 for q, t in probs]
+    for (q, t), w, s in zip(probs, want, want_sc):
+        buf, sc = ctypes.create_string_buffer(len(q) + len(t) + 2), ctypes.c_int()
+        ln = L.hostemu_lane_dp(use_nw, q.encode(), len(q), t.encode(), len(t), K, buf, ctypes.byref(sc))
+        assert buf.value.decode() == w, (q, t)
+        assert ln == len(w) and sc.value == s, (q, t, sc.value, s)
+    pairs, idx = dp.unlike_order(probs)
+    for k in range(0, len(pairs), 2):
+        (qa, ta), (qb, tb) = pairs[k], pairs[k + 1]
+        oa, ob = ctypes.create_string_buffer(len(qa) + len(ta) + 2), ctypes.create_string_buffer(len(qb) + len(tb) + 2)
+        sc, ln = (ctypes.c_int * 2)(), (ctypes.c_int * 2)()
+        assert L.hostemu_lane_dp2(use_nw, qa.encode(), len(qa), ta.encode(), len(ta), qb.encode(), len(qb), tb.encode(), len(tb), K, oa, ob, sc, ln) == 0
+        for h, o in enumerate((oa, ob)):
+            i = idx[k + h]
+            assert o.value.decode() == want[i], (h, pairs[k], pairs[k + 1])
+            assert ln[h] == len(want[i]) and sc[h] == want_sc[i], (h, pairs[k], pairs[k + 1], sc[h], want_sc[i])
+
+
 @pytest.mark.parametrize("switch", ["MCX_EMU_NO_CODES", "MCX_EMU_ORACLE_DP", "MCX_EMU_DP_X1"])
 @pytest.mark.parametrize("alg", ["nw", "ksw2"])
 def test_lane_dp_inputs_and_the_scalar_dp_agree(hostemu_lib, golden, tmp_path, monkeypatch, alg, switch):
