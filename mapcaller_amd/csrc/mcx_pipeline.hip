@@ -1,52 +1,34 @@
-// mapcaller_amd/csrc/mcx_pipeline.hip — HIP kernels, the batch pipeline and the C ABI.
+// mapcaller_amd/csrc/mcx_pipeline.hip — the batch pipeline: its kernels (but the DP stage's), the context, the tiers and the batch ABI.
 //
 // One batch of reads goes through (all on one stream, no host round trip inside a tier):
 //   k_pack_reads  ASCII -> 2-bit words + N masks, mate 2 reverse-complemented (ReadMapping.cpp:447,451)
 //   k_seed        jump table + FM steps + direct comparison, one read per lane (IdentifySimplePairs/BWT_Search)
 //   k_sa          hits that are still BWT rows -> text positions            (bwt_sa)
-//   k_cluster     one pair per lane: sort, cluster, pair by distance        (SimplePairClustering, CheckPairedAlignmentDistance)
-//   k_rescue      unpaired pairs only, one workgroup each: 8-mer mate rescue (AlignmentRescue)
-//   k_build       mask, fragment lists, DP job emission by size class       (ProduceReadAlignment up to ProcessNormalPair)
-//   k_dp_small / k_dp_sel<K>  16-lane groups / one wavefront per DP job     (ksw2_alignment / nw_alignment)
+//   k_simple      the straight-line pairs of a whole batch from their seeds to their records (mcx_simple.h), k_simple_dp their small gaps;
+//                 k_order_* deal what is left to the lanes by weight
+//   k_cluster     one pair per lane: sort, cluster, pair by distance        (SimplePairClustering, CheckPairedAlignmentDistance);
+//                 the large tier: k_cluster_wave, a pair per wavefront
+//   k_rescue_plan / _eval / _apply   mate rescue window by window; k_rescue: pairs with an N in a read (AlignmentRescue)
+//   k_build       mask, fragment lists, DP job emission by size class       (ProduceReadAlignment up to ProcessNormalPair);
+//                 the large tier: k_build_wave
+//   launch_dp()   the gapped extensions of the job lists: mcx_dp_stage.hip   (ksw2_alignment / nw_alignment)
 //   k_finish      gates, scores, pair stats, flags, MAPQ, CIGAR, records    (ProduceReadAlignment tail, SamReport.cpp)
 // Pairs that overflow the tier-0 pair-state capacities are re-run in tier 1 (hard bounds).
 // The reference's per-chunk avgDist feedback is then replayed: per-chunk sums on the device, the
 // trajectory on the host, and only the pairs whose decision depends on the exact estimate re-run.
-// The -vcf bookkeeping of a batch (mcx_profile.h) follows when a profile is attached.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <type_traits>
-#include <vector>
-
-#include "../../include/mcx.h"
-#include "mcx_dp.h"
-#include "mcx_dp_lane2.h"
-#include "mcx_simple.h"
-#include "mcx_profile.h"
+// The -vcf bookkeeping of a batch (mcx_profile.hip) follows when a profile is attached.
+//
+// Also here: the error string of the library (mcx_last_error, mcx_set_error), the context (mcx_ctx_create / _free; its layout is
+// mcx_ctx.h's), -m (mcx_ctx_set_multi, mcx_multi_*), mcx_bwt_search_batch and mcx_cigar_words.  The other units of the library
+// reach this one through the ABI, pack_reads() and reserve_tier0().
+#include "mcx_ctx.h"
 #include <hipcub/hipcub.hpp>
-#include "mcx_internal.h"
-
-using namespace mcx;
 
 // ---------------------------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(MCX_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 int mcx_set_error(int code, const std::string &msg) { return fail(code, msg); }
 extern "C" const char *mcx_last_error(void) { return g_err.c_str(); }
 extern "C" int mcx_device_count(void)
@@ -57,353 +39,8 @@ extern "C" int mcx_device_count(void)
 }
 
 // ---------------------------------------------------------------------------------------------
-// index
-// ---------------------------------------------------------------------------------------------
-
-// Expands the sampled suffix array: the chain of LF steps that starts at a sampled row visits
-// exactly the rows whose bwt_sa() walk ends at the next sampled row, with values one lower per
-// step (SA[LF(k)] = SA[k] - 1).  One chain per lane, ~32 dependent block fetches each.
-__global__ void k_expand_sa(IndexView ix, uint64_t n_sa, uint64_t *full)
-{
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_sa) return;
-    uint64_t k = j * (uint64_t)ix.sa_intv;
-    uint64_t val = j == 0 ? ix.seq_len : ix.sa[j];
-    full[k] = j == 0 ? ~0ull : val;
-    const uint64_t mask = (uint64_t)ix.sa_intv - 1;
-    for (;;) {
-        k = fm_lf(ix, k);
-        val -= 1;
-        if ((k & mask) == 0) break;
-        full[k] = val;
-    }
-}
-
-// the derived form of the index blocks (mcx_fm.h fm_derive_block): one thread per block that holds symbols
-__global__ void k_derive_bwt(uint32_t *bwt, uint64_t n_blocks)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_blocks) fm_derive_block(bwt + (i << 4));
-}
-
-static int derive_bwt(mcx_index *ix)
-{
-    const uint64_t n_blocks = (ix->host.seq_len + 127) / 128;
-    k_derive_bwt<<<(unsigned)((n_blocks + 255) / 256), 256>>>((uint32_t *)ix->d_bwt, n_blocks);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-
-__global__ void k_build_ktab(IndexView ix, int K, U4 *tab)
-{
-    const uint64_t n = 1ull << (2 * K);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t x0, x1, x2;
-        ktab_entry(ix, (uint32_t)i, K, x0, x1, x2);
-        tab[i] = ktab_pack(x0, x1, x2);
-    }
-}
-
-// the K-mer jump table of the seeding walk (mcx_fm.h): 16 bytes per K-mer, K from the text length
-// (MCX_KTAB_K overrides it for experiments)
-static int build_rank(mcx_index *ix);
-static int build_ktab(mcx_index *ix)
-{
-    int K = ktab_k_for(ix->view.seq_len);
-    if (const char *e = getenv("MCX_KTAB_K")) { const int k = atoi(e); if (k >= 4 && k <= 16) K = k; } // (16: 69 GB — one pair step fewer per search; no room for it beside the -vcf planes)
-    const size_t bytes = (size_t)16 << (2 * K);
-    hipError_t e = hipMalloc(&ix->d_ktab, bytes);
-    if (e != hipSuccess) { g_err = std::string("hipMalloc(ktab): ") + hipGetErrorString(e); return MCX_ERR_DEVICE; }
-    ix->view.ktab = nullptr; ix->view.ktab_k = K;
-    k_build_ktab<<<8192, 256>>>(ix->view, K, (U4 *)ix->d_ktab);
-    e = hipDeviceSynchronize();
-    if (e != hipSuccess) { g_err = std::string("k_build_ktab: ") + hipGetErrorString(e); return MCX_ERR_DEVICE; }
-    ix->view.ktab = (const uint32_t *)ix->d_ktab;
-    ix->hbm_bytes += (int64_t)bytes;
-    return build_rank(ix);
-}
-
-// the rank records of the seeding walk (mcx_fm.h RankChunk): one thread per .bwt block, four records per base
-__global__ void k_build_rank(const uint32_t *bwt, uint64_t n_blocks, uint64_t n_chunks, RankChunk *rank, unsigned long long *cross)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_blocks) return;
-    const uint32_t *blk = bwt + (i << 4);
-    uint64_t before[4];
-    for (int c = 0; c < 4; c++) before[c] = fm_plain_count((uint64_t)blk[2 * c] | ((uint64_t)blk[2 * c + 1] << 32));
-    for (int q = 0; q < 4; q++) {
-        const uint64_t chunk = 4 * i + q;
-        if (chunk >= n_chunks) break;
-        RankChunk out[4];
-        uint64_t ne[4], ng[4];
-        fm_rank_records(blk[8 + 2 * q], blk[9 + 2 * q], before, out, ne, ng);
-        for (int b = 0; b < 4; b++) {
-            rank[(uint64_t)b * n_chunks + chunk] = out[b];
-            if (ne[b] >> 32) atomicMin(&cross[b], (unsigned long long)chunk);
-            if (ng[b] >> 32) atomicMin(&cross[4 + b], (unsigned long long)chunk);
-            before[b] += (uint64_t)__popc(out[b].eq);
-        }
-    }
-}
-
-static int build_rank(mcx_index *ix)
-{
-    if (!ix->view.sa_full || getenv("MCX_NO_RANK")) return 0; // (the walk then counts in the .bwt blocks: MCX_NO_RANK for experiments)
-    // a record keeps its two running counts in 32 bits plus ONE crossing chunk per base and count (rank_cross): exact while no count
-    // passes 2^32 twice, i.e. below 2^33 symbols.  Longer texts (genomes above ~4.29 Gbp) walk the .bwt blocks, which have no such limit.
-    if (ix->host.seq_len >= ((uint64_t)1 << 33)) return 0;
-    const uint64_t n_blocks = (ix->host.seq_len + 127) / 128, n_chunks = (ix->host.seq_len + 31) / 32;
-    const size_t bytes = (size_t)4 * n_chunks * sizeof(RankChunk) + 64;
-    unsigned long long *d_cross = nullptr, h_cross[8];
-    for (auto &x : h_cross) x = ~0ull;
-    hipError_t e = hipMalloc(&ix->d_rank, bytes);
-    if (e != hipSuccess) { g_err = std::string("hipMalloc(rank records): ") + hipGetErrorString(e); return MCX_ERR_DEVICE; }
-    HIP_TRY(hipMalloc((void **)&d_cross, sizeof h_cross));
-    e = hipMemcpy(d_cross, h_cross, sizeof h_cross, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_build_rank<<<(unsigned)((n_blocks + 255) / 256), 256>>>((const uint32_t *)ix->d_bwt, n_blocks, n_chunks, (RankChunk *)ix->d_rank, d_cross);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h_cross, d_cross, sizeof h_cross, hipMemcpyDeviceToHost);
-    (void)hipFree(d_cross);
-    if (e != hipSuccess) return fail(MCX_ERR_DEVICE, std::string("rank records: ") + hipGetErrorString(e)); // (d_rank is the index's: mcx_index_free releases it)
-    ix->view.rank = ix->d_rank; ix->view.rank_chunks = n_chunks;
-    for (int k = 0; k < 8; k++) ix->view.rank_cross[k] = h_cross[k];
-    ix->hbm_bytes += (int64_t)bytes;
-    // the pair records on top (two bases per step): MCX_NO_RANK2 for experiments, MCX_RANK2_CHECK=n extends n random intervals both ways
-    if (!ix->pair_records || getenv("MCX_NO_RANK2")) return 0;
-    const char *chk = getenv("MCX_RANK2_CHECK");
-    const int rc = mcx_build_pair_records(ix->view, &ix->d_rank2, &ix->d_rank2_c2, &ix->rank2_bytes, chk ? atoi(chk) : 0);
-    if (rc && ix->pair_records == MCX_INDEX_PAIRS_IF_ROOM) {
-        // nobody asked for the records by name (the CLI without -vcf takes them when there is room): a device that is too full for them
-        // — several shards on it, a smaller part — keeps the one-base walk, which needs nothing more
-        fprintf(stderr, "[mcx] the pair records do not fit this device (%s): the seeding walk takes one base per step\n", g_err.c_str());
-        (void)hipGetLastError();
-        g_err.clear();
-        ix->d_rank2 = ix->d_rank2_c2 = nullptr; ix->rank2_bytes = 0;
-        ix->view.rank2 = nullptr; ix->view.rank2_c2 = nullptr;
-        return 0;
-    }
-    if (rc) return rc;
-    ix->hbm_bytes += ix->rank2_bytes;
-    return 0;
-}
-
-static int upload(void **dst, const void *src, size_t bytes, size_t pad, int64_t &acc)
-{
-    HIP_TRY(hipMalloc(dst, bytes + pad));
-    if (pad) HIP_TRY(hipMemset((uint8_t *)*dst + bytes, 0, pad));
-    HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    acc += (int64_t)(bytes + pad);
-    return 0;
-}
-
-static int index_to_device(mcx_index *ix, int full_sa)
-{
-    HostIndex &h = ix->host;
-    int rc;
-    if ((rc = upload(&ix->d_bwt, h.bwt.data(), h.bwt.size() * 4, 128, ix->hbm_bytes))) return rc;
-    if ((rc = upload(&ix->d_sa, h.sa.data(), h.sa.size() * 8, 0, ix->hbm_bytes))) return rc;
-    if ((rc = upload(&ix->d_pac, h.pac.data(), h.pac.size(), 16, ix->hbm_bytes))) return rc;
-    if ((rc = upload(&ix->d_end_pos, h.end_pos.data(), h.end_pos.size() * 8, 0, ix->hbm_bytes))) return rc;
-    if ((rc = upload(&ix->d_end_chr, h.end_chr.data(), h.end_chr.size() * 4, 0, ix->hbm_bytes))) return rc;
-    if ((rc = upload(&ix->d_chr_fwd, h.chr_fwd.data(), h.chr_fwd.size() * 8, 0, ix->hbm_bytes))) return rc;
-    IndexView &v = ix->view;
-    v.bwt = (const uint32_t *)ix->d_bwt; v.sa = (const uint64_t *)ix->d_sa; v.sa_full = nullptr; v.ktab = nullptr; v.ktab_k = 0; v.rank = nullptr; v.rank_chunks = 0; for (auto &x : v.rank_cross) x = ~0ull; v.rank2 = nullptr; v.rank2_c2 = nullptr; v.rank2_lone = ~0ull; v.rank2_t0 = 0;
-    v.pac = (const uint8_t *)ix->d_pac;
-    v.end_pos = (const int64_t *)ix->d_end_pos; v.end_chr = (const int32_t *)ix->d_end_chr;
-    v.chr_fwd = (const int64_t *)ix->d_chr_fwd;
-    v.primary = h.primary; for (int i = 0; i < 5; i++) v.L2[i] = h.L2[i];
-    v.seq_len = h.seq_len; v.G = h.G; v.G2 = 2 * h.G;
-    v.n_ends = (int32_t)h.end_pos.size(); v.n_chr = (int32_t)h.chr_len.size(); v.sa_intv = h.sa_intv;
-    if ((rc = derive_bwt(ix))) return rc;
-    if (full_sa) {
-        size_t bytes = (size_t)(h.seq_len + 1) * 8;
-        HIP_TRY(hipMalloc(&ix->d_sa_full, bytes + 16)); // (+16: rows are fetched in pairs, seed_take)
-        ix->hbm_bytes += (int64_t)bytes;
-        uint64_t n_sa = h.sa.size();
-        k_expand_sa<<<(unsigned)((n_sa + 255) / 256), 256>>>(v, n_sa, (uint64_t *)ix->d_sa_full);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-        v.sa_full = (const uint64_t *)ix->d_sa_full;
-    }
-    return build_ktab(ix);
-}
-
-extern "C" int mcx_index_load(const char *prefix, int device, int full_sa, mcx_index **out)
-{
-    if (!prefix || !out) return fail(MCX_ERR_ARG, "mcx_index_load: null argument");
-    mcx_index *ix = new mcx_index();
-    std::string err;
-    if (!host_index_load(prefix, ix->host, err)) { delete ix; return fail(MCX_ERR_IO, err); }
-    ix->device = device;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) { delete ix; return fail(MCX_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
-    ix->pair_records = full_sa >= 2 ? full_sa : 0;
-    int rc = index_to_device(ix, full_sa);
-    if (rc) { mcx_index_free(ix); return rc; }
-    *out = ix;
-    return 0;
-}
-
-__global__ void k_pack_pac(const uint8_t *codes, uint64_t G, uint8_t *pac)
-{
-    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < G / 4 + 1; b += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t v = 0;
-        for (int k = 0; k < 4; k++) { uint64_t i = b * 4 + k; v = (v << 2) | (i < G ? (codes[i] & 3u) : 0u); }
-        pac[b] = (uint8_t)v;
-    }
-}
-
-static int index_from_arrays(mcx_index *ix, const DevIndexArrays &arr, const uint8_t *d_codes, int64_t G);
-
-extern "C" int mcx_index_from_codes(const uint8_t *d_codes, int32_t n_chr, const int32_t *chr_len, const char *const *chr_name,
-                                    int device, int full_sa, mcx_index **out, double *build_seconds)
-{
-    if (!d_codes || !chr_len || n_chr <= 0 || !out) return fail(MCX_ERR_ARG, "mcx_index_from_codes: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    mcx_index *ix = new mcx_index();
-    ix->device = device;
-    HostIndex &h = ix->host;
-    int64_t G = 0;
-    for (int i = 0; i < n_chr; i++) {
-        h.chr_len.push_back(chr_len[i]);
-        h.chr_name.push_back(chr_name && chr_name[i] ? chr_name[i] : ("chr" + std::to_string(i + 1)));
-        G += chr_len[i];
-    }
-    h.G = G;
-    host_index_finish(h);
-    DevIndexArrays arr;
-    int rc = mcx_build_suffix_index(d_codes, (uint64_t)G, full_sa != 0, arr, build_seconds);
-    if (rc) { delete ix; return rc; }
-    ix->pair_records = full_sa >= 2 ? full_sa : 0;
-    rc = index_from_arrays(ix, arr, d_codes, G);
-    if (rc) { mcx_index_free(ix); return rc; }
-    *out = ix;
-    return 0;
-}
-
-static int index_from_arrays(mcx_index *ix, const DevIndexArrays &arr, const uint8_t *d_codes, int64_t G)
-{
-    HostIndex &h = ix->host;
-    int rc;
-    h.primary = arr.primary; for (int i = 0; i < 5; i++) h.L2[i] = arr.L2[i];
-    h.seq_len = arr.seq_len; h.sa_intv = 32;
-    ix->d_bwt = arr.bwt; ix->d_sa = arr.sa; ix->d_sa_full = arr.sa_full;
-    ix->hbm_bytes = (int64_t)(arr.bwt_words * 4 + arr.n_sa * 8 + (arr.sa_full ? (arr.seq_len + 1) * 8 : 0));
-    ix->n_bwt_words = arr.bwt_words; ix->n_sa = arr.n_sa;
-    HIP_TRY(hipMalloc(&ix->d_pac, (size_t)G / 4 + 32));
-    k_pack_pac<<<1024, 256>>>(d_codes, (uint64_t)G, (uint8_t *)ix->d_pac);
-    HIP_TRY(hipGetLastError());
-    int64_t acc = 0;
-    if ((rc = upload(&ix->d_end_pos, h.end_pos.data(), h.end_pos.size() * 8, 0, acc))) return rc;
-    if ((rc = upload(&ix->d_end_chr, h.end_chr.data(), h.end_chr.size() * 4, 0, acc))) return rc;
-    if ((rc = upload(&ix->d_chr_fwd, h.chr_fwd.data(), h.chr_fwd.size() * 8, 0, acc))) return rc;
-    ix->hbm_bytes += acc + G / 4 + 32;
-    IndexView &v = ix->view;
-    v.bwt = (const uint32_t *)ix->d_bwt; v.sa = (const uint64_t *)ix->d_sa; v.sa_full = (const uint64_t *)ix->d_sa_full; v.ktab = nullptr; v.ktab_k = 0; v.rank = nullptr; v.rank_chunks = 0; for (auto &x : v.rank_cross) x = ~0ull; v.rank2 = nullptr; v.rank2_c2 = nullptr; v.rank2_lone = ~0ull; v.rank2_t0 = 0;
-    v.pac = (const uint8_t *)ix->d_pac;
-    v.end_pos = (const int64_t *)ix->d_end_pos; v.end_chr = (const int32_t *)ix->d_end_chr; v.chr_fwd = (const int64_t *)ix->d_chr_fwd;
-    v.primary = h.primary; for (int i = 0; i < 5; i++) v.L2[i] = h.L2[i];
-    v.seq_len = h.seq_len; v.G = h.G; v.G2 = 2 * h.G;
-    v.n_ends = (int32_t)h.end_pos.size(); v.n_chr = (int32_t)h.chr_len.size(); v.sa_intv = 32;
-    HIP_TRY(hipDeviceSynchronize());
-    if ((rc = derive_bwt(ix))) return rc;
-    return build_ktab(ix);
-}
-
-// writes <prefix>.bwt/.sa/.pac/.ann/.amb from an index built in HBM (no ambiguity holes: the
-// codes it was built from had none)
-extern "C" int mcx_index_save(const mcx_index *ix, const char *prefix)
-{
-    if (!ix || !prefix) return fail(MCX_ERR_ARG, "mcx_index_save: null argument");
-    if (!ix->n_bwt_words) return fail(MCX_ERR_ARG, "mcx_index_save: only indexes built with mcx_index_from_codes can be saved");
-    HIP_TRY(hipSetDevice(ix->device));
-    const HostIndex &h = ix->host;
-    std::string p(prefix);
-    std::vector<uint32_t> words(ix->n_bwt_words);
-    HIP_TRY(hipMemcpy(words.data(), ix->d_bwt, words.size() * 4, hipMemcpyDeviceToHost));
-    { // the file holds the plain counts (the blocks in HBM carry sub-block counts in their top bits: fm_derive_block)
-        const uint64_t n_blocks = (h.seq_len + 127) / 128;
-        for (uint64_t i = 0; i < n_blocks && i * 16 + 8 <= words.size(); i++) for (int x = 0; x < 4; x++) words[i * 16 + 2 * x + 1] &= 0xFFu;
-    }
-    FILE *f = fopen((p + ".bwt").c_str(), "wb");
-    if (!f) return fail(MCX_ERR_IO, "cannot write " + p + ".bwt");
-    fwrite(&h.primary, 8, 1, f); fwrite(h.L2 + 1, 8, 4, f); fwrite(words.data(), 4, words.size(), f); fclose(f);
-    std::vector<uint64_t> sa(ix->n_sa);
-    HIP_TRY(hipMemcpy(sa.data(), ix->d_sa, sa.size() * 8, hipMemcpyDeviceToHost));
-    f = fopen((p + ".sa").c_str(), "wb");
-    if (!f) return fail(MCX_ERR_IO, "cannot write " + p + ".sa");
-    const uint64_t intv = 32;
-    fwrite(&h.primary, 8, 1, f); fwrite(h.L2 + 1, 8, 4, f); fwrite(&intv, 8, 1, f); fwrite(&h.seq_len, 8, 1, f);
-    fwrite(sa.data() + 1, 8, sa.size() - 1, f); fclose(f);
-    const uint64_t G = (uint64_t)h.G;
-    std::vector<uint8_t> pac(G / 4 + 1);
-    HIP_TRY(hipMemcpy(pac.data(), ix->d_pac, pac.size(), hipMemcpyDeviceToHost));
-    f = fopen((p + ".pac").c_str(), "wb");
-    if (!f) return fail(MCX_ERR_IO, "cannot write " + p + ".pac");
-    fwrite(pac.data(), 1, (G >> 2) + ((G & 3) == 0 ? 0 : 1), f);
-    uint8_t ct = 0;
-    if (G % 4 == 0) fwrite(&ct, 1, 1, f);
-    ct = (uint8_t)(G % 4); fwrite(&ct, 1, 1, f); fclose(f);
-    f = fopen((p + ".ann").c_str(), "w");
-    if (!f) return fail(MCX_ERR_IO, "cannot write " + p + ".ann");
-    fprintf(f, "%lld %d %u\n", (long long)h.G, (int)h.chr_len.size(), 11u);
-    for (size_t i = 0; i < h.chr_len.size(); i++)
-        fprintf(f, "%d %s (null)\n%lld %d %d\n", 0, h.chr_name[i].c_str(), (long long)h.chr_fwd[i], h.chr_len[i], 0);
-    fclose(f);
-    f = fopen((p + ".amb").c_str(), "w");
-    if (!f) return fail(MCX_ERR_IO, "cannot write " + p + ".amb");
-    fprintf(f, "%lld %d %u\n", (long long)h.G, (int)h.chr_len.size(), 0u);
-    fclose(f);
-    return 0;
-}
-
-extern "C" void mcx_index_free(mcx_index *ix)
-{
-    if (!ix) return;
-    void *p[] = {ix->d_bwt, ix->d_sa, ix->d_sa_full, ix->d_pac, ix->d_end_pos, ix->d_end_chr, ix->d_chr_fwd, ix->d_ktab, ix->d_rank, ix->d_rank2, ix->d_rank2_c2};
-    for (void *q : p) if (q) (void)hipFree(q);
-    // (a caller that frees the index before its contexts — allowed: a context that is only freed afterwards touches no device memory of the index — leaves
-    //  the host object to the last mcx_ctx_free, which still counts itself out of it)
-    ix->d_bwt = ix->d_sa = ix->d_sa_full = ix->d_pac = ix->d_end_pos = ix->d_end_chr = ix->d_chr_fwd = ix->d_ktab = ix->d_rank = ix->d_rank2 = ix->d_rank2_c2 = nullptr;
-    if (ix->n_ctx.load() > 0) { ix->orphan.store(true); return; }
-    delete ix;
-}
-// gives back what an index holds above `full_sa` (2 -> 1: the pair records).  Contexts made before keep their view of the index: close them first.
-extern "C" int mcx_index_trim(mcx_index *ix, int full_sa)
-{
-    if (!ix) return fail(MCX_ERR_ARG, "mcx_index_trim: null argument");
-    if (full_sa < 1) return fail(MCX_ERR_UNSUPPORTED, "mcx_index_trim: only the pair records can be released (full_sa = 1)");
-    if (full_sa >= 2 || !ix->d_rank2) return 0;
-    // a context keeps pointers into what goes (the view it copies per pass, a batch under way): none may be alive
-    if (ix->n_ctx.load() > 0) return fail(MCX_ERR_ARG, "mcx_index_trim: " + std::to_string(ix->n_ctx.load()) + " context(s) of this index are still open; free them first");
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(ix->d_rank2); (void)hipFree(ix->d_rank2_c2);
-    ix->d_rank2 = ix->d_rank2_c2 = nullptr;
-    ix->view.rank2 = nullptr; ix->view.rank2_c2 = nullptr;
-    ix->hbm_bytes -= ix->rank2_bytes; ix->rank2_bytes = 0;
-    return 0;
-}
-extern "C" int64_t mcx_index_genome_size(const mcx_index *ix) { return ix->host.G; }
-extern "C" int32_t mcx_index_n_chr(const mcx_index *ix) { return (int32_t)ix->host.chr_len.size(); }
-extern "C" const char *mcx_index_chr_name(const mcx_index *ix, int32_t i) { return ix->host.chr_name[i].c_str(); }
-extern "C" int32_t mcx_index_chr_len(const mcx_index *ix, int32_t i) { return ix->host.chr_len[i]; }
-extern "C" int64_t mcx_index_hbm_bytes(const mcx_index *ix) { return ix->hbm_bytes; }
-
-// ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
-struct PairSel {             // which pairs a launch works on
-    const uint32_t *ids;     // batch pair id per local index (null: identity)
-    const int32_t *est;      // EstiDistance per local index
-    uint32_t n;
-};
-
-static __device__ __forceinline__ uint32_t sel_pair(const PairSel &s, uint32_t local) { return s.ids ? s.ids[local] : local; }
-
 // The chromosome tables (PosChrIdMap as sorted arrays) are binary-searched several times per
 // pair; each probe is a dependent load.  Blocks copy them to LDS once (when they fit) and the
 // per-pair code then searches LDS through the same pointers.
@@ -561,6 +198,12 @@ __global__ void __launch_bounds__(256) k_pack_reads(ReadBatch rb, int paired, in
 // The reads of a pass form one queue; a wavefront takes a chunk of it with one atomic whenever its lanes run dry, and a
 // lane that has finished a read takes the chunk's next one — every search iteration of the wave finds (nearly) all
 // lanes with work, and the launch ends when the queue does, not block by block.
+// (launched from two units: a batch's own step — mcx_batch_begin — and a batch on its way in — mcx_stream.hip)
+void pack_reads(const ReadBatch &rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag, hipStream_t s)
+{
+    k_pack_reads<<<(unsigned)(((uint64_t)rb.n_reads * (uint64_t)tpr + 255) / 256), 256, 0, s>>>(rb, paired, wpad, tpr, out, any_n, odd_flag);
+}
+
 constexpr int kSeedReadsPerLane = 4; // reads per lane and chunk (small selections: one, their launch is as long as its longest chain of reads)
 
 // FM steps a lane takes before the wave looks at its other lanes again (MCX_SEED_FM_BUDGET for experiments)
@@ -707,8 +350,6 @@ struct EarlyList { uint32_t *ids; int32_t *est; uint32_t *n; uint32_t cap; uint3
 // (dozens of hits to sort and cluster, a dozen candidates to build and score) sixty-three ordinary pairs wait.  So the pairs
 // of a pass are dealt to the lanes by weight — total seed hits, known once k_seed is done — heaviest class first: like sits
 // with like, and the long wavefronts start early.  Two small passes (count, place) make the permutation `order`.
-// (counters that many wavefronts add to sit one per 256 bytes: their atomics then run in different L2 channels instead of queueing on one line)
-constexpr int kCntPad = 64;
 constexpr int kWorkClasses = 6;
 static __device__ __forceinline__ int work_class(uint32_t hits) { return hits > 64 ? 0 : hits > 32 ? 1 : hits > 16 ? 2 : hits > 8 ? 3 : hits > 4 ? 4 : 5; }
 
@@ -1654,364 +1295,6 @@ __global__ void __launch_bounds__(64) k_build_wave(Ctx cx, ReadBatch rb, PairSel
     if (lane == 0) { if (my_cells) atomicAdd((unsigned long long *)cells, (unsigned long long)my_cells); if (bad) atomicAdd(unsupported, bad); }
 }
 
-// LDS per problem is sized per class: the small classes are latency-bound (a chain of dependent
-// fetches per problem), so what counts is how many problems a CU holds at once; the rare problem
-// that does not fit its class's LDS keeps its sequences / traceback in the workgroup's HBM scratch.
-template <int K> struct DpLds { static constexpr int seq = kDpLdsSeq, dir = kDpLdsDir; };
-template <> struct DpLds<1> { static constexpr int seq = 512, dir = 4096; }; // targets <= 64: e.g. 48 x 48 fits
-template <> struct DpLds<4> { static constexpr int seq = 1024, dir = 3072; }; // targets 65..256: the traceback of most does not fit 12 KB either — more problems per CU instead
-
-// one problem on the W lanes of a group (W = 64: the wave; 32: a half wave): stage the two strings,
-// sweep, trace back, hand the column string to the fragment
-template <int K, int W>
-static __device__ __forceinline__ void dp_run_job(const Ctx &cx, const JobSink &sink, uint32_t jb, const DpJob &job, const ReadBatch &rb,
-                                                  const PairSel &sel, const DpBuf &b)
-{
-    const int nr = cx.pm.paired ? 2 : 1;
-    const int lane = threadIdx.x & (W - 1);
-    const uint32_t read = sel_pair(sel, job.pair) * nr + job.slot;
-    ReadRef rd;
-    rd.ascii = rb.bases + rb.off[read]; rd.rlen = (int)(rb.off[read + 1] - rb.off[read]); rd.flipped = (cx.pm.paired && job.slot == 1) ? 1 : 0;
-    // q = read fragment, t = genome fragment; both reversed on the reverse strand (the
-    // reference also complements both, which no comparison can see)
-    for (int i = lane; i < job.rLen; i += W) b.q[i] = (uint8_t)read_code(rd, job.rev ? job.rPos + job.rLen - 1 - i : job.rPos + i);
-    for (int i = lane; i < job.gLen; i += W) b.t[i] = (uint8_t)ref_code(cx.ix, job.rev ? job.gPos + job.gLen - 1 - i : job.gPos + i);
-    dp_sync<W>();
-    PairState st = pair_state(cx.state, cx.lay, cx.caps, job.pair);
-    int score = 0;
-    DpSummary *sum = cx.dp_summary ? (DpSummary *)(st.ops + job.ops_off - kDpSum) : nullptr; // (stage_build left room for it)
-    const int w = dp_core<K, W>(cx.pm.use_nw != 0, job.rLen, job.gLen, b, st.ops + job.ops_off, &score, sum, (uint32_t)job.ops_off);
-    if (lane == 0) {
-        Frag f = st.frags[job.frag]; // one fetch, one store (the fields share two words)
-        f.ops_off = job.ops_off + w;
-        f.ops_len = job.rLen + job.gLen - w;
-        f.meta = sum ? (uint32_t)((job.ops_off - kDpSum) >> 3) + 1u : 0u;
-        st.frags[job.frag] = f;
-        sink.jobs[jb].score = score;
-    }
-    dp_sync<W>();
-}
-
-template <int K>
-__global__ void __launch_bounds__(64) k_dp_sel(Ctx cx, JobSink sink, ReadBatch rb, PairSel sel, uint8_t *scratch,
-                                               uint64_t scratch_stride)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[DpLds<K>::seq + DpLds<K>::dir];
-    uint8_t *spill = scratch + (uint64_t)blockIdx.x * scratch_stride;
-    const uint32_t n = min(*sink.count, sink.cap);
-    for (uint32_t jb = blockIdx.x; jb < n; jb += gridDim.x) {
-        const DpJob job = sink.jobs[jb];
-        dp_run_job<K, 64>(cx, sink, jb, job, rb, sel, dp_buffers(job.rLen, job.gLen, lds, spill, DpLds<K>::seq, DpLds<K>::dir));
-    }
-}
-
-// The one-wavefront classes, a group of problems at a time.  k_dp_sel sweeps a problem and then lets lane 0 walk its traceback
-// while 63 lanes look on — as many vector instructions as the sweep itself.  Here a wavefront sweeps up to 64 problems one after
-// the other, every sweep leaving its traceback bytes (and the two strings) in the wavefront's stretch of an HBM scratch that
-// stays in L2, and then walks the 64 tracebacks at once, one per lane.  Same bytes, same walks, same column strings.
-constexpr int kDpGroup = 64;
-struct DpGroupSlot { uint32_t off; int32_t score; }; // where a problem's strings and traceback bytes lie in the wave's scratch; its sweep's score
-
-template <int K>
-__global__ void __launch_bounds__(64) k_dp_group(Ctx cx, JobSink sink, ReadBatch rb, PairSel sel, uint8_t *scratch, uint64_t scratch_stride, uint32_t max_n)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[DpLds<K>::seq];
-    __shared__ DpGroupSlot slot[kDpGroup];
-    uint8_t *mine = scratch + (uint64_t)blockIdx.x * scratch_stride;
-    const uint32_t n = min(*sink.count, sink.cap);
-    if (n >= max_n) return; // (a long list: k_dp_lane's)
-    const int nr = cx.pm.paired ? 2 : 1;
-    const int lane = threadIdx.x;
-    const bool nw = cx.pm.use_nw != 0;
-    // (few problems: small groups, so that every wavefront of the launch gets some; many: whole groups of 64)
-    uint32_t group = (n + 2 * gridDim.x - 1) / (2 * gridDim.x);
-    group = group < 8 ? 8 : (group > (uint32_t)kDpGroup ? (uint32_t)kDpGroup : group);
-    for (uint32_t slice = blockIdx.x * group; slice < n; slice += gridDim.x * group) {
-        const uint32_t slice_end = min(slice + group, n);
-        for (uint32_t jb0 = slice; jb0 < slice_end;) {
-            // ---- the sweeps, one problem after the other, all lanes on each; the group ends when the wave's stretch of scratch is full ----
-            uint32_t used = 0;
-            int g_n = 0;
-            for (; jb0 + g_n < slice_end; g_n++) {
-                const DpJob job = sink.jobs[jb0 + g_n];
-                const uint32_t need = (uint32_t)((job.rLen + job.gLen + 15) & ~15) + (uint32_t)(job.rLen + job.gLen - 1) * (uint32_t)job.gLen;
-                if (g_n > 0 && used + need > scratch_stride) break; // (a stretch holds the largest problem of its class)
-                const uint32_t read = sel_pair(sel, job.pair) * nr + job.slot;
-                ReadRef rd;
-                rd.ascii = rb.bases + rb.off[read]; rd.rlen = (int)(rb.off[read + 1] - rb.off[read]); rd.flipped = (cx.pm.paired && job.slot == 1) ? 1 : 0;
-                uint8_t *gq = mine + used, *gt = gq + job.rLen, *gdir = gq + ((job.rLen + job.gLen + 15) & ~15);
-                DpBuf b;
-                const bool in_lds = job.rLen <= DpLds<K>::seq / 2 && job.gLen <= DpLds<K>::seq / 2;
-                b.q = in_lds ? lds : gq; b.t = in_lds ? lds + DpLds<K>::seq / 2 : gt; b.dir = gdir;
-                for (int i = lane; i < job.rLen; i += 64) { const uint8_t c = (uint8_t)read_code(rd, job.rev ? job.rPos + job.rLen - 1 - i : job.rPos + i); b.q[i] = c; if (in_lds) gq[i] = c; }
-                for (int i = lane; i < job.gLen; i += 64) { const uint8_t c = (uint8_t)ref_code(cx.ix, job.rev ? job.gPos + job.gLen - 1 - i : job.gPos + i); b.t[i] = c; if (in_lds) gt[i] = c; }
-                __syncthreads();
-                int score = 0;
-                dp_sweep<K, 64>(nw, job.rLen, job.gLen, b, &score);
-                if (lane == 0) { slot[g_n].off = used; slot[g_n].score = score; }
-                used += need;
-                __syncthreads();
-            }
-            __threadfence_block();
-            __syncthreads();
-            // ---- the walks, one problem per lane ----
-            if (lane < g_n) {
-                const uint32_t jb = jb0 + (uint32_t)lane;
-                const DpJob job = sink.jobs[jb];
-                const uint8_t *gq = mine + slot[lane].off, *gt = gq + job.rLen, *gdir = gq + ((job.rLen + job.gLen + 15) & ~15);
-                PairState st = pair_state(cx.state, cx.lay, cx.caps, job.pair);
-                DpSummary *sum = cx.dp_summary ? (DpSummary *)(st.ops + job.ops_off - kDpSum) : nullptr;
-                const int w = dp_trace(nw, job.rLen, job.gLen, gq, gt, gdir, st.ops + job.ops_off, sum, (uint32_t)job.ops_off);
-                Frag f = st.frags[job.frag];
-                f.ops_off = job.ops_off + w;
-                f.ops_len = job.rLen + job.gLen - w;
-                f.meta = sum ? (uint32_t)((job.ops_off - kDpSum) >> 3) + 1u : 0u;
-                st.frags[job.frag] = f;
-                sink.jobs[jb].score = slot[lane].score;
-            }
-            __syncthreads();
-            jb0 += (uint32_t)g_n;
-        }
-    }
-}
-
-constexpr int kDpHalfT = 32, kDpHalfQ = 64, kDpHalfLds = kDpHalfQ + kDpHalfT + (kDpHalfQ + kDpHalfT - 1) * kDpHalfT + 32;
-// One problem per LANE (mcx_dp_lane.h): a wavefront takes 64 problems of its list at a time; the group's words (queries, strip
-// edges, packed traceback flags) lie lane-interleaved in the wavefront's stretch of scratch, laid out for the group's longest
-// query and widest target, so that every store and load of the sweep is one line per 16 lanes.  order: the list's problems by
-// size (null: as listed), so that the 64 of a group finish together.
-template <int K, bool NW>
-__global__ void __launch_bounds__(64) k_dp_lane(Ctx cx, JobSink sink, const uint32_t *order, ReadBatch rb, PairSel sel, uint32_t *scratch, uint64_t stride_words, uint32_t *unsupported,
-                                                uint32_t min_n)
-{
-    const uint32_t n = min(*sink.count, sink.cap);
-    if (n < min_n) return; // (a short list: k_dp_group's)
-    const int lane = threadIdx.x;
-    const int nr = cx.pm.paired ? 2 : 1;
-    LaneMem mem; mem.base = scratch + (uint64_t)blockIdx.x * stride_words; mem.stride = 64; mem.lane = (uint32_t)lane;
-    for (uint32_t g0 = blockIdx.x * 64u; g0 < n; g0 += gridDim.x * 64u) {
-        const uint32_t jb = g0 + (uint32_t)lane;
-        const bool have = jb < n;
-        const uint32_t at = have ? (order ? order[jb] : jb) : 0u;
-        DpJob job;
-        if (have) job = sink.jobs[at]; else { job.rLen = 0; job.gLen = 0; }
-        int rows = job.rLen, strips = (job.gLen + K - 1) / K;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { rows = max(rows, __shfl_xor(rows, o, 64)); strips = max(strips, __shfl_xor(strips, o, 64)); }
-        const LaneLayout l = lane_layout<K, NW>(rows, strips);
-        if ((uint64_t)l.words * 64u > stride_words) { if (lane == 0) atomicAdd(unsupported, 1u); continue; } // (cannot happen: the lists' size limits are the strides')
-        if (!have) continue;
-        const uint32_t read = sel_pair(sel, job.pair) * nr + job.slot;
-        ReadRef rd;
-        rd.ascii = rb.bases + rb.off[read]; rd.rlen = (int)(rb.off[read + 1] - rb.off[read]); rd.flipped = (cx.pm.paired && job.slot == 1) ? 1 : 0;
-        rd.codes = (cx.packed && !(cx.read_ext[read] >> 31)) ? cx.packed + (uint64_t)read * cx.wpad : nullptr;
-        sink.jobs[at].score = lane_dp_job<K, NW>(cx, mem, l, job, rd);
-    }
-}
-
-// TWO problems per lane (mcx_dp_lane2.h): a wavefront takes 128 problems of its list at a time, lane l the neighbours 2l and 2l + 1 of the (shape-sorted)
-// list; every value of both recurrences in the sixteen bits it needs, problem A in the low half of a register and problem B in the high one, so that one
-// v_pk_*_i16 instruction advances both — the arithmetic width of the reference's own vectors (ksw2_alignment.cpp:70-248: sixteen int8 lanes).  Same words
-// per problem in the wavefront's stretch of scratch, same column strings and summaries as k_dp_lane (MCX_DP_X1=1 runs that one: the A/B of the parity tests).
-template <int K, bool NW>
-__global__ void __launch_bounds__(64) k_dp_lane2(Ctx cx, JobSink sink, const uint32_t *order, ReadBatch rb, PairSel sel, uint32_t *scratch, uint64_t stride_words, uint32_t *unsupported,
-                                                 uint32_t min_n)
-{
-    const uint32_t n = min(*sink.count, sink.cap);
-    if (n < min_n) return; // (a short list: k_dp_group's)
-    const int lane = threadIdx.x;
-    const int nr = cx.pm.paired ? 2 : 1;
-    LaneMem mem; mem.base = scratch + (uint64_t)blockIdx.x * stride_words; mem.stride = 64; mem.lane = (uint32_t)lane;
-    for (uint32_t g0 = blockIdx.x * 128u; g0 < n; g0 += gridDim.x * 128u) {
-        const uint32_t ja = g0 + 2u * (uint32_t)lane, jb = ja + 1u;
-        const bool have_a = ja < n, have_b = jb < n;
-        const uint32_t at_a = have_a ? (order ? order[ja] : ja) : 0u, at_b = have_b ? (order ? order[jb] : jb) : at_a;
-        DpJob job_a, job_b;
-        if (have_a) job_a = sink.jobs[at_a]; else { job_a.rLen = 0; job_a.gLen = 0; }
-        if (have_b) job_b = sink.jobs[at_b]; else job_b = job_a;
-        int rows = max(job_a.rLen, job_b.rLen), strips = (max(job_a.gLen, job_b.gLen) + K - 1) / K;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { rows = max(rows, __shfl_xor(rows, o, 64)); strips = max(strips, __shfl_xor(strips, o, 64)); }
-        const LaneLayout2 l = lane_layout2<K, NW>(rows, strips);
-        if ((uint64_t)l.words * 64u > stride_words) { if (lane == 0) atomicAdd(unsupported, 1u); continue; } // (cannot happen: the lists' size limits are the strides')
-        if (!have_a) continue;
-        ReadRef rd[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const DpJob &job = h ? job_b : job_a;
-            const uint32_t read = sel_pair(sel, job.pair) * nr + job.slot;
-            rd[h].flipped = (cx.pm.paired && job.slot == 1) ? 1 : 0;
-            // (the job says whether its read holds an N — k_build knew —: a read without one is its 2-bit words and nothing else, no look at its offsets or its flags)
-            if (cx.packed && job.score == 0) { rd[h].codes = cx.packed + (uint64_t)read * cx.wpad; rd[h].ascii = nullptr; rd[h].rlen = 0; }
-            else { rd[h].codes = nullptr; rd[h].ascii = rb.bases + rb.off[read]; rd[h].rlen = (int)(rb.off[read + 1] - rb.off[read]); }
-        }
-        int sc[2];
-        lane_dp_job2<K, NW>(cx, mem, l, job_a, rd[0], have_b, job_b, rd[1], sc);
-        sink.jobs[at_a].score = sc[0];
-        if (have_b) sink.jobs[at_b].score = sc[1];
-    }
-}
-
-// the three short lists (job_class): tiny <= 8 x 8 in strips of 8; small: targets <= 16, queries <= 32; half: targets <= 32, queries <= 64
-static uint64_t lane_short_words(int which) // ksw2's flags take more words than nw's: sized for them; a lane of k_dp_lane2 keeps two problems
-{
-    const uint64_t one = which == 0 ? 64ull * lane_layout<8, false>(kDpTiny, 1).words : which == 1 ? 64ull * lane_layout<16, false>(kDpSmallQ, 1).words : 64ull * lane_layout<16, false>(kDpHalfQ, 2).words;
-    const uint64_t two = which == 0 ? 64ull * lane_layout2<8, false>(kDpTiny, 1).words : which == 1 ? 64ull * lane_layout2<16, false>(kDpSmallQ, 1).words : 64ull * lane_layout2<16, false>(kDpHalfQ, 2).words;
-    return std::max(one, two);
-}
-
-// ---- the problems of a long list by shape ------------------------------------------------------------------------------------
-// A wavefront of k_dp_lane runs as long as the longest query times the most strips among its problems.  The two long lists
-// (targets of 17-64 and of 65-256 bases, queries of any length) are therefore dealt to the wavefronts by shape: 1024 buckets of
-// (strips, query length in 64 classes), largest first; within a bucket the problems differ by less than 4 rows for reads of up
-// to 256 bases (8 / 16 rows for longer ones).  With the 16 row classes this began with, a wavefront's rows were the class's
-// largest — 7.5 rows above its problems' mean, a sixth of the cells of config 5's 45-row problems computed for nothing.  Three
-// small passes — count per bucket, start of every bucket, place — over the list's 40-byte records; the order among equals is
-// whatever the atomics give (no result depends on it).
-constexpr int kDpBuckets = 1024, kDpRowClasses = 64, kDpSortTile = 8;
-static __device__ __forceinline__ int dp_bucket(const DpJob &j, int row_shift)
-{
-    const int strips = (j.gLen + 15) >> 4, rows = min(kDpRowClasses - 1, j.rLen >> row_shift);
-    return (min(16, max(strips, 1)) - 1) * kDpRowClasses + rows; // (0..1023; the largest shapes get the largest numbers)
-}
-
-__global__ void __launch_bounds__(256) k_dp_sort_count(JobSink sink, int row_shift, uint32_t *counts, uint32_t min_n)
-{
-    __shared__ uint32_t h[kDpBuckets];
-    const uint32_t n = min(*sink.count, sink.cap);
-    if (n < min_n) return;
-    for (int b = threadIdx.x; b < kDpBuckets; b += 256) h[b] = 0u;
-    __syncthreads();
-    for (uint32_t base = blockIdx.x * (256u * kDpSortTile); base < n; base += gridDim.x * (256u * kDpSortTile))
-        for (int t = 0; t < kDpSortTile; t++) {
-            const uint32_t i = base + t * 256u + threadIdx.x;
-            if (i < n) atomicAdd(&h[dp_bucket(sink.jobs[i], row_shift)], 1u);
-        }
-    __syncthreads();
-    for (int b = threadIdx.x; b < kDpBuckets; b += 256) if (h[b]) atomicAdd(&counts[b], h[b]);
-}
-
-// counts[0..1024) -> cursor[b] = where bucket b begins when the buckets are laid out from the largest shape down
-__global__ void __launch_bounds__(256) k_dp_sort_scan(const uint32_t *counts, uint32_t *cursor)
-{
-    __shared__ uint32_t c[kDpBuckets], part[256];
-    constexpr int per = kDpBuckets / 256;
-    // thread t owns the buckets kDpBuckets-1 - (per t .. per t + per-1): the largest shapes first
-    uint32_t mine[per], sum = 0;
-    for (int k = 0; k < per; k++) { mine[k] = counts[kDpBuckets - 1 - (per * (int)threadIdx.x + k)]; sum += mine[k]; }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint32_t at = 0; for (int k = 0; k < 256; k++) { const uint32_t m = part[k]; part[k] = at; at += m; } }
-    __syncthreads();
-    uint32_t at = part[threadIdx.x];
-    for (int k = 0; k < per; k++) { c[per * threadIdx.x + k] = at; at += mine[k]; }
-    for (int k = 0; k < per; k++) cursor[kDpBuckets - 1 - (per * (int)threadIdx.x + k)] = c[per * threadIdx.x + k];
-}
-
-__global__ void __launch_bounds__(256) k_dp_sort_place(JobSink sink, int row_shift, uint32_t *cursor, uint32_t *order, uint32_t min_n)
-{
-    __shared__ uint32_t h[kDpBuckets], at[kDpBuckets];
-    const uint32_t n = min(*sink.count, sink.cap);
-    if (n < min_n) return;
-    for (uint32_t base = blockIdx.x * (256u * kDpSortTile); base < n; base += gridDim.x * (256u * kDpSortTile)) {
-        for (int b = threadIdx.x; b < kDpBuckets; b += 256) h[b] = 0u;
-        __syncthreads();
-        int b[kDpSortTile];
-        uint32_t rank[kDpSortTile];
-#pragma unroll
-        for (int t = 0; t < kDpSortTile; t++) {
-            const uint32_t i = base + t * 256u + threadIdx.x;
-            b[t] = i < n ? dp_bucket(sink.jobs[i], row_shift) : -1;
-            rank[t] = b[t] >= 0 ? atomicAdd(&h[b[t]], 1u) : 0u;
-        }
-        __syncthreads();
-        for (int q = threadIdx.x; q < kDpBuckets; q += 256) at[q] = h[q] ? atomicAdd(&cursor[q], h[q]) : 0u;
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < kDpSortTile; t++) if (b[t] >= 0) order[at[b[t]] + rank[t]] = base + t * 256u + threadIdx.x;
-        __syncthreads();
-    }
-}
-
-// words a wavefront's stretch of scratch must hold for a list whose problems have at most `rows` query bases and `strips` strips
-template <int K>
-static uint64_t lane_stride_words(bool nw, int rows, int strips, bool x2)
-{
-    if (x2) return 64ull * (nw ? lane_layout2<K, true>(rows, strips).words : lane_layout2<K, false>(rows, strips).words);
-    return 64ull * (nw ? lane_layout<K, true>(rows, strips).words : lane_layout<K, false>(rows, strips).words);
-}
-
-template <int K>
-static void launch_dp_lane(bool nw, bool x2, unsigned blocks, hipStream_t s, const Ctx &cx, const JobSink &sink, const uint32_t *order, const ReadBatch &rb, const PairSel &sel,
-                           uint32_t *scratch, uint64_t stride_words, uint32_t *unsupported, uint32_t min_n)
-{
-    if (x2) {
-        if (nw) k_dp_lane2<K, true><<<blocks, 64, 0, s>>>(cx, sink, order, rb, sel, scratch, stride_words, unsupported, min_n);
-        else k_dp_lane2<K, false><<<blocks, 64, 0, s>>>(cx, sink, order, rb, sel, scratch, stride_words, unsupported, min_n);
-        return;
-    }
-    if (nw) k_dp_lane<K, true><<<blocks, 64, 0, s>>>(cx, sink, order, rb, sel, scratch, stride_words, unsupported, min_n);
-    else k_dp_lane<K, false><<<blocks, 64, 0, s>>>(cx, sink, order, rb, sel, scratch, stride_words, unsupported, min_n);
-}
-
-// targets <= 32 (queries <= 64) of the one-column-per-lane class: two problems per wave, 32 lanes each — the
-// class is bound by vector instructions issued, and most of its targets are that short
-
-__global__ void __launch_bounds__(256) k_dp_half(Ctx cx, JobSink sink, ReadBatch rb, PairSel sel)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[8 * kDpHalfLds];
-    const int group = threadIdx.x >> 5;
-    uint8_t *mine = lds + group * kDpHalfLds;
-    DpBuf b; b.q = mine; b.t = mine + kDpHalfQ; b.dir = mine + kDpHalfQ + kDpHalfT;
-    const uint32_t n = min(*sink.count, sink.cap);
-    for (uint32_t jb = blockIdx.x * 8 + group; jb < n; jb += gridDim.x * 8)
-        dp_run_job<1, 32>(cx, sink, jb, sink.jobs[jb], rb, sel, b);
-}
-
-// one tiny problem per lane (mcx_dp.h kDpTiny)
-__global__ void __launch_bounds__(256) k_dp_tiny(Ctx cx, JobSink sink, ReadBatch rb, PairSel sel)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[256 * kDpTinyLds];
-    uint8_t *mine = lds + threadIdx.x * kDpTinyLds;
-    DpBuf b; b.q = mine; b.t = mine + kDpTiny; b.dir = mine + 2 * kDpTiny;
-    const uint32_t n = min(*sink.count, sink.cap);
-    for (uint32_t jb = blockIdx.x * blockDim.x + threadIdx.x; jb < n; jb += gridDim.x * blockDim.x)
-        dp_run_job<kDpTiny, 1>(cx, sink, jb, sink.jobs[jb], rb, sel, b);
-}
-
-// four small problems per wave, sixteen per block; each 16-lane group owns 800 bytes of LDS
-__global__ void __launch_bounds__(256) k_dp_small(Ctx cx, JobSink sink, ReadBatch rb, PairSel sel)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[16 * kDpSmallLds];
-    const int nr = cx.pm.paired ? 2 : 1;
-    const int group = threadIdx.x >> 4, lane = threadIdx.x & 15;
-    uint8_t *mine = lds + group * kDpSmallLds;
-    const uint32_t n = min(*sink.count, sink.cap);
-    for (uint32_t jb = blockIdx.x * 16 + group; jb < n; jb += gridDim.x * 16) {
-        const DpJob job = sink.jobs[jb];
-        const uint32_t read = sel_pair(sel, job.pair) * nr + job.slot;
-        ReadRef rd;
-        rd.ascii = rb.bases + rb.off[read]; rd.rlen = (int)(rb.off[read + 1] - rb.off[read]); rd.flipped = (cx.pm.paired && job.slot == 1) ? 1 : 0;
-        DpBuf b; b.q = mine; b.t = mine + kDpSmallQ; b.dir = mine + 64;
-        for (int i = lane; i < job.rLen; i += 16) b.q[i] = (uint8_t)read_code(rd, job.rev ? job.rPos + job.rLen - 1 - i : job.rPos + i);
-        if (lane < job.gLen) b.t[lane] = (uint8_t)ref_code(cx.ix, job.rev ? job.gPos + job.gLen - 1 - lane : job.gPos + lane);
-        dp_sync<16>();
-        PairState st = pair_state(cx.state, cx.lay, cx.caps, job.pair);
-        int score = 0;
-        DpSummary *sum = cx.dp_summary ? (DpSummary *)(st.ops + job.ops_off - kDpSum) : nullptr;
-        const int w = dp_core<1, 16>(cx.pm.use_nw != 0, job.rLen, job.gLen, b, st.ops + job.ops_off, &score, sum, (uint32_t)job.ops_off);
-        if (lane == 0) {
-            Frag f = st.frags[job.frag]; // one fetch, one store (the fields share two words)
-            f.ops_off = job.ops_off + w;
-            f.ops_len = job.rLen + job.gLen - w;
-            f.meta = sum ? (uint32_t)((job.ops_off - kDpSum) >> 3) + 1u : 0u;
-            st.frags[job.frag] = f;
-            sink.jobs[jb].score = score;
-        }
-        dp_sync<16>();
-    }
-}
-
 // -m: the lines of a read after its first (emit_extra) go to an extras pool that the finish kernel fills in no particular order; per read
 // {record offset, records, word offset, words} says where its lines went.  A re-run pair writes a fresh entry (what it took before is left
 // unreferenced); a pair that did not fit says so with kMxOver in its count and is mapped again once the pool has grown (multi_close).
@@ -2093,21 +1376,11 @@ __global__ void __launch_bounds__(256, MCX_FINISH_WAVES) k_finish(Ctx cx, ReadBa
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
-// The MCX_* switches of DESIGN §3 (none changes a result), read ONCE when a context is made: nothing in the launch path asks the
-// environment.  What was measured slower and served no test is gone (the heavy pairs clustered first, one DP stream per list, the
-// ungrouped wavefront DP, the narrow comparison windows of the seeding walk, mate rescue a workgroup per pair for every pair).
-struct Knobs {
-    bool timing = false, seed_one_base = false, dp_by_wave = false, dp_lane_always = false, dp_x1 = false, late_reseed = false, no_work_order = false, no_simple = false,
-         simple_no_dp = false, cluster_by_lane = false, rescue_in_line = false, build_by_lane = false, no_sums_cache = false, prof_by_column = false,
-         tier1_hist = false, dp_hist = false, no_tier_overlap = false, no_late_overlap = false, no_prof_overlap = false, no_prepack = false, no_tier1_grow = false;
-    int seed_fm_budget = 6, build_wave_limit = 0x7fffffff;
-    uint32_t order_min = 16384u;
-};
 static Knobs knobs_read()
 {
     Knobs k;
     auto on = [](const char *name) { return getenv(name) != nullptr; };
-    k.timing = on("MCX_TIMING"); k.seed_one_base = on("MCX_SEED_ONE_BASE"); k.dp_by_wave = on("MCX_DP_BY_WAVE"); k.dp_lane_always = on("MCX_DP_LANE_ALWAYS"); k.dp_x1 = on("MCX_DP_X1");
+    k.timing = on("MCX_TIMING"); k.seed_one_base = on("MCX_SEED_ONE_BASE"); k.dp_by_wave = on("MCX_DP_BY_WAVE"); k.dp_lane_always = on("MCX_DP_LANE_ALWAYS");
     k.late_reseed = on("MCX_LATE_RESEED"); k.no_work_order = on("MCX_NO_WORK_ORDER"); k.no_simple = on("MCX_NO_SIMPLE"); k.simple_no_dp = on("MCX_SIMPLE_NO_DP");
     k.cluster_by_lane = on("MCX_CLUSTER_BY_LANE"); k.rescue_in_line = on("MCX_RESCUE_IN_LINE"); k.build_by_lane = on("MCX_BUILD_BY_LANE");
     k.no_sums_cache = on("MCX_NO_SUMS_CACHE"); k.prof_by_column = on("MCX_PROF_BY_COLUMN"); k.tier1_hist = on("MCX_TIER1_HIST"); k.dp_hist = on("MCX_DP_HIST");
@@ -2124,183 +1397,7 @@ static Knobs knobs_read()
     return k;
 }
 
-struct Tier {
-    Caps caps;
-    Layout lay;
-    uint8_t *state = nullptr;
-    uint32_t max_pairs = 0;
-    uint32_t grow_to = 0; // the large tier: how many pair records it may grow to when a batch's heavy pairs do not fit one pass (tier1_grow; 0 = fixed)
-};
-
 constexpr uint32_t kPoutSel = 1u << 16; // pair outcomes gathered per copy (run_selection)
-enum { CNT_TASKS = 0, CNT_RESCUE = 1 * kCntPad, CNT_JOB0 = 2 * kCntPad, CNT_JOB1 = 3 * kCntPad, CNT_JOB2 = 4 * kCntPad, CNT_JOB3 = 5 * kCntPad,
-       CNT_JOB4 = 6 * kCntPad, CNT_JOB5 = 7 * kCntPad, CNT_OV = 8 * kCntPad, CNT_LF = 9 * kCntPad, CNT_CELLS = 10 * kCntPad, CNT_UNSUP = 11 * kCntPad,
-       CNT_QUEUE = 12 * kCntPad, CNT_EARLY = 13 * kCntPad, CNT_LATE = 14 * kCntPad, CNT_RTASK = 15 * kCntPad, CNT_RPLAN = 16 * kCntPad, CNT_RESCUE_N = 17 * kCntPad, CNT_RSEED = 18 * kCntPad,
-       CNT_SIMPLE = 19 * kCntPad, CNT_EARLY_HITS = 20 * kCntPad, CNT_SIMPLE_LATER = 21 * kCntPad, CNT_SIMPLE_JOBS = 22 * kCntPad, CNT_N = 23 * kCntPad,
-       // behind the counters proper, cleared with them at the start of a pass (a memset in the middle of a pass was seen to sit 1.4 ms in its queue):
-       CNT_ORDER = CNT_N, CNT_DP_SORT = CNT_ORDER + 16 * kCntPad, CNT_ALL = CNT_DP_SORT + 4 * kDpBuckets };
-constexpr uint32_t kLateRoom = 2048; // pairs of a pass that may run over after clustering and still go through the large tier beside it
-
-// What a pass over a selection of pairs works with besides the pair records: stream, counters, work lists, DP scratch.
-// The context holds two sets, so that the large tier can map the heavy pairs of a pass (listed while the pass clusters)
-// on a stream of its own while the rest of the pass is still under way.
-struct PassRes {
-    hipStream_t stream = nullptr;
-    uint32_t *d_cnt = nullptr, *h_cnt = nullptr;
-    uint2 *d_tasks = nullptr; uint32_t task_cap = 0;
-    DpJob *d_jobs[kDpClasses] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; uint32_t job_cap[kDpClasses] = {0, 0, 0, 0, 0, 0};
-    uint32_t *d_rescue = nullptr; uint32_t rescue_cap = 0;
-    uint32_t *d_kscratch = nullptr; // k_rescue's scratch (not owned: a third of the context's)
-    RescueTask *d_rtasks = nullptr; RescueRes *d_rres = nullptr; Hit *d_rseeds = nullptr; RescuePlan *d_rplans = nullptr; uint32_t *d_rescue_n = nullptr; // mate rescue window by window
-    uint32_t rtask_cap = 0, rseed_cap = 0;
-    uint8_t *d_dp_scratch[3] = {nullptr, nullptr, nullptr}; uint64_t dp_stride[3] = {0, 0, 0}; uint32_t dp_blocks[3] = {0, 0, 0};
-    uint32_t *d_dp_lane = nullptr; uint32_t dp_lane_blocks = 0; // k_dp_lane's words for the three short lists (tiny | small | half), dp_lane_blocks wavefronts each
-    uint32_t *d_dp_order[2] = {nullptr, nullptr}; // the two long lists by shape (k_dp_sort_*; their bucket counts and cursors: CNT_DP_SORT)
-    hipStream_t dp_stream[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t dp_fork = nullptr, dp_join[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t *d_ov = nullptr; uint32_t ov_cap = 0;
-    uint32_t *d_sel_ids = nullptr; int32_t *d_est = nullptr;
-    hipEvent_t ev[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-};
-
-struct BatchRun { // the batch between mcx_batch_begin and mcx_batch_end
-    bool open = false, sums_valid = false, keys_out = false;
-    ReadBatch rb; int paired = 0;
-    uint32_t n_pairs = 0, n_chunks = 0, longest = 0; // (longest read of the batch)
-    AlnRec *recs = nullptr; uint32_t *cig = nullptr; // records [n_reads]; the batch's CIGAR pool
-    uint32_t cig_cap = 0, cig_words = 0;             // its capacity (MCX_CIGAR_POOL_WORDS(n_reads)) and, once the batch is closed, the words taken
-    int64_t read_base = 0, mapped = 0;
-    unsigned long long hs[3] = {0, 0, 0};
-    std::vector<uint32_t> ok, ds; // per chunk: proper pairs; summed distance, then summed read lengths
-    const uint32_t *d_ok = nullptr, *d_ds = nullptr; // ... and where they lie on the device while sums_valid (the batch's tail keeps them in its own words, mcx_batch_sums in the per-read arrays)
-    const uint64_t *d_sorted_keys = nullptr; uint64_t n_keys = 0; uint32_t n_sparse_keys = 0;
-    std::chrono::steady_clock::time_point t0, t_begun; double ms_setup = 0; // (t_begun, ms_setup: MCX_TIMING)
-    mcx_stats *stats = nullptr;
-};
-
-struct mcx_ctx {
-    const mcx_index *idx = nullptr;
-    bool counted = false; // (among idx->n_ctx)
-    bool lens_checked = false; // the batch about to begin holds no read longer than max_read_len (mcx_stream_next says so for batches that came as 2-bit rows)
-    const uint32_t *lens_checked_off = nullptr; const uint8_t *lens_checked_bases = nullptr; // ... said of THESE buffers (the slot's) and of no others
-    // ... and is packed already (mcx_stream_submit_packed packed it behind its copy in, under the batch before it): where, from which bytes, mated or not, and its any-N word
-    struct PrePacked { const uint32_t *packed = nullptr; const uint8_t *bases = nullptr; int paired = 0; const uint32_t *any_n = nullptr; } pre;
-    int last_paired = 1;                 // what the last batch was mapped as: the guess a batch on its way in is packed under
-    const uint32_t *packed_now = nullptr; // the 2-bit form the batch in flight is mapped from (d_packed, or a slot's)
-    Knobs kn;
-    Params pm;
-    mcx_opts opts;
-    hipStream_t stream = nullptr;
-    Tier tier[2];
-    uint64_t max_reads = 0, max_bases = 0;
-    int rlen_max = 256;
-    uint2 *d_tasks = nullptr; uint32_t task_cap = 0;
-    DpJob *d_jobs[kDpClasses] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; uint32_t job_cap[kDpClasses] = {0, 0, 0, 0, 0, 0};
-    uint32_t *d_cnt = nullptr;   // CNT_N counters
-    uint32_t *h_cnt = nullptr;   // pinned mirror
-    uint32_t *d_rescue = nullptr; uint32_t rescue_cap = 0;
-    uint32_t *d_kscratch = nullptr; // k_rescue's scratch for reads with N
-    RescueTask *d_rtasks = nullptr; RescueRes *d_rres = nullptr; Hit *d_rseeds = nullptr; RescuePlan *d_rplans = nullptr; uint32_t *d_rescue_n = nullptr;
-    uint32_t rtask_cap = 0, rseed_cap = 0;
-    hipEvent_t ev_pack[2] = {nullptr, nullptr};
-    hipStream_t dp_stream[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t dp_fork = nullptr, dp_join[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint8_t *d_dp_scratch[3] = {nullptr, nullptr, nullptr}; uint64_t dp_stride[3] = {0, 0, 0}; uint32_t dp_blocks[3] = {0, 0, 0};
-    uint32_t *d_dp_lane = nullptr; uint32_t dp_lane_blocks = 0;
-    uint32_t *d_dp_order[2] = {nullptr, nullptr};
-    uint32_t *d_ov = nullptr; uint32_t ov_cap = 0;
-    uint32_t *d_sel_ids = nullptr; int32_t *d_est = nullptr;
-    uint32_t *d_read_ext = nullptr, *d_read_blocks = nullptr;
-    uint32_t *d_packed = nullptr; int wpad = 0; // 2-bit form of the batch's reads
-    uint32_t *d_order = nullptr; // the pairs of a pass by weight (k_order_*; their class counts: CNT_ORDER)
-    uint8_t *d_done = nullptr;                           // per pair of a pass: k_simple wrote its records (the per-pair kernels skip it)
-    uint32_t *d_sl_pairs = nullptr, *d_sl_list = nullptr; // the straight-line pairs that wait for a small gapped extension (SimpleLater)
-    SimpleJob *d_sl_jobs = nullptr; SimpleRes *d_sl_res = nullptr; uint32_t sl_cap = 0;
-    PairOut *d_pout = nullptr, *d_pout_sel = nullptr; // per-pair outcome of the finish stage; a gathered selection of it
-    uint8_t *d_mapq = nullptr; int mapq_rows = 0;
-    // -vcf bookkeeping (mcx_profile.h): caller-owned counter planes, per-read alignment detail
-    uint32_t *prof_planes = nullptr; int prof_max_dup = 5, prof_max_clip = 5;
-    ColItem *d_prof_items = nullptr; uint32_t prof_items_cap = 0; // fragments whose columns k_prof_cols walks
-    uint16_t *d_prof_match = nullptr; bool prof_settled = false, prof_broken = false; // (broken: a settle failed half way — some planes scanned, some not)
-    // exact-seed coverage as differences (mcx_profile.h); freed by mcx_profile_settle
-    uint8_t *d_detail = nullptr; DetailLayout dlay;
-    // One shard: a batch's bookkeeping is queued behind its mapping on a stream of its own and runs under the NEXT batch's kernels.  What the
-    // mapping writes for it exists twice (detail records, flag bytes: the sets change places when a batch's bookkeeping is queued), the batch's reads are kept
-    // in a copy of the context's (the caller's buffer is the caller's again when the call returns), and the bookkeeping has counters and an event list of its own.
-    struct ProfLater {
-        bool have = false, tried = false, pending = false, kept_now = false; // the resources exist; a batch's bookkeeping is queued and the host has not looked at its counts; the batch in flight has its reads kept
-        hipStream_t stream = nullptr, keep_stream = nullptr; hipEvent_t go = nullptr, done = nullptr, kept = nullptr, begun = nullptr;
-        uint8_t *d_detail_alt = nullptr, *d_admit_alt = nullptr, *d_keep_bases = nullptr, *d_keep_bases_alt = nullptr; uint32_t *d_keep_off = nullptr, *d_keep_off_alt = nullptr;
-        uint32_t *d_cnt = nullptr, *h_cnt = nullptr; SparseRec *d_ev = nullptr; uint32_t ev_cap = 0;
-        std::chrono::steady_clock::time_point t_queued;
-    } later;
-    uint64_t *d_keys[2] = {nullptr, nullptr}; uint8_t *d_admit = nullptr; void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-    SparseRec *d_sparse = nullptr; uint32_t sparse_cap = 0;
-    struct Archive { SparseRec *d = nullptr; uint64_t n = 0, cap = 0; std::vector<mcx_sparse_rec> *host = nullptr; };
-    Archive arch, arch_ev;                      // the tally records / discordant-pair events of the batches so far, still in HBM
-    uint64_t arch_limit = (uint64_t)1 << 28;    // (at most 16 GB)
-    SparseRec *h_sparse_pin = nullptr; uint32_t sparse_pin_recs = 1u << 18; // page-locked bounce buffer for their way to the host (16 MB)
-    std::vector<mcx_sparse_rec> h_sparse, h_events; // tallies (followed by what the last mcx_profile_sparse* call appended for its caller: n_tally is where that starts); discordant-pair events ('E')
-    size_t n_tally = 0;
-    uint64_t keys_cap = 0;       // keys the sort buffers hold
-    uint64_t *h_keys = nullptr; uint64_t h_keys_cap = 0; // pinned: the batch's keys for the exchange between shards
-    // the tail of a whole-batch pass queued behind its kernels, before the host waits for them (mcx_map_batch_dev: queue_batch_tail) — the
-    // seeding statistics, the per-chunk sums, the insert-size walk over them and the check of every pair's estimate, one copy back
-    struct Tail {
-        bool want = false, queued = false, ran = false; // asked for by the caller of this batch; queued by its pass and still standing; queued at all
-        int64_t state0[3] = {1000, 0, 0};      // avgDist, pairs, distance sum before the batch
-        uint32_t *d = nullptr;                 // device: [0..8) counters (n_redo, mapped), [8..8 + nc) the chunks' estimates
-        uint32_t *h = nullptr; uint32_t cap = 0; // page-locked: counters[8] | flags[4] | statistics (3 x u64) | ok[nc] ds[nc] ls[nc] est[nc]
-        hipEvent_t ev[2] = {nullptr, nullptr};
-    } tail;
-    uint32_t *d_batch_flags = nullptr; // [0] words taken in the batch's CIGAR pool, [1] longest read of the batch, [2] the pool ran over, [3] a read holds an N
-    BatchRun run;
-    PassRes t1;               // the large tier's own set (the members above are tier 0's); allocated when every suffix-array entry is resident
-    bool overlap_tiers = false;
-    bool dp_grown = false; // dp_scratch_grow() has had its one attempt
-    uint32_t job2_seen = 0; // the longest 65-256-column DP list of a tier-0 pass so far
-    volatile uint32_t *h_early = nullptr; uint32_t *d_early = nullptr; // page-locked words k_publish_early writes behind the clustering kernel: the host's view and the device's
-    PassRes t2;               // a third set: the large tier's pass over the pairs that ran over after clustering (k_build's list)
-    hipEvent_t ev_built = nullptr, ev_late_done = nullptr;
-    bool overlap_late = false;
-    hipEvent_t ev_clustered = nullptr;
-    // mcx_stream_*: three batches in flight (copy in | kernels | copy out), each in a slot of its own
-    struct Slot {
-        uint8_t *d_bases = nullptr; uint32_t *d_off = nullptr; AlnRec *d_recs = nullptr; uint32_t *d_cig = nullptr;
-        mcx_aln32 *d_recs32 = nullptr; // the records in 32 bytes each for their way out (mcx_stream_mapped32)
-        uint32_t *d_codes = nullptr, *d_len = nullptr, *d_err = nullptr; uint64_t *d_odd = nullptr; uint32_t odd_cap = 0; // mcx_stream_submit_packed: what arrives; restored to d_bases / d_off
-        uint32_t n_reads = 0; int state = 0; uint64_t seq = 0; // 0 free, 1 copy in started, 2 handed to the kernels, 3 copy out started
-        bool lens_checked = false; // the batch came as 2-bit rows: no read is longer than the context's slots (k_unpack_reads / k_neutralize saw to it)
-        uint32_t *h_err = nullptr; // pinned: d_err's word on its way out with the batch's records (mcx_stream_mapped / _mapped32 -> mcx_stream_collect)
-        uint32_t *d_prepack = nullptr, *d_any_n = nullptr; bool prepacked = false; int pre_paired = 0; // k_pack_reads' output made on the way in
-        hipEvent_t in_ready = nullptr, mapped = nullptr, out_done = nullptr;
-        // -m: the batch's extras on their way out with its records (slot_multi_out): in read order, the records as mcx_aln32
-        struct Extras {
-            bool have = false; uint32_t n_reads = 0, n_recs = 0, n_words = 0;
-            uint32_t *d_index = nullptr, *d_cig = nullptr; mcx_aln32 *d_recs = nullptr; uint32_t rec_cap = 0, word_cap = 0;
-            uint32_t *h_index = nullptr, *h_cig = nullptr; mcx_aln32 *h_recs = nullptr; uint32_t h_rec_cap = 0, h_word_cap = 0;
-        } mx;
-    } slot[3];
-    const Slot *collected = nullptr; // the slot mcx_stream_collect handed over last (mcx_stream_multi)
-    hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-    uint64_t stream_seq = 0, stream_bytes_in = 0, stream_bytes_out = 0;
-    void *d_scan_tmp = nullptr; size_t scan_tmp_bytes = 0; // the prefix sum of the read lengths (mcx_stream_submit_packed)
-    void *files_state = nullptr; void (*files_drop)(void *) = nullptr; // mcx_files.cpp's batch buffers (mcx_ctx_files_slot)
-    void *sam_state = nullptr; void (*sam_drop)(void *) = nullptr;     // mcx_sam.hip's device buffers (mcx_ctx_sam_slot)
-    // staging for the host-buffer entry point
-    uint8_t *d_bases = nullptr; uint32_t *d_off = nullptr; AlnRec *d_recs = nullptr; uint32_t *d_cig = nullptr;
-    hipEvent_t ev[12];
-    // -m (mcx_ctx_set_multi): the extras pool k_finish<true> fills, and the last batch's extras in read order (multi_close)
-    struct Multi {
-        bool on = false, ready = false;
-        uint32_t rec_cap = 0, word_cap = 0;            // the pool's
-        AlnRec *d_pool = nullptr; uint32_t *d_pool_cig = nullptr; uint32_t *d_cnt = nullptr; uint4 *d_ref = nullptr;
-        uint32_t *d_counts = nullptr;                  // records | words per read, [2][max_reads + 1], scanned into d_index | d_windex
-        uint32_t *d_index = nullptr, *d_windex = nullptr;
-        AlnRec *d_out = nullptr; uint32_t *d_out_cig = nullptr; uint32_t out_cap = 0, out_wcap = 0;
-        void *d_tmp = nullptr; size_t tmp_bytes = 0;
-        uint32_t n_reads = 0, n_recs = 0, n_words = 0;  // the last batch's
-    } mx;
-};
-
 static MultiOut multi_out(const mcx_ctx *c)
 {
     MultiOut m;
@@ -2334,27 +1431,7 @@ static Caps tier1_caps(int rlen_max)
     return c;
 }
 
-// (MCX_TIMING) a host wait that took long says so
-template <typename F>
-static inline hipError_t timed_wait(bool on, const char *what, int line, F &&f)
-{
-    if (!on) return f();
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = f();
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms > 15) fprintf(stderr, "[mcx] %.1f ms in %s (line %d)\n", ms, what, line);
-    return e;
-}
-static std::atomic<size_t> g_dmalloc_bytes(0); // (MCX_TIMING: what a context takes)
-template <class T>
-static int dmalloc(T **p, size_t n, int line = __builtin_LINE())
-{
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    g_dmalloc_bytes += n * sizeof(T);
-    static const bool log = getenv("MCX_ALLOC_LOG") != nullptr;
-    if (log && n * sizeof(T) >= ((size_t)256 << 20)) fprintf(stderr, "[mcx alloc] %8.2f GB at mcx_pipeline.hip:%d\n", (double)(n * sizeof(T)) / 1e9, line);
-    return 0;
-}
+std::atomic<size_t> g_dmalloc_bytes(0);
 
 static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o);
 
@@ -2368,7 +1445,6 @@ extern "C" int mcx_ctx_create(const mcx_index *idx, const mcx_opts *opts, mcx_ct
     if (o.max_batch_reads < 2) o.max_batch_reads = 2;
     mcx_ctx *c = new mcx_ctx();
     c->kn = knobs_read();
-    for (auto &e : c->ev) e = nullptr;
     const size_t before = g_dmalloc_bytes.load();
     const int rc = ctx_fill(c, idx, o);
     if (c->kn.timing) fprintf(stderr, "[mcx_ctx_create] %.2f GB of HBM for batches of %lld reads of up to %d bases\n", (double)(g_dmalloc_bytes.load() - before) / 1e9, (long long)o.max_batch_reads, (int)o.max_read_len);
@@ -2378,62 +1454,115 @@ extern "C" int mcx_ctx_create(const mcx_index *idx, const mcx_opts *opts, mcx_ct
     return 0;
 }
 
-struct mcx_ctx;
 // the window lists of mate rescue for a set of pass resources that lists up to `pairs` pairs
-static int rescue_alloc(mcx_ctx *c, uint64_t pairs, bool large, RescueTask **tasks, RescueRes **res, Hit **seeds, RescuePlan **plans, uint32_t **ids_n, uint32_t *task_cap, uint32_t *seed_cap)
+static int rescue_alloc(PassRes &t, uint64_t pairs, bool large)
 {
     int rc;
     // (the large tier's pairs have hundreds of candidates: many more windows per pair than tier 0's, whose lists stay short)
-    *task_cap = large ? 1u << 22 : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs, 1u << 18), 1u << 21);
-    if (const char *e = getenv("MCX_RESCUE_TASK_CAP")) *task_cap = (uint32_t)std::max(16, atoi(e)); // (tests: make the list run over)
-    *seed_cap = large ? *task_cap * 4 : *task_cap; // seeds are kept only of windows that beat the mate's best candidate (a few per pair; a heavy pair's windows mostly do)
-    if ((rc = dmalloc(tasks, *task_cap))) return rc;
-    if ((rc = dmalloc(res, *task_cap))) return rc;
-    if ((rc = dmalloc(seeds, (size_t)*seed_cap))) return rc;
-    if ((rc = dmalloc(plans, pairs))) return rc;
-    if ((rc = dmalloc(ids_n, pairs))) return rc;
+    t.rtask_cap = large ? 1u << 22 : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs, 1u << 18), 1u << 21);
+    if (const char *e = getenv("MCX_RESCUE_TASK_CAP")) t.rtask_cap = (uint32_t)std::max(16, atoi(e)); // (tests: make the list run over)
+    t.rseed_cap = large ? t.rtask_cap * 4 : t.rtask_cap; // seeds are kept only of windows that beat the mate's best candidate (a few per pair; a heavy pair's windows mostly do)
+    if ((rc = dmalloc(&t.d_rtasks, t.rtask_cap))) return rc;
+    if ((rc = dmalloc(&t.d_rres, t.rtask_cap))) return rc;
+    if ((rc = dmalloc(&t.d_rseeds, (size_t)t.rseed_cap))) return rc;
+    if ((rc = dmalloc(&t.d_rplans, pairs))) return rc;
+    if ((rc = dmalloc(&t.d_rescue_n, pairs))) return rc;
     return 0;
 }
 
-// a set of pass resources beside the context's own (PassRes): work lists for `pairs` pairs at a time, selections of up to `sel_cap`
-static int passres_alloc(mcx_ctx *c, PassRes &t, uint64_t pairs, uint64_t sel_cap, int priority)
+// what differs between the sets of pass resources (PassRes): tier 0's, and the side sets beside it (the large tier's, the late pairs')
+struct PassSizes {
+    bool tier0 = false;              // tier 0's stream is the context's: a blocking stream at default priority (callers' copies on the null stream order against it)
+    int priority = 0;                // a side set's streams
+    int n_side = 0;                  // side streams for the DP lists
+    uint64_t pairs = 0, sel_cap = 0; // pairs a pass lists at a time (rescue lists); selections (ids, estimates, overflow list)
+    bool rescue_large = false;       // the large tier's window lists (rescue_alloc)
+    uint32_t task_cap = 0;           // SA tasks (0: no list — a side set runs only with every suffix-array entry resident)
+    uint32_t job_cap[kDpClasses] = {0, 0, 0, 0, 0, 0};
+    uint64_t dp_stride[3] = {0, 0, 0}; uint32_t dp_blocks[3] = {0, 0, 0}, dp_lane_blocks = 0;
+    uint32_t h_cnt_words = CNT_N;
+};
+
+static PassSizes tier0_sizes(const mcx_ctx *c)
 {
-    int rc;
-    HIP_TRY(hipStreamCreateWithPriority(&t.stream, hipStreamNonBlocking, priority));
+    PassSizes z;
+    z.tier0 = true; z.n_side = 2;
+    z.pairs = z.sel_cap = c->max_reads;
+    z.task_cap = (uint32_t)std::min<uint64_t>(c->max_reads * 24, 0x7fffffffu);
+    for (int k = 0; k < kDpClasses; k++) {
+        z.job_cap[k] = (uint32_t)std::min<uint64_t>(c->max_reads * ((k == 0 || k == 4) ? 4 : ((k == 1 || k == 5) ? 2 : 1)) + 1024, 0x7fffffffu);
+        if (const char *e = getenv("MCX_JOB_CAP")) z.job_cap[k] = std::min<uint32_t>(z.job_cap[k], (uint32_t)std::max(1024, atoi(e))); // (tests: make the lists run over)
+    }
+    // DP traceback spill per block: 4 KB of sequences + (qlen + tlen - 1) * tlen direction bytes
+    // (the two grouped classes: a wavefront's stretch holds the strings and traceback bytes of a group of problems — k_dp_group —,
+    //  at least those of the class's largest one)
+    const uint64_t spill[3] = {(uint64_t)512 << 10, (uint64_t)1 << 20, kDpSpillSeq + (uint64_t)(2048 + 1024) * 1024};
+    uint32_t blocks[3] = {8192, 4096, 512}; // (the 65-256-column class at 2048 or 8192 wavefronts: the same DP stage, 3.3-3.8 ms)
+    if (const char *e = getenv("MCX_DP_BLOCKS1")) blocks[1] = (uint32_t)std::max(256, atoi(e)); // (experiments; a size that was asked for stays: dp_scratch_grow)
+    for (int k = 0; k < 3; k++) { z.dp_stride[k] = spill[k]; z.dp_blocks[k] = blocks[k]; }
+    z.dp_lane_blocks = 4096;
+    z.h_cnt_words = CNT_N + 8; // (+8: the seeding statistics of a batch, on their way to batch_close)
+    return z;
+}
+
+// a side set: work lists for `pairs` pairs at a time, selections of up to `sel_cap`
+static PassSizes side_sizes(const mcx_ctx *c, uint64_t pairs, uint64_t sel_cap, int priority)
+{
+    PassSizes z;
+    z.priority = priority;
     // side streams for the DP lists only where lists are long enough to share the chip: a stream that exists lands on one of the
     // runtime's few hardware queues, and a queue that waits for an event holds up every stream folded onto it (the late pairs' pass
     // once sat 4 ms behind the large tier's DP fork that way)
-    const int n_side = pairs >= 4096 ? 2 : 0;
-    for (int k = 0; k < n_side; k++) { HIP_TRY(hipStreamCreateWithPriority(&t.dp_stream[k], hipStreamNonBlocking, priority)); HIP_TRY(hipEventCreateWithFlags(&t.dp_join[k], hipEventDisableTiming)); }
+    z.n_side = pairs >= 4096 ? 2 : 0;
+    z.pairs = pairs; z.sel_cap = sel_cap; z.rescue_large = pairs >= 4096;
+    for (int k = 0; k < kDpClasses; k++) z.job_cap[k] = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs * 16, 1u << 20), c->t0.job_cap[k]);
+    const uint32_t blocks1[3] = {pairs >= 4096 ? 2048u : 256u, pairs >= 4096 ? 2048u : 128u, 256};
+    for (int k = 0; k < 3; k++) { z.dp_stride[k] = c->t0.dp_stride[k]; z.dp_blocks[k] = blocks1[k]; }
+    z.dp_lane_blocks = pairs >= 4096 ? 2048u : 256u;
+    return z;
+}
+
+static int passres_alloc(PassRes &t, const PassSizes &z)
+{
+    int rc;
+    if (z.tier0) HIP_TRY(hipStreamCreate(&t.stream));
+    else HIP_TRY(hipStreamCreateWithPriority(&t.stream, hipStreamNonBlocking, z.priority));
+    for (int k = 0; k < z.n_side; k++) {
+        if (z.tier0) HIP_TRY(hipStreamCreateWithFlags(&t.dp_stream[k], hipStreamNonBlocking));
+        else HIP_TRY(hipStreamCreateWithPriority(&t.dp_stream[k], hipStreamNonBlocking, z.priority));
+        HIP_TRY(hipEventCreateWithFlags(&t.dp_join[k], hipEventDisableTiming));
+    }
     HIP_TRY(hipEventCreateWithFlags(&t.dp_fork, hipEventDisableTiming));
     for (auto &e : t.ev) HIP_TRY(hipEventCreate(&e));
-    if ((rc = dmalloc(&t.d_cnt, CNT_ALL))) return rc;
-    HIP_TRY(hipHostMalloc((void **)&t.h_cnt, CNT_N * sizeof(uint32_t)));
+    t.task_cap = z.task_cap;
+    if (t.task_cap && (rc = dmalloc(&t.d_tasks, t.task_cap))) return rc;
     for (int k = 0; k < kDpClasses; k++) {
-        t.job_cap[k] = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs * 16, 1u << 20), c->job_cap[k]);
+        t.job_cap[k] = z.job_cap[k];
         if ((rc = dmalloc(&t.d_jobs[k], t.job_cap[k]))) return rc;
     }
-    t.rescue_cap = (uint32_t)pairs;
+    if ((rc = dmalloc(&t.d_cnt, CNT_ALL))) return rc;
+    HIP_TRY(hipHostMalloc((void **)&t.h_cnt, z.h_cnt_words * sizeof(uint32_t)));
+    t.rescue_cap = (uint32_t)z.pairs;
     if ((rc = dmalloc(&t.d_rescue, t.rescue_cap))) return rc;
-    if ((rc = rescue_alloc(c, pairs, pairs >= 4096, &t.d_rtasks, &t.d_rres, &t.d_rseeds, &t.d_rplans, &t.d_rescue_n, &t.rtask_cap, &t.rseed_cap))) return rc;
-    const uint32_t blocks1[3] = {pairs >= 4096 ? 2048u : 256u, pairs >= 4096 ? 2048u : 128u, 256};
+    if ((rc = rescue_alloc(t, z.pairs, z.rescue_large))) return rc;
     for (int k = 0; k < 3; k++) {
-        t.dp_stride[k] = c->dp_stride[k]; t.dp_blocks[k] = blocks1[k];
+        t.dp_stride[k] = z.dp_stride[k]; t.dp_blocks[k] = z.dp_blocks[k];
         if ((rc = dmalloc(&t.d_dp_scratch[k], (size_t)t.dp_stride[k] * t.dp_blocks[k]))) return rc;
     }
-    t.dp_lane_blocks = pairs >= 4096 ? 2048u : 256u;
+    t.dp_lane_blocks = z.dp_lane_blocks;
     if ((rc = dmalloc(&t.d_dp_lane, (size_t)(lane_short_words(0) + lane_short_words(1) + lane_short_words(2)) * t.dp_lane_blocks))) return rc;
     for (int k = 0; k < 2; k++) if ((rc = dmalloc(&t.d_dp_order[k], t.job_cap[1 + k]))) return rc;
-    t.ov_cap = (uint32_t)sel_cap;
+    t.ov_cap = (uint32_t)z.sel_cap;
     if ((rc = dmalloc(&t.d_ov, t.ov_cap))) return rc;
-    if ((rc = dmalloc(&t.d_sel_ids, sel_cap))) return rc;
-    if ((rc = dmalloc(&t.d_est, sel_cap))) return rc;
+    if ((rc = dmalloc(&t.d_sel_ids, z.sel_cap))) return rc;
+    if ((rc = dmalloc(&t.d_est, z.sel_cap))) return rc;
     return 0;
 }
 
+// (d_kscratch is the context's)
 static void passres_free(PassRes &t)
 {
-    void *q[] = {t.d_cnt, t.d_jobs[0], t.d_jobs[1], t.d_jobs[2], t.d_jobs[3], t.d_jobs[4], t.d_jobs[5], t.d_rescue, t.d_dp_scratch[0], t.d_dp_scratch[1],
+    void *q[] = {t.d_cnt, t.d_tasks, t.d_jobs[0], t.d_jobs[1], t.d_jobs[2], t.d_jobs[3], t.d_jobs[4], t.d_jobs[5], t.d_rescue, t.d_dp_scratch[0], t.d_dp_scratch[1],
                  t.d_dp_scratch[2], t.d_ov, t.d_sel_ids, t.d_est, t.d_rtasks, t.d_rres, t.d_rseeds, t.d_rplans, t.d_rescue_n, t.d_dp_lane, t.d_dp_order[0], t.d_dp_order[1]};
     for (void *x : q) if (x) (void)hipFree(x);
     if (t.h_cnt) (void)hipHostFree(t.h_cnt);
@@ -2451,11 +1580,7 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
     c->max_reads = (uint64_t)o.max_batch_reads;
     c->max_bases = c->max_reads * (uint64_t)c->rlen_max;
     HIP_TRY(hipSetDevice(idx->device));
-    HIP_TRY(hipStreamCreate(&c->stream));
-    for (int k = 0; k < 2; k++) { HIP_TRY(hipStreamCreateWithFlags(&c->dp_stream[k], hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&c->dp_join[k], hipEventDisableTiming)); }
-    HIP_TRY(hipEventCreateWithFlags(&c->dp_fork, hipEventDisableTiming));
     for (auto &e : c->ev_pack) HIP_TRY(hipEventCreate(&e));
-    for (auto &e : c->ev) HIP_TRY(hipEventCreate(&e));
     int rc = 0;
     c->tier[0].caps = tier0_caps(); c->tier[0].lay = make_layout(c->tier[0].caps); c->tier[0].max_pairs = (uint32_t)c->max_reads;
     c->tier[1].caps = tier1_caps(c->rlen_max); c->tier[1].lay = make_layout(c->tier[1].caps);
@@ -2473,36 +1598,9 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
     //  record the other half is 33 GB at 8 M reads — only single-end batches need a record per read)
     c->tier[0].max_pairs = 0;
     if ((rc = dmalloc(&c->tier[1].state, (size_t)c->tier[1].lay.stride * c->tier[1].max_pairs))) return rc;
-    c->task_cap = (uint32_t)std::min<uint64_t>(c->max_reads * 24, 0x7fffffffu);
-    if ((rc = dmalloc(&c->d_tasks, c->task_cap))) return rc;
-    for (int k = 0; k < kDpClasses; k++) {
-        c->job_cap[k] = (uint32_t)std::min<uint64_t>(c->max_reads * ((k == 0 || k == 4) ? 4 : ((k == 1 || k == 5) ? 2 : 1)) + 1024, 0x7fffffffu);
-        if (const char *e = getenv("MCX_JOB_CAP")) c->job_cap[k] = std::min<uint32_t>(c->job_cap[k], (uint32_t)std::max(1024, atoi(e))); // (tests: make the lists run over)
-        if ((rc = dmalloc(&c->d_jobs[k], c->job_cap[k]))) return rc;
-    }
-    if ((rc = dmalloc(&c->d_cnt, CNT_ALL))) return rc;
-    HIP_TRY(hipHostMalloc((void **)&c->h_cnt, (CNT_N + 8) * sizeof(uint32_t))); // (+8: the seeding statistics of a batch, on their way to batch_close)
-    c->rescue_cap = (uint32_t)c->max_reads;
-    if ((rc = dmalloc(&c->d_rescue, c->rescue_cap))) return rc;
-    if ((rc = rescue_alloc(c, c->max_reads, false, &c->d_rtasks, &c->d_rres, &c->d_rseeds, &c->d_rplans, &c->d_rescue_n, &c->rtask_cap, &c->rseed_cap))) return rc;
+    if ((rc = passres_alloc(c->t0, tier0_sizes(c)))) return rc;
     if ((rc = dmalloc(&c->d_kscratch, 3 * (size_t)kRescueBlocks * kRescueScratchWords))) return rc; // (one part per set of pass resources)
-    // DP traceback spill per block: 4 KB of sequences + (qlen + tlen - 1) * tlen direction bytes
-    // (the two grouped classes: a wavefront's stretch holds the strings and traceback bytes of a group of problems — k_dp_group —,
-    //  at least those of the class's largest one)
-    const uint64_t spill[3] = {(uint64_t)512 << 10, (uint64_t)1 << 20, kDpSpillSeq + (uint64_t)(2048 + 1024) * 1024};
-    uint32_t blocks[3] = {8192, 4096, 512}; // (the 65-256-column class at 2048 or 8192 wavefronts: the same DP stage, 3.3-3.8 ms)
-    if (const char *e = getenv("MCX_DP_BLOCKS1")) blocks[1] = (uint32_t)std::max(256, atoi(e)); // (experiments; a size that was asked for stays: dp_scratch_grow)
-    for (int k = 0; k < 3; k++) {
-        c->dp_stride[k] = spill[k]; c->dp_blocks[k] = blocks[k];
-        if ((rc = dmalloc(&c->d_dp_scratch[k], (size_t)spill[k] * blocks[k]))) return rc;
-    }
-    c->dp_lane_blocks = 4096;
-    if ((rc = dmalloc(&c->d_dp_lane, (size_t)(lane_short_words(0) + lane_short_words(1) + lane_short_words(2)) * c->dp_lane_blocks))) return rc;
-    for (int k = 0; k < 2; k++) if ((rc = dmalloc(&c->d_dp_order[k], c->job_cap[1 + k]))) return rc;
-    c->ov_cap = (uint32_t)c->max_reads;
-    if ((rc = dmalloc(&c->d_ov, c->ov_cap))) return rc;
-    if ((rc = dmalloc(&c->d_sel_ids, c->max_reads))) return rc;
-    if ((rc = dmalloc(&c->d_est, c->max_reads))) return rc;
+    c->t0.d_kscratch = c->d_kscratch;
     if ((rc = dmalloc(&c->d_read_ext, c->max_reads))) return rc;
     if ((rc = dmalloc(&c->d_read_blocks, c->max_reads))) return rc;
     if ((rc = dmalloc(&c->d_batch_flags, 4))) return rc;
@@ -2537,7 +1635,7 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
         // (human-like bench genome: 40.0 -> 37.4 ms per step)
         int pr_lo = 0, pr_hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
-        if ((rc = passres_alloc(c, c->t1, std::max(c->tier[1].max_pairs, c->tier[1].grow_to), c->max_reads, pr_hi))) return rc; // (lists for as many pairs as the records may grow to)
+        if ((rc = passres_alloc(c->t1, side_sizes(c, std::max(c->tier[1].max_pairs, c->tier[1].grow_to), c->max_reads, pr_hi)))) return rc; // (lists for as many pairs as the records may grow to)
         c->t1.d_kscratch = c->d_kscratch + (size_t)kRescueBlocks * kRescueScratchWords;
         HIP_TRY(hipEventCreate(&c->ev_clustered));
         c->overlap_tiers = true;
@@ -2549,7 +1647,7 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
         // and a small third set for the pairs that run over after clustering: they go through the large tier while the pass's
         // DP and finish stages run, in the last kLateRoom records of the tier, instead of in a pass of their own after it
         if (c->tier[1].max_pairs >= 4 * kLateRoom && !c->kn.no_late_overlap) {
-            if ((rc = passres_alloc(c, c->t2, kLateRoom, kLateRoom, pr_hi))) return rc;
+            if ((rc = passres_alloc(c->t2, side_sizes(c, kLateRoom, kLateRoom, pr_hi)))) return rc;
             c->t2.d_kscratch = c->d_kscratch + 2 * (size_t)kRescueBlocks * kRescueScratchWords;
             HIP_TRY(hipEventCreateWithFlags(&c->ev_built, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&c->ev_late_done, hipEventDisableTiming));
@@ -2565,12 +1663,9 @@ extern "C" void mcx_ctx_free(mcx_ctx *c)
     if (c->counted && c->idx && --c->idx->n_ctx == 0 && c->idx->orphan.load()) delete c->idx; // (the index was freed first: its host object waited for this)
     if (c->files_state && c->files_drop) c->files_drop(c->files_state);
     if (c->sam_state && c->sam_drop) c->sam_drop(c->sam_state);
-    void *p[] = {c->tier[0].state, c->tier[1].state, c->d_tasks, c->d_jobs[0], c->d_jobs[1], c->d_jobs[2], c->d_jobs[3], c->d_jobs[4], c->d_jobs[5],
-                 c->d_cnt, c->d_rescue, c->d_kscratch, c->d_rtasks, c->d_rres, c->d_rseeds, c->d_rplans, c->d_rescue_n, c->d_dp_scratch[0], c->d_dp_scratch[1], c->d_dp_scratch[2],
-                 c->d_ov, c->d_sel_ids, c->d_est, c->d_read_ext, c->d_read_blocks, c->d_pout, c->d_mapq,
-                 c->d_dp_lane, c->d_dp_order[0], c->d_dp_order[1], c->d_bases, c->d_off, c->d_recs, c->d_cig, c->d_detail, c->d_keys[0], c->d_keys[1], c->d_admit, c->d_sort_tmp, c->d_sparse, c->d_pout_sel, c->d_order, c->d_done, c->d_sl_pairs, c->d_sl_list, c->d_sl_jobs, c->d_sl_res, c->d_packed, c->d_batch_flags, c->d_scan_tmp, c->d_prof_match, c->d_prof_items};
+    void *p[] = {c->tier[0].state, c->tier[1].state, c->d_kscratch, c->d_read_ext, c->d_read_blocks, c->d_pout, c->d_mapq,
+                 c->d_bases, c->d_off, c->d_recs, c->d_cig, c->d_detail, c->d_keys[0], c->d_keys[1], c->d_admit, c->d_sort_tmp, c->d_sparse, c->d_pout_sel, c->d_order, c->d_done, c->d_sl_pairs, c->d_sl_list, c->d_sl_jobs, c->d_sl_res, c->d_packed, c->d_batch_flags, c->d_scan_tmp, c->d_prof_match, c->d_prof_items};
     for (void *q : p) if (q) (void)hipFree(q);
-    if (c->h_cnt) (void)hipHostFree(c->h_cnt);
     if (c->h_keys) (void)hipHostFree(c->h_keys);
     if (c->h_sparse_pin) (void)hipHostFree(c->h_sparse_pin);
     if (c->arch.d) (void)hipFree(c->arch.d);
@@ -2601,10 +1696,7 @@ extern "C" void mcx_ctx_free(mcx_ctx *c)
     }
     if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
     if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-    for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    for (int k = 0; k < 5; k++) { if (c->dp_stream[k]) (void)hipStreamDestroy(c->dp_stream[k]); if (c->dp_join[k]) (void)hipEventDestroy(c->dp_join[k]); }
-    if (c->dp_fork) (void)hipEventDestroy(c->dp_fork);
+    passres_free(c->t0);
     for (auto &e : c->ev_pack) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -2628,30 +1720,6 @@ static Ctx make_ctx(const mcx_ctx *c, int tier, int paired)
 struct StageMs { float seed, sa, cluster, rescue, build, dp, finish; };
 
 constexpr int kListOverflow = 1; // (internal) a work list of run_pairs was too short for the selection
-
-// tier 0's set: the context's own members
-static PassRes res_tier0(mcx_ctx *c)
-{
-    PassRes r;
-    r.stream = c->stream; r.d_cnt = c->d_cnt; r.h_cnt = c->h_cnt; r.d_tasks = c->d_tasks; r.task_cap = c->task_cap;
-    for (int k = 0; k < kDpClasses; k++) { r.d_jobs[k] = c->d_jobs[k]; r.job_cap[k] = c->job_cap[k]; }
-    r.d_rescue = c->d_rescue; r.rescue_cap = c->rescue_cap; r.d_kscratch = c->d_kscratch;
-    r.d_rtasks = c->d_rtasks; r.d_rres = c->d_rres; r.d_rseeds = c->d_rseeds; r.d_rplans = c->d_rplans; r.d_rescue_n = c->d_rescue_n; r.rtask_cap = c->rtask_cap; r.rseed_cap = c->rseed_cap;
-    for (int k = 0; k < 3; k++) { r.d_dp_scratch[k] = c->d_dp_scratch[k]; r.dp_stride[k] = c->dp_stride[k]; r.dp_blocks[k] = c->dp_blocks[k]; }
-    r.d_dp_lane = c->d_dp_lane; r.dp_lane_blocks = c->dp_lane_blocks; r.d_dp_order[0] = c->d_dp_order[0]; r.d_dp_order[1] = c->d_dp_order[1];
-    for (int k = 0; k < 5; k++) { r.dp_stream[k] = c->dp_stream[k]; r.dp_join[k] = c->dp_join[k]; }
-    r.dp_fork = c->dp_fork; r.d_ov = c->d_ov; r.ov_cap = c->ov_cap; r.d_sel_ids = c->d_sel_ids; r.d_est = c->d_est;
-    for (int k = 0; k < 12; k++) r.ev[k] = c->ev[k];
-    return r;
-}
-
-// the DP job lists of a pass, one kernel per size class: they work on disjoint lists and are each bound by latency at
-// modest occupancy, so side streams let them share the chip instead of queueing behind one another
-// A long list is worth a lane per problem; a short one (the large tier's, a replay's, the late pairs': a few thousand problems of
-// 100 x 100 cells) is done sooner with a wavefront per problem — fewer problems than the chip has lanes, each 60 times quicker
-// that way.  The list's length is known on the device only, so both kernels are launched and the one whose turn it is not leaves at
-// once: k_dp_group below kDpLaneMin problems, k_dp_lane from there on.
-constexpr uint32_t kDpLaneMin[2] = {65536, 131072}; // targets of 17-64 bases (mean 45 x 45 cells), of 65-256 (95 x 95): two wavefronts per SIMD's worth of problems
 
 // The large tier's records grow when a batch sends it more pairs than one pass holds.  Its passes follow one another, each as long as its slowest pair,
 // and only the first runs beside tier 0: BASELINE config 5 (185 k heavy pairs of 4 M, 260 KB of records each) took two passes of 99 k and 86 k with the
@@ -2699,97 +1767,32 @@ static int dp_scratch_grow(mcx_ctx *c, uint32_t list_len)
 {
     if (c->dp_grown || getenv("MCX_DP_BLOCKS1") || c->kn.no_tier1_grow) return 0;
     const bool nw = c->pm.use_nw != 0;
-    const uint64_t w2 = lane_stride_words<16>(nw, c->rlen_max, 16, true) * 4; // bytes a wavefront's stretch takes
-    const uint64_t have = c->dp_stride[1] * c->dp_blocks[1];
+    const uint64_t w2 = lane_stride_words(nw, c->rlen_max, 16) * 4; // bytes a wavefront's stretch takes
+    const uint64_t have = c->t0.dp_stride[1] * c->t0.dp_blocks[1];
     uint64_t enough = 2 * 128 * (have / w2); // (fewer than two groups per wavefront there is room for: short enough)
     if (const char *e = getenv("MCX_DP_GROW_MIN")) enough = (uint64_t)std::max(0, atoi(e)); // (tests)
     if ((uint64_t)list_len <= enough) return 0;
     c->dp_grown = true; // (one attempt)
     const uint64_t want_bytes = std::min<uint64_t>(4096 * w2, (uint64_t)12 << 30);
-    const uint32_t want = (uint32_t)((want_bytes + c->dp_stride[1] - 1) / c->dp_stride[1]);
-    if (want <= c->dp_blocks[1]) return 0;
+    const uint32_t want = (uint32_t)((want_bytes + c->t0.dp_stride[1] - 1) / c->t0.dp_stride[1]);
+    if (want <= c->t0.dp_blocks[1]) return 0;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
     if (const char *e = getenv("MCX_HBM_CAP_GB")) { const uint64_t cap = (uint64_t)std::max(1, atoi(e)) << 30, used = total_b - free_b; free_b = cap > used ? cap - used : 0; }
-    if (free_b + have < (uint64_t)want * c->dp_stride[1] + kGrowKeep) return 0;
+    if (free_b + have < (uint64_t)want * c->t0.dp_stride[1] + kGrowKeep) return 0;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(c->d_dp_scratch[1])); c->d_dp_scratch[1] = nullptr;
+    HIP_TRY(hipFree(c->t0.d_dp_scratch[1])); c->t0.d_dp_scratch[1] = nullptr;
     uint8_t *p = nullptr;
     uint32_t got = want;
-    if (hipMalloc((void **)&p, (size_t)want * c->dp_stride[1]) != hipSuccess) {
+    if (hipMalloc((void **)&p, (size_t)want * c->t0.dp_stride[1]) != hipSuccess) {
         (void)hipGetLastError();
-        got = c->dp_blocks[1];
+        got = c->t0.dp_blocks[1];
         if (hipMalloc((void **)&p, (size_t)have) != hipSuccess) { (void)hipGetLastError(); return fail(MCX_ERR_DEVICE, "the DP lists' scratch: out of device memory"); }
     }
-    if (got != c->dp_blocks[1] && (c->kn.timing || getenv("MCX_ALLOC_LOG")))
-        fprintf(stderr, "[mcx] the 65-256-column DP list's scratch grows from %.1f to %.1f GB: %u problems in this batch\n", (double)have / 1e9, (double)got * c->dp_stride[1] / 1e9, list_len);
-    g_dmalloc_bytes += (size_t)got * c->dp_stride[1] - have;
-    c->d_dp_scratch[1] = p; c->dp_blocks[1] = got;
-    return 0;
-}
-
-static int launch_dp(const Knobs &kn, const PassRes &R, const Ctx &cx, const JobSinks &sinks, const ReadBatch &rb, const PairSel &sel, int rlen_max)
-{
-    hipStream_t s = R.stream;
-    // three chains of about the same length (the runtime folds streams onto a few hardware queues anyway: more streams only
-    // make the pairing of kernels on a queue a matter of luck); a set of pass resources without side streams runs them in turn
-    const int n_side = R.dp_stream[1] ? 2 : 0;
-    hipStream_t side0 = n_side ? R.dp_stream[0] : s, side1 = n_side ? R.dp_stream[1] : s;
-    HIP_TRY(hipEventRecord(R.dp_fork, s));
-    for (int k = 0; k < n_side; k++) HIP_TRY(hipStreamWaitEvent(R.dp_stream[k], R.dp_fork, 0));
-    const bool by_wave = kn.dp_by_wave; // (experiments, and the A/B of the parity tests: the wavefront-per-problem kernels of mcx_dp.h)
-    if (!by_wave) {
-        // every list but the largest problems': one problem per lane (mcx_dp_lane.h).  A list's stretch of scratch per wavefront is
-        // sized for its largest possible group; the two long lists share the wavefront kernels' buffers
-        const bool nw = cx.pm.use_nw != 0;
-        uint32_t *unsup = sinks.unsupported;
-        const bool always = kn.dp_lane_always;
-        uint32_t lane_min[2] = {always ? 0u : kDpLaneMin[0], always ? 0u : kDpLaneMin[1]};
-        // two problems per lane in 16-bit halves (k_dp_lane2) wherever the scores fit them with room to spare: queries + targets far below kNeg2's reach, and a cell's
-        // s~ (never below -2 (i + j) - 2: mismatches down the diagonal and one gap) within the fourteen bits a strip's edge word keeps of it
-        const bool x2 = !kn.dp_x1 && rlen_max + 256 <= 3000;
-        const uint64_t w1 = lane_stride_words<16>(nw, rlen_max, 4, x2), w2 = lane_stride_words<16>(nw, rlen_max, 16, x2);
-        const unsigned b1 = (unsigned)std::min<uint64_t>(4096, R.dp_stride[0] * R.dp_blocks[0] / (w1 * 4)), b2 = (unsigned)std::min<uint64_t>(4096, R.dp_stride[1] * R.dp_blocks[1] / (w2 * 4));
-        // (a set of pass resources whose scratch does not hold one lane group for reads this long — the small sets with a large max_read_len —
-        //  leaves that list to the wavefront kernel whatever its length)
-        if (b1 == 0) lane_min[0] = 0xFFFFFFFFu;
-        if (b2 == 0) lane_min[1] = 0xFFFFFFFFu;
-        const bool by_shape = true;
-        const uint32_t *ord[2] = {nullptr, nullptr};
-        hipStream_t st[2] = {s, side1};
-        if (by_shape) {
-            const int row_shift = rlen_max <= 256 ? 2 : (rlen_max <= 512 ? 3 : (rlen_max <= 1024 ? 4 : 6)); // (64 row classes cover the longest query)
-            for (int k = 0; k < 2; k++) {
-                if (lane_min[k] == 0xFFFFFFFFu) continue;
-                uint32_t *counts = R.d_cnt + CNT_DP_SORT + 2 * kDpBuckets * k, *cursor = counts + kDpBuckets; // (cleared with the pass's counters)
-                k_dp_sort_count<<<1024, 256, 0, st[k]>>>(sinks.s[1 + k], row_shift, counts, lane_min[k]);
-                k_dp_sort_scan<<<1, 256, 0, st[k]>>>(counts, cursor);
-                k_dp_sort_place<<<1024, 256, 0, st[k]>>>(sinks.s[1 + k], row_shift, cursor, R.d_dp_order[k], lane_min[k]);
-                ord[k] = R.d_dp_order[k];
-            }
-        }
-        if (b1) launch_dp_lane<16>(nw, x2, b1, st[0], cx, sinks.s[1], ord[0], rb, sel, (uint32_t *)R.d_dp_scratch[0], w1, unsup, lane_min[0]);
-        k_dp_group<1><<<R.dp_blocks[0], 64, 0, st[0]>>>(cx, sinks.s[1], rb, sel, R.d_dp_scratch[0], R.dp_stride[0], lane_min[0]);
-        if (b2) launch_dp_lane<16>(nw, x2, b2, st[1], cx, sinks.s[2], ord[1], rb, sel, (uint32_t *)R.d_dp_scratch[1], w2, unsup, lane_min[1]);
-        k_dp_group<4><<<R.dp_blocks[1], 64, 0, st[1]>>>(cx, sinks.s[2], rb, sel, R.d_dp_scratch[1], R.dp_stride[1], lane_min[1]);
-        uint32_t *p = R.d_dp_lane;
-        launch_dp_lane<8>(nw, x2, R.dp_lane_blocks, side0, cx, sinks.s[4], nullptr, rb, sel, p, lane_short_words(0), unsup, 0u);
-        p += lane_short_words(0) * R.dp_lane_blocks;
-        launch_dp_lane<16>(nw, x2, R.dp_lane_blocks, side0, cx, sinks.s[0], nullptr, rb, sel, p, lane_short_words(1), unsup, 0u);
-        p += lane_short_words(1) * R.dp_lane_blocks;
-        launch_dp_lane<16>(nw, x2, R.dp_lane_blocks, side0, cx, sinks.s[5], nullptr, rb, sel, p, lane_short_words(2), unsup, 0u);
-        k_dp_sel<16><<<R.dp_blocks[2], 64, 0, side1>>>(cx, sinks.s[3], rb, sel, R.d_dp_scratch[2], R.dp_stride[2]);
-    } else {
-    k_dp_group<1><<<R.dp_blocks[0], 64, 0, s>>>(cx, sinks.s[1], rb, sel, R.d_dp_scratch[0], R.dp_stride[0], 0xFFFFFFFFu);
-    k_dp_small<<<2560, 256, 0, side0>>>(cx, sinks.s[0], rb, sel);
-    k_dp_group<4><<<R.dp_blocks[1], 64, 0, side1>>>(cx, sinks.s[2], rb, sel, R.d_dp_scratch[1], R.dp_stride[1], 0xFFFFFFFFu);
-    // (the half-wave class behind the 65-256-column class looks like the long pole on a timeline; moved behind the shorter chains
-    //  the stage takes the same 3.3-3.4 ms: the kernels share the chip, the stage is the sum of their work)
-    k_dp_tiny<<<2048, 256, 0, s>>>(cx, sinks.s[4], rb, sel);
-    k_dp_half<<<2048, 256, 0, side1>>>(cx, sinks.s[5], rb, sel);
-    k_dp_sel<16><<<R.dp_blocks[2], 64, 0, side0>>>(cx, sinks.s[3], rb, sel, R.d_dp_scratch[2], R.dp_stride[2]);
-    }
-    for (int k = 0; k < n_side; k++) { HIP_TRY(hipEventRecord(R.dp_join[k], R.dp_stream[k])); HIP_TRY(hipStreamWaitEvent(s, R.dp_join[k], 0)); }
+    if (got != c->t0.dp_blocks[1] && (c->kn.timing || getenv("MCX_ALLOC_LOG")))
+        fprintf(stderr, "[mcx] the 65-256-column DP list's scratch grows from %.1f to %.1f GB: %u problems in this batch\n", (double)have / 1e9, (double)got * c->t0.dp_stride[1] / 1e9, list_len);
+    g_dmalloc_bytes += (size_t)got * c->t0.dp_stride[1] - have;
+    c->t0.d_dp_scratch[1] = p; c->t0.dp_blocks[1] = got;
     return 0;
 }
 
@@ -3241,7 +2244,7 @@ static int queue_batch_tail(mcx_ctx *c)
 {
     BatchRun &br = c->run;
     mcx_ctx::Tail &t = c->tail;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     const uint32_t nc = br.n_chunks, n_reads = br.rb.n_reads;
     if (int rc = tail_reserve(c)) return rc;
     if (c->overlap_tiers) { // the passes of the large tier beside this one write records and outcomes of their own pairs
@@ -3259,7 +2262,7 @@ static int queue_batch_tail(mcx_ctx *c)
     k_chunk_sums<<<(nc + 255) / 256, 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, d_ok, d_ds, d_ls, t.d + 1);
     if (br.paired) {
         k_avg_walk<<<1, 1024, 0, s>>>(d_ok, d_ds, nc, (long long)t.state0[0], (long long)t.state0[1], (long long)t.state0[2], 1, d_est);
-        k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->d_sel_ids, c->d_est, t.d, c->ov_cap);
+        k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->t0.d_sel_ids, c->t0.d_est, t.d, c->t0.ov_cap);
     }
     HIP_TRY(hipGetLastError());
     uint32_t *h = t.h;
@@ -3272,14 +2275,6 @@ static int queue_batch_tail(mcx_ctx *c)
     br.d_ok = d_ok; br.d_ds = d_ds;
     return 0;
 }
-
-static int profile_keys(mcx_ctx *c);
-static int profile_queue(mcx_ctx *c);
-static int profile_collect(mcx_ctx *c);
-static int archive_append(mcx_ctx *c, mcx_ctx::Archive &a, const SparseRec *d_src, uint64_t n, hipStream_t on = nullptr);
-static int profile_foreign(mcx_ctx *c, const uint64_t *h_all, uint64_t n_all);
-static int sort_reserve(mcx_ctx *c, uint64_t n);
-static int profile_accumulate(mcx_ctx *c, const uint64_t *h_all, uint64_t n_all, uint32_t slot_stride, uint32_t own_slot);
 
 extern "C" void mcx_avg_init(int64_t a[4]) { a[0] = 1000; a[1] = 0; a[2] = 0; a[3] = 0; }
 
@@ -3307,25 +2302,25 @@ static int run_selection(mcx_ctx *c, const ReadBatch &rb, int paired, const std:
                          const std::vector<int32_t> *est, int32_t est_all, uint32_t n_pairs, AlnRec *d_recs,
                          uint32_t *d_cig, mcx_stats *stats, bool timing)
 {
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     const uint32_t n = ids ? (uint32_t)ids->size() : n_pairs;
     if (n == 0) return 0;
-    PairSel sel; sel.n = n; sel.ids = nullptr; sel.est = c->d_est;
+    PairSel sel; sel.n = n; sel.ids = nullptr; sel.est = c->t0.d_est;
     if (ids) {
-        HIP_TRY(hipMemcpyAsync(c->d_sel_ids, ids->data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        sel.ids = c->d_sel_ids;
+        HIP_TRY(hipMemcpyAsync(c->t0.d_sel_ids, ids->data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        sel.ids = c->t0.d_sel_ids;
     }
-    if (est) HIP_TRY(hipMemcpyAsync(c->d_est, est->data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    else k_fill_i32<<<(n + 255) / 256, 256, 0, s>>>(c->d_est, est_all, n);
+    if (est) HIP_TRY(hipMemcpyAsync(c->t0.d_est, est->data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    else k_fill_i32<<<(n + 255) / 256, 256, 0, s>>>(c->t0.d_est, est_all, n);
     if (c->mx.on) { // (-m) the selection's reads have no extra lines until k_finish<true> says otherwise: a pair that k_simple finishes this time keeps none from an earlier pass
         const int nr = paired ? 2 : 1;
-        if (ids) k_mx_clear<<<(n + 255) / 256, 256, 0, s>>>(c->d_sel_ids, n, nr, c->mx.d_ref);
+        if (ids) k_mx_clear<<<(n + 255) / 256, 256, 0, s>>>(c->t0.d_sel_ids, n, nr, c->mx.d_ref);
         else HIP_TRY(hipMemsetAsync(c->mx.d_ref, 0, (size_t)n * nr * sizeof(uint4), s));
     }
-    const PassRes R0 = res_tier0(c);
+    const PassRes &R0 = c->t0;
     int rc = run_pairs(c, 0, R0, rb, paired, sel, d_recs, d_cig, stats, timing, true);
     // (the batch's tail, if the pass queued it, stands only when the pass is all there was: no halves, no pairs left for the large tier)
-    if (rc != 0 || c->h_cnt[CNT_OV] != 0) c->tail.queued = false;
+    if (rc != 0 || c->t0.h_cnt[CNT_OV] != 0) c->tail.queued = false;
     if (rc == kListOverflow) {
         // unusually many hits or DP problems per read (e.g. indel-heavy long reads): halve the selection
         if (n < 2) return fail(MCX_ERR_CAPACITY, "work list overflow for a single pair");
@@ -3340,20 +2335,20 @@ static int run_selection(mcx_ctx *c, const ReadBatch &rb, int paired, const std:
         return 0;
     }
     if (rc) return rc;
-    uint32_t n_ov = c->h_cnt[CNT_OV];
+    uint32_t n_ov = c->t0.h_cnt[CNT_OV];
     if (n_ov == 0) return 0;
-    if (n_ov > c->ov_cap) return fail(MCX_ERR_CAPACITY, "overflow list overflow");
+    if (n_ov > c->t0.ov_cap) return fail(MCX_ERR_CAPACITY, "overflow list overflow");
     // tier 1: the overflowed pairs again, with capacities that are hard bounds for the read length
     std::vector<uint32_t> ov(n_ov);
-    HIP_TRY(hipMemcpy(ov.data(), c->d_ov, n_ov * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ov.data(), c->t0.d_ov, n_ov * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::sort(ov.begin(), ov.end());
     std::vector<int32_t> ov_est(n_ov);
     // their estimates (and flags): gathered on the device — the whole PairOut array is 128 MB at 4 M pairs
     std::vector<PairOut> ov_out(n_ov);
     for (uint32_t lo = 0; lo < n_ov; lo += kPoutSel) {
         const uint32_t m = std::min<uint32_t>(kPoutSel, n_ov - lo);
-        HIP_TRY(hipMemcpyAsync(c->d_sel_ids, ov.data() + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        k_gather_pout<<<(m + 255) / 256, 256, 0, s>>>(c->d_pout, c->d_sel_ids, m, c->d_pout_sel);
+        HIP_TRY(hipMemcpyAsync(c->t0.d_sel_ids, ov.data() + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        k_gather_pout<<<(m + 255) / 256, 256, 0, s>>>(c->d_pout, c->t0.d_sel_ids, m, c->d_pout_sel);
         HIP_TRY(hipMemcpyAsync(ov_out.data() + lo, c->d_pout_sel, m * sizeof(PairOut), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
@@ -3369,9 +2364,9 @@ static int run_selection(mcx_ctx *c, const ReadBatch &rb, int paired, const std:
     //  left ran over later: column strings, job lists)
     for (uint32_t lo = 0; lo < n_ov; lo += c->tier[1].max_pairs) {
         uint32_t m = std::min<uint32_t>(c->tier[1].max_pairs, n_ov - lo);
-        HIP_TRY(hipMemcpyAsync(c->d_sel_ids, ov.data() + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->d_est, ov_est.data() + lo, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        PairSel s1; s1.n = m; s1.ids = c->d_sel_ids; s1.est = c->d_est;
+        HIP_TRY(hipMemcpyAsync(c->t0.d_sel_ids, ov.data() + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->t0.d_est, ov_est.data() + lo, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        PairSel s1; s1.n = m; s1.ids = c->t0.d_sel_ids; s1.est = c->t0.d_est;
         if (c->kn.timing) { // where the time of the large-capacity tier goes (not added to the caller's stage times)
             mcx_stats t1; memset(&t1, 0, sizeof t1);
             rc = run_pairs(c, 1, R0, rb, paired, s1, d_recs, d_cig, &t1, true);
@@ -3382,7 +2377,7 @@ static int run_selection(mcx_ctx *c, const ReadBatch &rb, int paired, const std:
         rc = run_pairs(c, 1, R0, rb, paired, s1, d_recs, d_cig, stats, false);
         if (rc == kListOverflow) return fail(MCX_ERR_CAPACITY, "work list overflow in tier 1");
         if (rc) return rc;
-        if (c->h_cnt[CNT_OV]) return tier1_error(c, R0);
+        if (c->t0.h_cnt[CNT_OV]) return tier1_error(c, R0);
     }
     return 0;
 }
@@ -3396,11 +2391,6 @@ __global__ void k_max_read_len(const uint32_t *off, uint32_t n_reads, uint32_t *
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
-__global__ void k_zero_but(uint32_t *cnt, int n, int keep_a, int keep_b)
-{
-    for (int k = threadIdx.x; k < n; k += blockDim.x) if (k != keep_a && k != keep_b) cnt[k] = 0;
-}
-
 // a batch's reads into the context's own copy (bases 16 bytes at a time: d_bases is 16-byte aligned, the copy's room ends on a multiple of 16)
 __global__ void k_keep_reads(const uint8_t *__restrict__ bases, const uint32_t *__restrict__ off, uint32_t n_reads, uint8_t *__restrict__ to_bases, uint32_t *__restrict__ to_off)
 {
@@ -3410,7 +2400,7 @@ __global__ void k_keep_reads(const uint8_t *__restrict__ bases, const uint32_t *
 }
 
 // tier 0's pair records: one per pair of the largest batch of this kind (allocated by the first batch that needs them, or ahead of it by mcx_ctx_create_fit)
-static int reserve_tier0(mcx_ctx *c, int paired, uint64_t n_reads)
+int reserve_tier0(mcx_ctx *c, int paired, uint64_t n_reads)
 {
     const uint64_t half = (c->max_reads + 1) / 2;
     const uint64_t want = (paired || n_reads <= half) ? half : c->max_reads; // (the single-end tail of an interleaved file fits the pairs' records)
@@ -3445,7 +2435,7 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     if (c->prof_planes && c->prof_settled) return fail(MCX_ERR_ARG, "the profile has been settled (mcx_profile_settle / _finalize): attach it again before mapping more reads");
     HIP_TRY(hipSetDevice(c->idx->device));
     br.t0 = std::chrono::steady_clock::now();
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     if (int rc = reserve_tier0(c, paired, n_reads)) return rc;
     br.rb.bases = d_bases; br.rb.off = d_off; br.rb.n_reads = n_reads;
     br.paired = paired; br.read_base = read_base;
@@ -3459,19 +2449,18 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     c->mx.ready = false;
     if (c->mx.on) HIP_TRY(hipMemsetAsync(c->mx.d_cnt, 0, 4 * sizeof(uint32_t), s)); // (-m: the extras pool starts empty with every batch)
     c->last_paired = paired ? 1 : 0;
-    if (vouched) c->h_cnt[1] = (uint32_t)c->rlen_max; // (vouched for: no kernel, no wait at the start of the step — under the copies of the neighbouring batches such a wait takes milliseconds)
+    if (vouched) c->t0.h_cnt[1] = (uint32_t)c->rlen_max; // (vouched for: no kernel, no wait at the start of the step — under the copies of the neighbouring batches such a wait takes milliseconds)
     else { // every read must fit the slots the context was sized for
         k_max_read_len<<<512, 256, 0, s>>>(d_off, n_reads, c->d_batch_flags + 1);
-        HIP_TRY(hipMemcpyAsync(c->h_cnt, c->d_batch_flags, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->t0.h_cnt, c->d_batch_flags, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (c->h_cnt[1] > (uint32_t)c->rlen_max)
-            return fail(MCX_ERR_UNSUPPORTED, "a read of " + std::to_string(c->h_cnt[1]) + " bases is longer than max_read_len (" + std::to_string(c->rlen_max) + ")");
+        if (c->t0.h_cnt[1] > (uint32_t)c->rlen_max)
+            return fail(MCX_ERR_UNSUPPORTED, "a read of " + std::to_string(c->t0.h_cnt[1]) + " bases is longer than max_read_len (" + std::to_string(c->rlen_max) + ")");
     }
     { // the batch in 2-bit form, once; every seeding pass (tiers, replay) reads it
         HIP_TRY(hipEventRecord(c->ev_pack[0], s));
-        const int tpr = ((int)c->h_cnt[1] + 31) / 32 + 1; // (threads per read: for the batch's longest read, found above)
-        br.longest = c->h_cnt[1];
-        const uint64_t threads = (uint64_t)n_reads * (uint64_t)tpr;
+        const int tpr = ((int)c->t0.h_cnt[1] + 31) / 32 + 1; // (threads per read: for the batch's longest read, found above)
+        br.longest = c->t0.h_cnt[1];
         // (the reads' flag bytes of the -vcf bookkeeping start here: bit 1 — a byte that is not an upper-case ACGT — is k_pack_reads'; MCX_PROF_BY_COLUMN:
         //  tests — every read is treated as if it held one, so that exact seeds are walked column by column like every other fragment)
         if (c->prof_planes) HIP_TRY(hipMemsetAsync(c->d_admit, c->kn.prof_by_column ? 2 : 0, ((size_t)n_reads + 3) & ~(size_t)3, s));
@@ -3481,7 +2470,7 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
             HIP_TRY(hipMemcpyAsync(c->d_batch_flags + 3, pre.any_n, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         } else {
             c->packed_now = c->d_packed;
-            k_pack_reads<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(br.rb, paired, c->wpad, tpr, c->d_packed, c->d_batch_flags + 3, c->prof_planes ? c->d_admit : nullptr);
+            pack_reads(br.rb, paired, c->wpad, tpr, c->d_packed, c->d_batch_flags + 3, c->prof_planes ? c->d_admit : nullptr, s);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev_pack[1], s));
@@ -3501,12 +2490,12 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     rc = run_selection(c, br.rb, paired, nullptr, nullptr, est0, br.n_pairs, br.recs, d_cigar, stats, true);
     br.t_begun = std::chrono::steady_clock::now();
     if (rc) return rc;
-    if (c->tail.queued) memcpy(c->h_cnt + CNT_N, c->tail.h + 2, sizeof br.hs); // (the pass queued the batch's tail and it stands: the statistics came with it)
+    if (c->tail.queued) memcpy(c->t0.h_cnt + CNT_N, c->tail.h + 2, sizeof br.hs); // (the pass queued the batch's tail and it stands: the statistics came with it)
     else { // seeding statistics (E, blocks, H of SURVEY.md 8d) before the per-read arrays are reused for the chunk sums
-        unsigned long long *d_sum = (unsigned long long *)c->d_cnt;
-        HIP_TRY(hipMemsetAsync(c->d_cnt, 0, CNT_N * sizeof(uint32_t), s));
+        unsigned long long *d_sum = (unsigned long long *)c->t0.d_cnt;
+        HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
         k_reduce_stats<<<256, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
-        HIP_TRY(hipMemcpyAsync(c->h_cnt + CNT_N, d_sum, sizeof br.hs, hipMemcpyDeviceToHost, s)); // (read by batch_close, behind the sums' synchronisation: no round trip of its own)
+        HIP_TRY(hipMemcpyAsync(c->t0.h_cnt + CNT_N, d_sum, sizeof br.hs, hipMemcpyDeviceToHost, s)); // (read by batch_close, behind the sums' synchronisation: no round trip of its own)
     }
     br.open = true;
     return 0;
@@ -3520,7 +2509,7 @@ extern "C" int mcx_batch_sums(mcx_ctx *c, uint32_t *n_chunks, const uint32_t **p
 {
     if (!c || !c->run.open) return fail(MCX_ERR_ARG, "mcx_batch_sums: no batch in flight");
     BatchRun &br = c->run;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     HIP_TRY(hipSetDevice(c->idx->device));
     const uint32_t nc = br.n_chunks;
     if (br.sums_valid && br.ok.size() == nc && !c->kn.no_sums_cache) { // nothing was re-run since the last call (the closing round of a sharded step): the sums still stand
@@ -3533,13 +2522,13 @@ extern "C" int mcx_batch_sums(mcx_ctx *c, uint32_t *n_chunks, const uint32_t **p
     uint32_t *d_ok = c->d_read_ext, *d_ds = c->d_read_blocks; // the per-read stat arrays were reduced by mcx_batch_begin
     uint32_t *d_ls = d_ds + nc;                               // (2 * n_chunks <= n_reads)
     br.ok.resize(nc); br.ds.resize(2 * (size_t)nc);
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-    k_chunk_sums<<<(nc + 255) / 256, 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, d_ok, d_ds, d_ls, c->d_cnt + CNT_LF);
+    HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
+    k_chunk_sums<<<(nc + 255) / 256, 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, d_ok, d_ds, d_ls, c->t0.d_cnt + CNT_LF);
     HIP_TRY(hipMemcpyAsync(br.ok.data(), d_ok, nc * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(br.ds.data(), d_ds, 2 * (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(c->h_cnt, c->d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c->t0.h_cnt, c->t0.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    br.mapped = c->h_cnt[CNT_LF];
+    br.mapped = c->t0.h_cnt[CNT_LF];
     br.sums_valid = true; br.d_ok = d_ok; br.d_ds = d_ds;
     if (n_chunks) *n_chunks = nc;
     if (pairs) *pairs = br.ok.data();
@@ -3553,17 +2542,17 @@ extern "C" int mcx_batch_replay(mcx_ctx *c, const int32_t *est_chunk, uint32_t *
 {
     if (!c || !c->run.open || !est_chunk) return fail(MCX_ERR_ARG, "mcx_batch_replay: no batch in flight");
     BatchRun &br = c->run;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     HIP_TRY(hipSetDevice(c->idx->device));
     if (n_redone) *n_redone = 0;
     if (!br.paired) return 0;
     int32_t *d_est_chunk = (int32_t *)c->d_read_ext; // the sums are on the host
     HIP_TRY(hipMemcpyAsync(d_est_chunk, est_chunk, br.n_chunks * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-    k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est_chunk, c->d_sel_ids, c->d_est, c->d_cnt + CNT_OV, c->ov_cap);
-    HIP_TRY(hipMemcpyAsync(c->h_cnt, c->d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
+    k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est_chunk, c->t0.d_sel_ids, c->t0.d_est, c->t0.d_cnt + CNT_OV, c->t0.ov_cap);
+    HIP_TRY(hipMemcpyAsync(c->t0.h_cnt, c->t0.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t n_redo = c->h_cnt[CNT_OV];
+    const uint32_t n_redo = c->t0.h_cnt[CNT_OV];
     if (n_redo == 0) return 0;
     if (int rc = replay_listed(c, n_redo, stats)) return rc;
     if (n_redone) *n_redone = n_redo;
@@ -3576,11 +2565,11 @@ static int replay_listed(mcx_ctx *c, uint32_t n_redo, mcx_stats *stats)
     BatchRun &br = c->run;
     br.sums_valid = false;
     c->tail.queued = false; // (what the batch's tail brought is no longer the batch's state)
-    if (n_redo > c->ov_cap) return fail(MCX_ERR_CAPACITY, "avgDist replay: redo list overflow");
+    if (n_redo > c->t0.ov_cap) return fail(MCX_ERR_CAPACITY, "avgDist replay: redo list overflow");
     if (stats) stats->replayed_pairs += (int64_t)n_redo;
     std::vector<uint32_t> redo(n_redo); std::vector<int32_t> redo_est(n_redo);
-    HIP_TRY(hipMemcpy(redo.data(), c->d_sel_ids, n_redo * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(redo_est.data(), c->d_est, n_redo * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(redo.data(), c->t0.d_sel_ids, n_redo * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(redo_est.data(), c->t0.d_est, n_redo * 4, hipMemcpyDeviceToHost));
     // the list was appended with atomics: bring it into pair order (results do not depend on it)
     std::vector<std::pair<uint32_t, int32_t>> ord(n_redo);
     for (uint32_t i = 0; i < n_redo; i++) ord[i] = std::make_pair(redo[i], redo_est[i]);
@@ -3614,11 +2603,11 @@ extern "C" int mcx_batch_check(mcx_ctx *c, const int64_t state_before[3], int fi
     int rc;
     if ((!br.sums_valid || !br.d_ok) && (rc = mcx_batch_sums(c, nullptr, nullptr, nullptr, nullptr))) return rc; // (the chunk sums lie at br.d_ok / br.d_ds behind it)
     if ((rc = tail_reserve(c))) return rc;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     int32_t *d_est = (int32_t *)(c->tail.d + 8);
     HIP_TRY(hipMemsetAsync(c->tail.d, 0, 8 * sizeof(uint32_t), s));
     k_avg_walk<<<1, 1024, 0, s>>>(br.d_ok, br.d_ds, br.n_chunks, (long long)state_before[0], (long long)state_before[1], (long long)state_before[2], first_of_round ? 1 : 0, d_est);
-    k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->d_sel_ids, c->d_est, c->tail.d, c->ov_cap);
+    k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->t0.d_sel_ids, c->t0.d_est, c->tail.d, c->t0.ov_cap);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->tail.h, c->tail.d, 8 * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -3681,9 +2670,9 @@ static int mx_alloc_pool(mcx_ctx *c, uint32_t recs, uint32_t words, bool keep)
     if ((rc = dmalloc(&p, recs))) return rc;
     if ((rc = dmalloc(&w, words))) { (void)hipFree(p); return rc; }
     if (keep && m.d_pool) { // (what the batch's pairs wrote so far stays where their entries point)
-        HIP_TRY(hipMemcpyAsync(p, m.d_pool, (size_t)std::min(m.rec_cap, recs) * sizeof(AlnRec), hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(w, m.d_pool_cig, (size_t)std::min(m.word_cap, words) * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpyAsync(p, m.d_pool, (size_t)std::min(m.rec_cap, recs) * sizeof(AlnRec), hipMemcpyDeviceToDevice, c->t0.stream));
+        HIP_TRY(hipMemcpyAsync(w, m.d_pool_cig, (size_t)std::min(m.word_cap, words) * 4, hipMemcpyDeviceToDevice, c->t0.stream));
+        HIP_TRY(hipStreamSynchronize(c->t0.stream));
     }
     if (m.d_pool) (void)hipFree(m.d_pool);
     if (m.d_pool_cig) (void)hipFree(m.d_pool_cig);
@@ -3722,7 +2711,7 @@ static int multi_close(mcx_ctx *c)
 {
     auto &m = c->mx;
     BatchRun &br = c->run;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->t0.stream;
     const uint32_t n_reads = br.rb.n_reads, nr = br.paired ? 2 : 1;
     int rc;
     for (int round = 0;; round++) {
@@ -3737,7 +2726,7 @@ static int multi_close(mcx_ctx *c)
                                                              m.rec_cap, recs, m.word_cap, words, h[0], h[1]);
         if ((rc = mx_alloc_pool(c, recs, words, true))) return rc;
         HIP_TRY(hipMemsetAsync(m.d_cnt + 2, 0, 4, s));
-        k_mx_over<<<(br.n_pairs + 255) / 256, 256, 0, s>>>(m.d_ref, br.n_pairs, (int)nr, c->d_pout, c->d_sel_ids, c->d_est, m.d_cnt + 2, c->ov_cap);
+        k_mx_over<<<(br.n_pairs + 255) / 256, 256, 0, s>>>(m.d_ref, br.n_pairs, (int)nr, c->d_pout, c->t0.d_sel_ids, c->t0.d_est, m.d_cnt + 2, c->t0.ov_cap);
         HIP_TRY(hipGetLastError());
         uint32_t n_over = 0;
         HIP_TRY(hipMemcpyAsync(&n_over, m.d_cnt + 2, 4, hipMemcpyDeviceToHost, s));
@@ -3792,10 +2781,10 @@ extern "C" int mcx_multi_copy(mcx_ctx *c, uint32_t *index, mcx_aln *recs, uint32
     const auto &m = c->mx;
     if ((m.n_recs && !recs) || (m.n_words && !cigar)) return fail(MCX_ERR_ARG, "mcx_multi_copy: null argument");
     HIP_TRY(hipSetDevice(c->idx->device));
-    HIP_TRY(hipMemcpyAsync(index, m.d_index, ((size_t)m.n_reads + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (m.n_recs) HIP_TRY(hipMemcpyAsync(recs, m.d_out, (size_t)m.n_recs * sizeof(AlnRec), hipMemcpyDeviceToHost, c->stream));
-    if (m.n_words) HIP_TRY(hipMemcpyAsync(cigar, m.d_out_cig, (size_t)m.n_words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(index, m.d_index, ((size_t)m.n_reads + 1) * 4, hipMemcpyDeviceToHost, c->t0.stream));
+    if (m.n_recs) HIP_TRY(hipMemcpyAsync(recs, m.d_out, (size_t)m.n_recs * sizeof(AlnRec), hipMemcpyDeviceToHost, c->t0.stream));
+    if (m.n_words) HIP_TRY(hipMemcpyAsync(cigar, m.d_out_cig, (size_t)m.n_words * 4, hipMemcpyDeviceToHost, c->t0.stream));
+    HIP_TRY(hipStreamSynchronize(c->t0.stream));
     return 0;
 }
 
@@ -3819,7 +2808,7 @@ static int batch_close(mcx_ctx *c, mcx_stats *stats)
         int64_t pairs = 0, dist_sum = 0, len_sum = 0;
         if (br.paired) for (uint32_t k = 0; k < br.n_chunks; k++) { pairs += br.ok[k]; dist_sum += br.ds[k]; len_sum += br.ds[br.n_chunks + k]; }
         stats->reads += br.rb.n_reads; stats->mapped += br.mapped; stats->pairs += pairs; stats->pair_dist_sum += dist_sum; stats->pair_len_sum += len_sum;
-        memcpy(br.hs, c->h_cnt + CNT_N, sizeof br.hs);
+        memcpy(br.hs, c->t0.h_cnt + CNT_N, sizeof br.hs);
         stats->fm_ext_steps += (int64_t)br.hs[0]; stats->fm_blocks += (int64_t)br.hs[1]; stats->sa_hits += (int64_t)br.hs[2];
         float ms_pack = 0;
         if (hipEventElapsedTime(&ms_pack, c->ev_pack[0], c->ev_pack[1]) == hipSuccess) stats->ms_encode += ms_pack; // k_pack_reads
@@ -3961,8 +2950,8 @@ int mcx_stage_in(mcx_ctx *c, const uint8_t *bases, const uint32_t *off, uint32_t
         if ((rc = dmalloc(&c->d_cig, MCX_CIGAR_POOL_WORDS(c->max_reads)))) return rc;
     }
     if (off[n_reads] > c->max_bases) return fail(MCX_ERR_ARG, "batch holds more bases than max_batch_reads * max_read_len");
-    HIP_TRY(hipMemcpyAsync(c->d_bases, bases, off[n_reads], hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_off, off, (size_t)(n_reads + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_bases, bases, off[n_reads], hipMemcpyHostToDevice, c->t0.stream));
+    HIP_TRY(hipMemcpyAsync(c->d_off, off, (size_t)(n_reads + 1) * 4, hipMemcpyHostToDevice, c->t0.stream));
     *d_bases = c->d_bases; *d_off = c->d_off; *d_aln = (mcx_aln *)c->d_recs; *d_cigar = c->d_cig;
     return 0;
 }
@@ -3970,9 +2959,9 @@ int mcx_stage_in(mcx_ctx *c, const uint8_t *bases, const uint32_t *off, uint32_t
 int mcx_stage_out(mcx_ctx *c, uint32_t n_reads, mcx_aln *aln, uint32_t *cigar)
 {
     HIP_TRY(hipSetDevice(c->idx->device));
-    HIP_TRY(hipMemcpyAsync(aln, c->d_recs, (size_t)n_reads * sizeof(AlnRec), hipMemcpyDeviceToHost, c->stream));
-    if (c->run.cig_words) HIP_TRY(hipMemcpyAsync(cigar, c->d_cig, (size_t)c->run.cig_words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(aln, c->d_recs, (size_t)n_reads * sizeof(AlnRec), hipMemcpyDeviceToHost, c->t0.stream));
+    if (c->run.cig_words) HIP_TRY(hipMemcpyAsync(cigar, c->d_cig, (size_t)c->run.cig_words * 4, hipMemcpyDeviceToHost, c->t0.stream));
+    HIP_TRY(hipStreamSynchronize(c->t0.stream));
     return 0;
 }
 
@@ -3986,861 +2975,6 @@ extern "C" int mcx_map_batch(mcx_ctx *c, const uint8_t *bases, const uint32_t *o
     if (rc) return rc;
     if ((rc = mcx_map_batch_dev(c, d_bases, d_off, n_reads, paired, avg, d_aln, d_cig, stats))) return rc;
     return mcx_stage_out(c, n_reads, aln, cigar);
-}
-
-// ---------------------------------------------------------------------------------------------
-// batches from host memory with the copies overlapped with the kernels
-// ---------------------------------------------------------------------------------------------
-// Bulk copies across the device boundary: the DMA engines by default (52 GB/s each way on the test box, and they leave the
-// CUs to the kernels).  MCX_STREAM_KERNEL_COPY=1 moves them with a kernel instead (page-locked host memory is mapped into
-// the device's address space) — measured slower next to the mapping kernels (82 ms instead of 70 ms per 8 M-read batch), kept for
-// boxes whose DMA queues are the bottleneck.
-__global__ void __launch_bounds__(256) k_copy16(const U4 *__restrict__ src, U4 *__restrict__ dst, uint64_t n16)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * blockDim.x) dst[i] = src[i];
-}
-
-static int bulk_copy(mcx_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s)
-{
-    if (bytes == 0) return 0;
-    // (MCX_STREAM_KERNEL_COPY: this library's own copy kernel over the mapped host memory instead of the runtime's copies — round 5 tried it for the way out
-    //  alone, on grids of 16 / 48 / 128 workgroups, next to the mapping kernels: 23.7 / 26.1 / 27.2 ms per step against the runtime's 20.6)
-    static const char *mode = getenv("MCX_STREAM_KERNEL_COPY"); // ("in" / "out": one direction alone)
-    static const int blocks = getenv("MCX_COPY_BLOCKS") ? atoi(getenv("MCX_COPY_BLOCKS")) : 512;
-    const bool use_dma = mode == nullptr || (!strcmp(mode, "in") && kind != hipMemcpyHostToDevice) || (!strcmp(mode, "out") && kind != hipMemcpyDeviceToHost);
-    const size_t n16 = bytes / 16;
-    bool mapped = false; // is the host side page-locked memory the device can address?
-    {
-        hipPointerAttribute_t a;
-        const void *host = kind == hipMemcpyHostToDevice ? src : dst;
-        if (hipPointerGetAttributes(&a, host) == hipSuccess) mapped = a.type == hipMemoryTypeHost;
-        else (void)hipGetLastError();
-    }
-    if (use_dma || !mapped || n16 == 0 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) { HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, s)); return 0; }
-    k_copy16<<<blocks, 256, 0, s>>>((const U4 *)src, (U4 *)dst, (uint64_t)n16);
-    HIP_TRY(hipGetLastError());
-    if (bytes & 15) HIP_TRY(hipMemcpyAsync((uint8_t *)dst + n16 * 16, (const uint8_t *)src + n16 * 16, bytes & 15, kind, s));
-    (void)c;
-    return 0;
-}
-
-static mcx_ctx::Slot *oldest_slot(mcx_ctx *c, int state)
-{
-    mcx_ctx::Slot *best = nullptr;
-    for (auto &sl : c->slot) if (sl.state == state && (!best || sl.seq < best->seq)) best = &sl;
-    return best;
-}
-
-// a free slot, its HBM allocated on first use
-static int stream_slot(mcx_ctx *c, mcx_ctx::Slot **out)
-{
-    mcx_ctx::Slot *sl = oldest_slot(c, 0);
-    if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_submit: three batches are in flight (collect one first)");
-    int rc;
-    if (!c->h2d_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-    }
-    if (!sl->d_bases) {
-        if ((rc = dmalloc(&sl->d_bases, c->max_bases + 16 * c->max_reads + 64))) return rc; // (+16 per read: packed rows end on a word)
-        if ((rc = dmalloc(&sl->d_off, c->max_reads + 1))) return rc;
-        if ((rc = dmalloc(&sl->d_recs, c->max_reads))) return rc;
-        if ((rc = dmalloc(&sl->d_cig, MCX_CIGAR_POOL_WORDS(c->max_reads)))) return rc;
-        HIP_TRY(hipEventCreateWithFlags(&sl->in_ready, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl->mapped, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl->out_done, hipEventDisableTiming));
-    }
-    *out = sl;
-    return 0;
-}
-
-// 2-bit rows -> the ASCII bytes of the batch: one thread per sixteen bases (the letters ACGT; k_apply_odd puts back every other byte)
-// (the lengths are the caller's: one beyond its row or the context's longest read — lim —, or a sum beyond the slot — max_bases —, is flagged in
-//  *err and nothing is written for it; mcx_stream_next refuses the batch.  Round 4 walked the lengths on the host before the copy: a
-//  millisecond per 8 M reads with the GPU idle.)
-__global__ void __launch_bounds__(256) k_unpack_reads(const uint32_t *codes, uint32_t row_words, const uint32_t *off, uint32_t n_reads, uint8_t *bases,
-                                                      uint64_t max_bases, uint32_t lim, uint32_t *err)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t r = (uint32_t)(t / row_words), k = (uint32_t)(t % row_words);
-    if (r >= n_reads) return;
-    const uint32_t o = off[r], rlen = off[r + 1] - o;
-    if (rlen > lim || off[r + 1] < o) { if (k == 0) atomicOr(err, 1u); return; }
-    if ((uint64_t)o + rlen > max_bases) { if (k == 0) atomicOr(err, 2u); return; }
-    if (16 * k >= rlen) return;
-    const uint32_t w = codes[(uint64_t)r * row_words + k];
-    uint32_t q[4]; // sixteen letters, four to a word, the first in the low byte
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t c = (w >> (30 - 2 * (4 * g + i))) & 3u;
-            v |= (uint32_t)((0x54474341u >> (8 * c)) & 0xFFu) << (8 * i); // "ACGT"
-        }
-        q[g] = v;
-    }
-    uint8_t *dst = bases + o + 16 * k;
-    const uint32_t nb = rlen - 16 * k < 16 ? rlen - 16 * k : 16;
-    const uintptr_t a = (uintptr_t)dst;
-    if (nb == 16 && (a & 3) == 0) { uint32_t *d4 = (uint32_t *)dst; d4[0] = q[0]; d4[1] = q[1]; d4[2] = q[2]; d4[3] = q[3]; }
-    else if (nb == 16 && (a & 1) == 0) { uint16_t *d2 = (uint16_t *)dst; for (int i = 0; i < 8; i++) d2[i] = (uint16_t)(q[i >> 1] >> (16 * (i & 1))); }
-    else for (uint32_t i = 0; i < nb; i++) dst[i] = (uint8_t)(q[i >> 2] >> (8 * (i & 3)));
-}
-
-__global__ void k_apply_odd(const uint64_t *odd, uint32_t n_odd, const uint32_t *off, uint32_t n_reads, uint8_t *bases, uint64_t max_bases)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_odd) return;
-    const uint64_t e = odd[i];
-    const uint32_t r = (uint32_t)(e >> 32), pos = (uint32_t)(e >> 8) & 0xFFFFFFu;
-    if (r < n_reads && off[r + 1] >= off[r] && pos < off[r + 1] - off[r] && (uint64_t)off[r] + pos < max_bases) bases[off[r] + pos] = (uint8_t)e;
-}
-
-// a batch whose lengths k_unpack_reads refused maps nothing: every read becomes empty, so that no kernel behind this one meets a length it was not sized
-// for — the host hears of it when it next looks (mcx_stream_map), not before the batch's first kernel: no wait at the start of a step
-__global__ void __launch_bounds__(256) k_neutralize(uint32_t *off, uint32_t n_reads, const uint32_t *err)
-{
-    if (*err == 0) return;
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += gridDim.x * blockDim.x) off[r] = 0;
-}
-
-extern "C" int mcx_stream_submit_packed(mcx_ctx *c, const uint32_t *codes, uint32_t row_words, const uint32_t *len, uint32_t n_reads, const uint64_t *odd,
-                                        uint32_t n_odd)
-{
-    if (!c || !codes || !len || n_reads == 0 || row_words == 0 || (n_odd && !odd)) return fail(MCX_ERR_ARG, "mcx_stream_submit_packed: bad argument");
-    if (n_reads > c->max_reads) return fail(MCX_ERR_ARG, "batch larger than max_batch_reads");
-    const uint32_t row_max = (uint32_t)(c->rlen_max + 15) / 16;
-    if (row_words > row_max) return fail(MCX_ERR_UNSUPPORTED, "mcx_stream_submit_packed: rows are longer than max_read_len");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    mcx_ctx::Slot *sl = nullptr;
-    int rc = stream_slot(c, &sl);
-    if (rc) return rc;
-    hipStream_t s = c->h2d_stream;
-    if (!sl->d_codes) {
-        if ((rc = dmalloc(&sl->d_codes, c->max_reads * (uint64_t)row_max))) return rc;
-        if ((rc = dmalloc(&sl->d_len, c->max_reads + 1))) return rc;
-        if ((rc = dmalloc(&sl->d_err, 1))) return rc;
-        HIP_TRY(hipHostMalloc((void **)&sl->h_err, sizeof(uint32_t)));
-        *sl->h_err = 0;
-    }
-    if (n_odd > sl->odd_cap) {
-        if (sl->d_odd) { HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(sl->d_odd); sl->d_odd = nullptr; }
-        sl->odd_cap = std::max<uint32_t>(n_odd + n_odd / 2, 1u << 16);
-        if ((rc = dmalloc(&sl->d_odd, sl->odd_cap))) return rc;
-    }
-    if (!c->d_scan_tmp) {
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, sl->d_len, sl->d_off + 1, (int)c->max_reads, s));
-        c->scan_tmp_bytes = need + 256;
-        HIP_TRY(hipMalloc(&c->d_scan_tmp, c->scan_tmp_bytes));
-    }
-    if ((rc = bulk_copy(c, sl->d_codes, codes, (size_t)n_reads * row_words * 4, hipMemcpyHostToDevice, s))) return rc;
-    if ((rc = bulk_copy(c, sl->d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s))) return rc;
-    if (n_odd && (rc = bulk_copy(c, sl->d_odd, odd, (size_t)n_odd * 8, hipMemcpyHostToDevice, s))) return rc;
-    HIP_TRY(hipMemsetAsync(sl->d_off, 0, 4, s));
-    size_t tmp = c->scan_tmp_bytes;
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->d_scan_tmp, tmp, sl->d_len, sl->d_off + 1, (int)n_reads, s));
-    const uint64_t threads = (uint64_t)n_reads * row_words;
-    HIP_TRY(hipMemsetAsync(sl->d_err, 0, 4, s));
-    k_unpack_reads<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(sl->d_codes, row_words, sl->d_off, n_reads, sl->d_bases, c->max_bases,
-                                                                   std::min<uint32_t>(row_words * 16u, (uint32_t)c->rlen_max), sl->d_err);
-    if (n_odd) k_apply_odd<<<(n_odd + 255) / 256, 256, 0, s>>>(sl->d_odd, n_odd, sl->d_off, n_reads, sl->d_bases, c->max_bases);
-    k_neutralize<<<256, 256, 0, s>>>(sl->d_off, n_reads, sl->d_err);
-    HIP_TRY(hipGetLastError());
-    sl->lens_checked = true;
-    // the batch's 2-bit form for the kernels, made here — behind its copy in, under the batch before it — instead of at the start of its own step (0.76 ms of
-    // the step per 8 M reads).  Mated or not is a guess (what the last batch was); a wrong one, or a profile attached meanwhile, and the step packs as before.
-    sl->prepacked = false;
-    if (!c->prof_planes && !c->kn.no_prepack) {
-        if (!sl->d_prepack) {
-            if ((rc = dmalloc(&sl->d_prepack, c->max_reads * (uint64_t)c->wpad))) return rc;
-            if ((rc = dmalloc(&sl->d_any_n, 1))) return rc;
-        }
-        ReadBatch rb; rb.bases = sl->d_bases; rb.off = sl->d_off; rb.n_reads = n_reads;
-        const int tpr = (c->rlen_max + 31) / 32 + 1;
-        HIP_TRY(hipMemsetAsync(sl->d_any_n, 0, 4, s));
-        k_pack_reads<<<(unsigned)(((uint64_t)n_reads * (uint64_t)tpr + 255) / 256), 256, 0, s>>>(rb, c->last_paired, c->wpad, tpr, sl->d_prepack, sl->d_any_n, nullptr);
-        HIP_TRY(hipGetLastError());
-        sl->prepacked = true; sl->pre_paired = c->last_paired;
-    }
-    HIP_TRY(hipEventRecord(sl->in_ready, s));
-    sl->n_reads = n_reads; sl->state = 1; sl->seq = ++c->stream_seq;
-    c->stream_bytes_in += (uint64_t)n_reads * row_words * 4 + (uint64_t)n_reads * 4 + (uint64_t)n_odd * 8;
-    return 0;
-}
-
-extern "C" int mcx_stream_submit(mcx_ctx *c, const uint8_t *bases, const uint32_t *off, uint32_t n_reads)
-{
-    if (!c || !bases || !off || n_reads == 0) return fail(MCX_ERR_ARG, "mcx_stream_submit: bad argument");
-    if (n_reads > c->max_reads) return fail(MCX_ERR_ARG, "batch larger than max_batch_reads");
-    if (off[n_reads] > c->max_bases) return fail(MCX_ERR_ARG, "batch holds more bases than max_batch_reads * max_read_len");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    mcx_ctx::Slot *sl = nullptr;
-    int rc = stream_slot(c, &sl);
-    if (rc) return rc;
-    if (sl->d_err) HIP_TRY(hipMemsetAsync(sl->d_err, 0, 4, c->h2d_stream)); // (the slot once took 2-bit rows: nothing of that batch's verdict is this one's)
-    sl->lens_checked = false; sl->prepacked = false;
-    if ((rc = bulk_copy(c, sl->d_bases, bases, off[n_reads], hipMemcpyHostToDevice, c->h2d_stream))) return rc;
-    if ((rc = bulk_copy(c, sl->d_off, off, (size_t)(n_reads + 1) * 4, hipMemcpyHostToDevice, c->h2d_stream))) return rc;
-    HIP_TRY(hipEventRecord(sl->in_ready, c->h2d_stream));
-    sl->n_reads = n_reads; sl->state = 1; sl->seq = ++c->stream_seq;
-    c->stream_bytes_in += (uint64_t)off[n_reads] + (uint64_t)(n_reads + 1) * 4;
-    return 0;
-}
-
-// the oldest submitted batch, in HBM once the context's stream gets there
-extern "C" int mcx_stream_next(mcx_ctx *c, const uint8_t **d_bases, const uint32_t **d_off, uint32_t *n_reads, mcx_aln **d_aln, uint32_t **d_cigar)
-{
-    if (c) c->mx.ready = false; // (-m: the extras in the context are of a batch before this one)
-    if (!c || !d_bases || !d_off || !d_aln || !d_cigar) return fail(MCX_ERR_ARG, "mcx_stream_next: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (oldest_slot(c, 2)) return fail(MCX_ERR_ARG, "mcx_stream_next: the previous batch was not handed back (mcx_stream_mapped)");
-    mcx_ctx::Slot *sl = oldest_slot(c, 1);
-    if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_next: nothing submitted");
-    HIP_TRY(hipStreamWaitEvent(c->stream, sl->in_ready, 0));
-    c->lens_checked = sl->lens_checked; // (for the mcx_batch_begin that follows: no need to look for an over-long read, nor to wait for the answer)
-    c->lens_checked_off = sl->d_off; c->lens_checked_bases = sl->d_bases;
-    c->pre = mcx_ctx::PrePacked();
-    if (sl->prepacked) { c->pre.packed = sl->d_prepack; c->pre.bases = sl->d_bases; c->pre.paired = sl->pre_paired; c->pre.any_n = sl->d_any_n; }
-    sl->state = 2;
-    *d_bases = sl->d_bases; *d_off = sl->d_off; *d_aln = (mcx_aln *)sl->d_recs; *d_cigar = sl->d_cig;
-    if (n_reads) *n_reads = sl->n_reads;
-    return 0;
-}
-
-__global__ void __launch_bounds__(256) k_pack_recs(const AlnRec *recs, uint32_t n, mcx_aln32 *out);
-
-// (-m) the batch's extras, in read order in the context's buffers until its next batch begins, go into the slot's own on the
-// mapping stream (packed to mcx_aln32 like the records) — behind its `mapped` event their copy out joins the records'
-static int slot_multi_pack(mcx_ctx *c, mcx_ctx::Slot *sl)
-{
-    auto &o = sl->mx;
-    const auto &m = c->mx;
-    o.have = m.on && m.ready && m.n_reads == sl->n_reads;
-    if (!o.have) { o.n_reads = o.n_recs = o.n_words = 0; return 0; }
-    int rc;
-    if (!o.d_index && (rc = dmalloc(&o.d_index, c->max_reads + 1))) return rc;
-    if (m.n_recs > o.rec_cap) {
-        if (o.d_recs) (void)hipFree(o.d_recs);
-        o.d_recs = nullptr; o.rec_cap = 0;
-        if ((rc = dmalloc(&o.d_recs, (size_t)m.n_recs + m.n_recs / 2 + 1024))) return rc;
-        o.rec_cap = m.n_recs + m.n_recs / 2 + 1024;
-    }
-    if (m.n_words > o.word_cap) {
-        if (o.d_cig) (void)hipFree(o.d_cig);
-        o.d_cig = nullptr; o.word_cap = 0;
-        if ((rc = dmalloc(&o.d_cig, (size_t)m.n_words + m.n_words / 2 + 4096))) return rc;
-        o.word_cap = m.n_words + m.n_words / 2 + 4096;
-    }
-    o.n_reads = m.n_reads; o.n_recs = m.n_recs; o.n_words = m.n_words;
-    HIP_TRY(hipMemcpyAsync(o.d_index, m.d_index, ((size_t)o.n_reads + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (o.n_words) HIP_TRY(hipMemcpyAsync(o.d_cig, m.d_out_cig, (size_t)o.n_words * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (o.n_recs) k_pack_recs<<<(o.n_recs + 255) / 256, 256, 0, c->stream>>>(m.d_out, o.n_recs, o.d_recs);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ... and their copy to the slot's page-locked buffers on the copy-out stream (counted in bytes_out)
-static int slot_multi_out(mcx_ctx *c, mcx_ctx::Slot *sl)
-{
-    auto &o = sl->mx;
-    if (!o.have) return 0;
-    if (!o.h_index) { o.h_index = (uint32_t *)mcx_pinned_alloc((c->max_reads + 1) * 4); if (!o.h_index) return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
-    if (o.n_recs > o.h_rec_cap) {
-        mcx_pinned_free(o.h_recs); o.h_rec_cap = o.rec_cap;
-        if (!(o.h_recs = (mcx_aln32 *)mcx_pinned_alloc((size_t)o.h_rec_cap * sizeof(mcx_aln32)))) { o.h_rec_cap = 0; return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
-    }
-    if (o.n_words > o.h_word_cap) {
-        mcx_pinned_free(o.h_cig); o.h_word_cap = o.word_cap;
-        if (!(o.h_cig = (uint32_t *)mcx_pinned_alloc((size_t)o.h_word_cap * 4))) { o.h_word_cap = 0; return fail(MCX_ERR_DEVICE, "cannot allocate pinned host memory"); }
-    }
-    const size_t b_index = ((size_t)o.n_reads + 1) * 4, b_recs = (size_t)o.n_recs * sizeof(mcx_aln32), b_cig = (size_t)o.n_words * 4;
-    HIP_TRY(hipMemcpyAsync(o.h_index, o.d_index, b_index, hipMemcpyDeviceToHost, c->d2h_stream));
-    if (b_recs) HIP_TRY(hipMemcpyAsync(o.h_recs, o.d_recs, b_recs, hipMemcpyDeviceToHost, c->d2h_stream));
-    if (b_cig) HIP_TRY(hipMemcpyAsync(o.h_cig, o.d_cig, b_cig, hipMemcpyDeviceToHost, c->d2h_stream));
-    c->stream_bytes_out += b_index + b_recs + b_cig;
-    return 0;
-}
-
-extern "C" int mcx_stream_multi(mcx_ctx *c, const uint32_t **index, const mcx_aln32 **recs, const uint32_t **cigar, uint32_t *n_reads, uint32_t *n_recs, uint32_t *n_words)
-{
-    if (!c) return fail(MCX_ERR_ARG, "mcx_stream_multi: null argument");
-    if (!c->mx.on) return fail(MCX_ERR_ARG, "mcx_stream_multi: -m is off (mcx_ctx_set_multi)");
-    const mcx_ctx::Slot *sl = c->collected;
-    const bool have = sl && sl->mx.have;
-    if (index) *index = have ? sl->mx.h_index : nullptr;
-    if (recs) *recs = have ? sl->mx.h_recs : nullptr;
-    if (cigar) *cigar = have ? sl->mx.h_cig : nullptr;
-    if (n_reads) *n_reads = have ? sl->mx.n_reads : 0;
-    if (n_recs) *n_recs = have ? sl->mx.n_recs : 0;
-    if (n_words) *n_words = have ? sl->mx.n_words : 0;
-    return 0;
-}
-
-// the batch mcx_stream_next gave out is mapped: its results start their way to host memory
-extern "C" int mcx_stream_mapped(mcx_ctx *c, mcx_aln *aln, uint32_t *cigar)
-{
-    if (!c || !aln || !cigar) return fail(MCX_ERR_ARG, "mcx_stream_mapped: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    mcx_ctx::Slot *sl = oldest_slot(c, 2);
-    if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_mapped: no batch is being mapped");
-    int rc;
-    if ((rc = slot_multi_pack(c, sl))) return rc;
-    HIP_TRY(hipEventRecord(sl->mapped, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl->mapped, 0));
-    const size_t rec_bytes = (size_t)sl->n_reads * sizeof(AlnRec), cig_bytes = (size_t)c->run.cig_words * 4; // (the pool's used words only)
-    if ((rc = slot_multi_out(c, sl))) return rc;
-    if ((rc = bulk_copy(c, aln, sl->d_recs, rec_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
-    if ((rc = bulk_copy(c, cigar, sl->d_cig, cig_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
-    if (sl->lens_checked) HIP_TRY(hipMemcpyAsync(sl->h_err, sl->d_err, 4, hipMemcpyDeviceToHost, c->d2h_stream)); // what k_unpack_reads thought of the caller's lengths: mcx_stream_collect reads it
-    HIP_TRY(hipEventRecord(sl->out_done, c->d2h_stream));
-    sl->state = 3;
-    c->stream_bytes_out += rec_bytes + cig_bytes;
-    return 0;
-}
-
-// the records of a mapped batch in 32 bytes each (mcx_aln32, include/mcx.h) for their way to the host
-__global__ void __launch_bounds__(256) k_pack_recs(const AlnRec *recs, uint32_t n, mcx_aln32 *out)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const AlnRec a = recs[r];
-    mcx_aln32 o;
-    o.pos_lo = (uint32_t)a.pos; o.pos_hi = (uint8_t)((uint64_t)a.pos >> 32); o.mate_lo = (uint32_t)a.mate_pos; o.mate_hi = (uint8_t)((uint64_t)a.mate_pos >> 32);
-    o.mapq = (uint8_t)a.mapq; o.bits = (uint8_t)((a.fwd ? 1 : 0) | (a.has_mate ? 2 : 0)); o.tlen = a.tlen; o.flag = (uint16_t)a.flag;
-    o.chr = a.chr < 0 ? (uint16_t)0xFFFFu : (uint16_t)a.chr; o.nm = (int16_t)a.nm; o.as = (int16_t)a.as; o.xs = (int16_t)a.xs;
-    o.n_cigar = (uint16_t)a.n_cigar; o.cigar_off = (uint32_t)a.pad[0];
-    ((U4 *)out)[2 * (uint64_t)r] = ((const U4 *)&o)[0]; ((U4 *)out)[2 * (uint64_t)r + 1] = ((const U4 *)&o)[1];
-}
-
-extern "C" int mcx_stream_mapped32(mcx_ctx *c, mcx_aln32 *aln, uint32_t *cigar)
-{
-    static_assert(sizeof(mcx_aln32) == 32, "mcx_aln32 is two 16-byte words");
-    if (!c || !aln || !cigar) return fail(MCX_ERR_ARG, "mcx_stream_mapped32: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    mcx_ctx::Slot *sl = oldest_slot(c, 2);
-    if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_mapped32: no batch is being mapped");
-    if (c->idx->view.n_chr >= 0xFFFF || (c->idx->view.G2 >> 40)) return fail(MCX_ERR_UNSUPPORTED, "mcx_stream_mapped32: more than 65534 contigs or positions beyond 2^40 (use mcx_stream_mapped)");
-    int rc;
-    if (!sl->d_recs32 && (rc = dmalloc(&sl->d_recs32, c->max_reads))) return rc;
-    k_pack_recs<<<(sl->n_reads + 255) / 256, 256, 0, c->stream>>>(sl->d_recs, sl->n_reads, sl->d_recs32); // (a read's operations are at most MCX_CIGAR_STRIDE x the pool's slack: far below 2^16)
-    HIP_TRY(hipGetLastError());
-    if ((rc = slot_multi_pack(c, sl))) return rc;
-    HIP_TRY(hipEventRecord(sl->mapped, c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl->mapped, 0));
-    const size_t rec_bytes = (size_t)sl->n_reads * sizeof(mcx_aln32), cig_bytes = (size_t)c->run.cig_words * 4; // (the pool's used words only)
-    if ((rc = slot_multi_out(c, sl))) return rc;
-    if ((rc = bulk_copy(c, aln, sl->d_recs32, rec_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
-    if ((rc = bulk_copy(c, cigar, sl->d_cig, cig_bytes, hipMemcpyDeviceToHost, c->d2h_stream))) return rc;
-    if (sl->lens_checked) HIP_TRY(hipMemcpyAsync(sl->h_err, sl->d_err, 4, hipMemcpyDeviceToHost, c->d2h_stream));
-    HIP_TRY(hipEventRecord(sl->out_done, c->d2h_stream));
-    sl->state = 3;
-    c->stream_bytes_out += rec_bytes + cig_bytes;
-    return 0;
-}
-
-static int stream_map(mcx_ctx *c, int paired, int64_t avg[4], mcx_aln *aln, mcx_aln32 *aln32, uint32_t *cigar, mcx_stats *stats);
-extern "C" int mcx_stream_map32(mcx_ctx *c, int paired, int64_t avg[4], mcx_aln32 *aln, uint32_t *cigar, mcx_stats *stats) { return stream_map(c, paired, avg, nullptr, aln, cigar, stats); }
-extern "C" int mcx_stream_map(mcx_ctx *c, int paired, int64_t avg[4], mcx_aln *aln, uint32_t *cigar, mcx_stats *stats) { return stream_map(c, paired, avg, aln, nullptr, cigar, stats); }
-static int stream_map(mcx_ctx *c, int paired, int64_t avg[4], mcx_aln *aln, mcx_aln32 *aln32, uint32_t *cigar, mcx_stats *stats)
-{
-    const uint8_t *d_bases; const uint32_t *d_off; mcx_aln *d_aln; uint32_t *d_cig; uint32_t n = 0;
-    int rc = mcx_stream_next(c, &d_bases, &d_off, &n, &d_aln, &d_cig);
-    if (rc) return rc;
-    rc = mcx_map_batch_dev(c, d_bases, d_off, n, paired, avg, d_aln, d_cig, stats);
-    mcx_ctx::Slot *sl = oldest_slot(c, 2);
-    if (rc == 0 && sl->lens_checked) { // what k_unpack_reads thought of the caller's lengths (a refused batch was mapped as empty reads)
-        uint32_t err = 0;
-        HIP_TRY(hipMemcpy(&err, sl->d_err, 4, hipMemcpyDeviceToHost));
-        if (err) rc = fail(MCX_ERR_ARG, (err & 1u) ? "mcx_stream_submit_packed: a read is longer than its row / max_read_len" : "batch holds more bases than max_batch_reads * max_read_len");
-    }
-    if (rc) { sl->state = 0; return rc; }
-    return aln32 ? mcx_stream_mapped32(c, aln32, cigar) : mcx_stream_mapped(c, aln, cigar);
-}
-
-extern "C" int mcx_stream_collect(mcx_ctx *c, uint64_t *bytes_in, uint64_t *bytes_out)
-{
-    if (!c) return fail(MCX_ERR_ARG, "mcx_stream_collect: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    mcx_ctx::Slot *sl = oldest_slot(c, 3);
-    if (!sl) return fail(MCX_ERR_ARG, "mcx_stream_collect: no mapped batch is on its way out");
-    HIP_TRY(hipEventSynchronize(sl->out_done));
-    sl->state = 0;
-    c->collected = sl;
-    if (bytes_in) *bytes_in = c->stream_bytes_in;
-    if (bytes_out) *bytes_out = c->stream_bytes_out;
-    if (sl->lens_checked && sl->h_err && *sl->h_err) { // the two-half form (mcx_stream_next + mcx_map_batch_dev / mcx_batch_* + mcx_stream_mapped): the refusal arrives with the records
-        const uint32_t err = *sl->h_err;
-        *sl->h_err = 0;
-        return fail(MCX_ERR_ARG, (err & 1u) ? "mcx_stream_submit_packed: a read is longer than its row / max_read_len (the batch was mapped as empty reads)"
-                                            : "mcx_stream_submit_packed: the batch holds more bases than max_batch_reads * max_read_len (it was mapped as empty reads)");
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// -vcf bookkeeping: UpdateProfile / UpdateMultiHitCount for a finished batch (mcx_profile.h)
-// ---------------------------------------------------------------------------------------------
-// discordant-pair events, ReadMapping.cpp:486-521: kept as seen ('E' records: pos = the pair's number in the input stream,
-// len = kind, seq = g1, g2, dist) — the reference's second branch pushes its DiscordPair variable whatever the previous
-// discordant pair left in it, so they are resolved in input order once the run is over
-// (mcx_disc_resolve: mcx_profile_sparse for one shard, mcx_call_variants for several)
-__global__ void k_prof_disc(const uint8_t *detail, DetailLayout dl, uint32_t n_pairs, int64_t first_pair, SparseRec *out, uint32_t *n, uint32_t cap)
-{
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-    const DetailHdr &d = *(const DetailHdr *)(detail + (uint64_t)(2 * p) * dl.stride);
-    if (d.disc_kind == 0) return;
-    const uint32_t at = atomicAdd(n, 1u);
-    if (at >= cap) return;
-    SparseRec e;
-    uint64_t *w = (uint64_t *)&e;
-    for (int k = 0; k < (int)(sizeof(SparseRec) / 8); k++) w[k] = 0;
-    e.pos = first_pair + p; e.type = 'E'; e.len = (uint8_t)d.disc_kind;
-    const int64_t v[3] = {d.disc_g1, d.disc_g2, d.disc_dist};
-    memcpy(e.seq, v, sizeof v);
-    out[at] = e;
-}
-
-extern "C" int mcx_profile_attach(mcx_ctx *c, uint32_t *d_planes, int max_dup, int max_clip)
-{
-    static_assert(sizeof(mcx_sparse_rec) == sizeof(SparseRec), "mcx_sparse_rec and SparseRec must have one layout");
-    if (!c || !d_planes) return fail(MCX_ERR_ARG, "mcx_profile_attach: null argument");
-    if (c->idx->view.G >= (int64_t)1 << 32) return fail(MCX_ERR_UNSUPPORTED, "the alignment profile takes genomes below 2^32 bases");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (c->later.pending) { (void)hipStreamSynchronize(c->later.stream); c->later.pending = false; } // (a profile that is given up with a batch's bookkeeping on its way)
-    c->prof_planes = d_planes;
-    c->prof_max_dup = (max_dup <= 0 || max_dup > 15) ? 15 : max_dup; // main.cpp:240-244, :323
-    c->prof_max_clip = max_clip;
-    if (!c->d_detail) {
-        c->dlay = make_detail_layout(c->rlen_max);
-        int rc;
-        if ((rc = dmalloc(&c->d_detail, (size_t)c->dlay.stride * c->max_reads))) return rc;
-        if ((rc = dmalloc(&c->d_admit, c->max_reads + 4))) return rc;
-        c->prof_items_cap = (uint32_t)std::min<uint64_t>((uint64_t)c->max_reads * 4 + 1024, 0x7fffffffu);
-        if ((rc = dmalloc(&c->d_prof_items, c->prof_items_cap))) return rc;
-        if ((rc = sort_reserve(c, c->max_reads))) return rc;
-        c->sparse_cap = (uint32_t)std::min<uint64_t>(c->max_reads * 2 + 4096, 0x7fffffffu);
-        if ((rc = dmalloc(&c->d_sparse, c->sparse_cap))) return rc;
-        HIP_TRY(hipHostMalloc((void **)&c->h_sparse_pin, (size_t)c->sparse_pin_recs * sizeof(SparseRec)));
-    }
-    c->h_sparse.clear(); c->h_events.clear(); c->n_tally = 0; c->arch.n = c->arch_ev.n = 0;
-    c->arch.host = &c->h_sparse; c->arch_ev.host = &c->h_events;
-    if (!c->arch.d) { // room for the first batches' records now, not in the middle of the first batch
-        const uint64_t first = std::min<uint64_t>(std::max<uint64_t>(c->sparse_cap, (uint64_t)1 << 20), (uint64_t)1 << 22);
-        if (hipMalloc((void **)&c->arch.d, first * sizeof(SparseRec)) == hipSuccess) c->arch.cap = first; else { (void)hipGetLastError(); c->arch.d = nullptr; }
-    }
-    const size_t match_n = (size_t)planes_stride(c->idx->view.G);
-    if (!c->d_prof_match) {
-        int rc = dmalloc(&c->d_prof_match, match_n);
-        if (rc && c->later.have) { // the device has filled up since the second set was taken: it goes back, the bookkeeping runs inside the batches' calls from here on
-            auto &L = c->later;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(L.stream); (void)hipStreamSynchronize(L.keep_stream);
-            for (void **q : {(void **)&L.d_detail_alt, (void **)&L.d_admit_alt, (void **)&L.d_keep_bases, (void **)&L.d_keep_off, (void **)&L.d_keep_bases_alt, (void **)&L.d_keep_off_alt, (void **)&L.d_ev}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-            L.have = false;
-            if (c->kn.timing) fprintf(stderr, "[mcx profile] the second set of detail records goes back: the device has no room for the coverage plane beside it\n");
-            rc = dmalloc(&c->d_prof_match, match_n);
-        }
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemsetAsync(c->d_prof_match, 0, match_n * sizeof(uint16_t), c->stream));
-    if (!c->kn.no_prof_overlap && !c->later.have && !c->later.tried) { // a second set of what a batch's mapping writes for the bookkeeping, if HBM has the room (without it: the bookkeeping inside the call, as before)
-        auto &L = c->later;
-        L.tried = true;
-        L.ev_cap = (uint32_t)std::min<uint64_t>(c->max_reads / 2 + 4096, 0x7fffffffu);
-        // (a stream of the lowest priority: queues of a priority of their own in the runtime — a stream of the default priority may share a hardware queue with the
-        //  context's main stream, and then the bookkeeping runs before the next batch's kernels, not under them — and the mapping goes first where both want the chip)
-        int prio_low = 0, prio_high = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
-        size_t hbm_free = 0, hbm_all = 0;
-        (void)hipMemGetInfo(&hbm_free, &hbm_all);
-        const size_t second_set = (size_t)c->dlay.stride * c->max_reads + 2 * (c->max_bases + 4 * c->max_reads) + (size_t)L.ev_cap * sizeof(SparseRec);
-        // (what is left afterwards has to hold the record archive's growth and the caller's own buffers: four gigabytes at least)
-        bool ok = hbm_free > second_set + ((size_t)4 << 30) && hipMalloc((void **)&L.d_detail_alt, (size_t)c->dlay.stride * c->max_reads) == hipSuccess && hipMalloc((void **)&L.d_admit_alt, c->max_reads + 4) == hipSuccess &&
-                  hipMalloc((void **)&L.d_keep_bases, c->max_bases + 64) == hipSuccess && hipMalloc((void **)&L.d_keep_off, (c->max_reads + 1) * sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void **)&L.d_keep_bases_alt, c->max_bases + 64) == hipSuccess && hipMalloc((void **)&L.d_keep_off_alt, (c->max_reads + 1) * sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void **)&L.d_cnt, CNT_N * sizeof(uint32_t)) == hipSuccess && hipMalloc((void **)&L.d_ev, (size_t)L.ev_cap * sizeof(SparseRec)) == hipSuccess &&
-                  hipHostMalloc((void **)&L.h_cnt, CNT_N * sizeof(uint32_t)) == hipSuccess &&
-                  hipStreamCreateWithPriority(&L.stream, hipStreamNonBlocking, prio_low) == hipSuccess && hipStreamCreateWithPriority(&L.keep_stream, hipStreamNonBlocking, prio_low) == hipSuccess;
-        for (hipEvent_t *e : {&L.go, &L.done, &L.kept, &L.begun}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (void **q : {(void **)&L.d_detail_alt, (void **)&L.d_admit_alt, (void **)&L.d_keep_bases, (void **)&L.d_keep_off, (void **)&L.d_keep_bases_alt, (void **)&L.d_keep_off_alt, (void **)&L.d_cnt, (void **)&L.d_ev}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-            if (c->kn.timing) fprintf(stderr, "[mcx profile] no room in HBM for a second set of detail records: a batch's bookkeeping runs inside its call\n");
-        }
-        L.have = ok;
-    }
-    c->prof_settled = false; c->prof_broken = false;
-    return 0;
-}
-
-// A context — and, for a -vcf run, the planes and the bookkeeping's buffers — sized to what the device has left (the -vcf leg at 3.1 Gbp left
-// 5.4 GB of 309, and a larger genome met a bare hipMalloc failure in the middle of its first batch).  Everything the run will take is taken HERE: the context,
-// tier 0's pair records (otherwise the first batch's), the planes, the detail records.  When that does not fit with kFitMargin to spare — the record
-// archive's growth, the caller's own batches, the stream slots — the run is degraded in a fixed order, each step said on stderr in one line:
-//   1. the index gives its pair records back (mcx_index_trim: the seeding walk takes one base per step, 24.8 GB at 3.1 Gbp);
-//   2. max_batch_reads is halved, again and again (down to 128 K reads);
-// (a second set of detail records, which lets a batch's bookkeeping run under the next batch, is only ever taken when there is room: mcx_profile_attach).
-// MCX_HBM_CAP_GB=n (tests): the run may take n GB, whatever the device has free.
-constexpr size_t kFitMargin = (size_t)4 << 30;
-extern "C" int mcx_ctx_create_fit(mcx_index *ix, const mcx_opts *opts, int with_profile, int paired, int max_dup, int max_clip, mcx_ctx **out, uint32_t **planes, mcx_fit *fit)
-{
-    if (!ix || !out || (with_profile && !planes)) return fail(MCX_ERR_ARG, "mcx_ctx_create_fit: null argument");
-    mcx_opts o;
-    if (opts) o = *opts; else mcx_opts_default(&o);
-    mcx_fit f; memset(&f, 0, sizeof f);
-    size_t cap = 0; // MCX_HBM_CAP_GB=n (tests): the run may take n GB of the device, whatever is free
-    if (const char *e = getenv("MCX_HBM_CAP_GB")) cap = (size_t)(atof(e) * (double)((size_t)1 << 30));
-    HIP_TRY(hipSetDevice(ix->device));
-    for (;;) {
-        mcx_ctx *c = nullptr;
-        uint32_t *pl = nullptr;
-        size_t free0 = 0, hbm_free = 0, hbm_all = 0;
-        (void)hipMemGetInfo(&free0, &hbm_all);
-        int rc = mcx_ctx_create(ix, &o, &c);
-        if (rc == 0) rc = reserve_tier0(c, paired, (uint64_t)o.max_batch_reads);
-        if (rc == 0 && with_profile) {
-            rc = mcx_planes_alloc(ix, &pl);
-            if (rc == 0) rc = mcx_profile_attach(c, pl, max_dup, max_clip);
-        }
-        (void)hipMemGetInfo(&hbm_free, &hbm_all);
-        const size_t took = free0 > hbm_free ? free0 - hbm_free : 0;
-        if (cap) hbm_free = std::min(hbm_free, cap > took ? cap - took : 0);
-        const bool fits = rc == 0 && hbm_free >= kFitMargin;
-        if (fits) {
-            f.max_batch_reads = o.max_batch_reads; f.hbm_free_bytes = (int64_t)hbm_free; f.hbm_taken_bytes = (int64_t)took; f.single_detail_set = with_profile && !c->later.have;
-            if (fit) *fit = f;
-            *out = c;
-            if (planes) *planes = pl;
-            return 0;
-        }
-        const std::string why = rc ? std::string(mcx_last_error()) : std::to_string((double)hbm_free / 1e9).substr(0, 5) + " GB of HBM would be left";
-        (void)hipGetLastError(); // (an allocation that failed is no error of the run)
-        if (pl) mcx_planes_free(pl);
-        if (c) mcx_ctx_free(c);
-        if (rc && rc != MCX_ERR_DEVICE) return rc; // (not a matter of room)
-        if (ix->d_rank2) {
-            if ((rc = mcx_index_trim(ix, 1))) return rc;
-            f.pair_records_trimmed = 1;
-            fprintf(stderr, "[mcx fit] %s with batches of %lld reads: the index gives its pair records back (the seeding walk takes one base per step)\n", why.c_str(), (long long)o.max_batch_reads);
-            continue;
-        }
-        if (o.max_batch_reads > ((int64_t)1 << 17)) {
-            o.max_batch_reads = std::max<int64_t>((int64_t)1 << 17, (o.max_batch_reads / 2 + 199) / 200 * 200); // (whole 200-read chunks: a caller that cuts its run into batches of this size keeps the chunk boundaries)
-            f.batch_halvings++;
-            fprintf(stderr, "[mcx fit] %s: batches of %lld reads instead\n", why.c_str(), (long long)o.max_batch_reads);
-            continue;
-        }
-        return fail(MCX_ERR_DEVICE, "mcx_ctx_create_fit: the device has no room for this run even with batches of " + std::to_string((long long)o.max_batch_reads) + " reads and without the pair records (" + why + ")");
-    }
-}
-
-// key buffers and radix-sort scratch for n keys (grown on demand: a round's keys of all shards can outnumber a batch)
-static int sort_reserve(mcx_ctx *c, uint64_t n)
-{
-    if (n <= c->keys_cap) return 0;
-    for (int k = 0; k < 2; k++) { if (c->d_keys[k]) (void)hipFree(c->d_keys[k]); c->d_keys[k] = nullptr; }
-    if (c->d_sort_tmp) { (void)hipFree(c->d_sort_tmp); c->d_sort_tmp = nullptr; }
-    c->keys_cap = 0;
-    int rc;
-    for (int k = 0; k < 2; k++) if ((rc = dmalloc(&c->d_keys[k], n))) return rc;
-    hipcub::DoubleBuffer<uint64_t> dk(c->d_keys[0], c->d_keys[1]);
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, c->sort_tmp_bytes, dk, (int64_t)n, 0, 64));
-    HIP_TRY(hipMalloc(&c->d_sort_tmp, c->sort_tmp_bytes + 256));
-    c->keys_cap = n;
-    return 0;
-}
-
-// What the host has to do about a queued batch's bookkeeping once it is through: overflow checks, the records into the archives.
-static int profile_collect(mcx_ctx *c)
-{
-    auto &L = c->later;
-    if (!L.pending) return 0;
-    L.pending = false;
-    HIP_TRY(hipEventSynchronize(L.done));
-    const uint32_t n_sp = L.h_cnt[CNT_TASKS], n_ev = L.h_cnt[CNT_RESCUE];
-    if (n_sp > c->sparse_cap || n_ev > L.ev_cap) return fail(MCX_ERR_CAPACITY, "profile: sparse record list overflow");
-    if (L.h_cnt[CNT_UNSUP]) return fail(MCX_ERR_UNSUPPORTED, "an insertion or deletion of more than 255 bases in an alignment: its string does not fit a tally record");
-    if (int rc = archive_append(c, c->arch, c->d_sparse, n_sp, L.stream)) return rc;
-    if (int rc = archive_append(c, c->arch_ev, L.d_ev, n_ev, L.stream)) return rc;
-    HIP_TRY(hipStreamSynchronize(L.stream)); // (the archives are read on the context's stream; the lists are the next batch's to fill)
-    if (c->kn.timing) fprintf(stderr, "[mcx profile] %u tally records, %u events, %u listed fragments (queued behind the batch; looked at %.2f ms later)\n", n_sp, n_ev, L.h_cnt[CNT_RTASK],
-                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - L.t_queued).count());
-    return 0;
-}
-
-// One shard: the whole bookkeeping of the batch just mapped — keys, sort, admission, accumulation — queued on the bookkeeping's stream; nothing of it is
-// waited for here.  The number of keys stays on the device (k_prof_admit / k_prof_count take it from there), the break-point records' count stays where
-// k_prof_keys left it.  The next batch's mapping writes the other set of detail records and flag bytes.
-static int profile_queue(mcx_ctx *c)
-{
-    if (c->prof_settled) return fail(MCX_ERR_ARG, "the profile has been settled (mcx_profile_settle / _finalize): attach it again before mapping more reads");
-    if (int rc = profile_collect(c)) return rc; // (the batch before this one: through long ago, it ran under this batch's kernels)
-    auto &L = c->later;
-    BatchRun &br = c->run;
-    hipStream_t ps = L.stream;
-    const IndexView &ix = c->idx->view;
-    ProfView pv; pv.pl = planes_view(c->prof_planes, ix.G); pv.match = c->d_prof_match; pv.G = ix.G; pv.max_dup = c->prof_max_dup; pv.max_clip = c->prof_max_clip;
-    SparseSink sink; sink.recs = c->d_sparse; sink.n = L.d_cnt + CNT_TASKS; sink.cap = c->sparse_cap; sink.refused = L.d_cnt + CNT_UNSUP;
-    const uint32_t n = br.rb.n_reads;
-    ReadBatch rb; rb.bases = L.d_keep_bases; rb.off = L.d_keep_off; rb.n_reads = n;
-    HIP_TRY(hipEventSynchronize(L.kept)); // (the caller's buffer is the caller's again: the copy was made beside the batch's first kernels)
-    HIP_TRY(hipEventRecord(L.go, c->stream));
-    HIP_TRY(hipStreamWaitEvent(ps, L.go, 0));
-    HIP_TRY(hipMemsetAsync(L.d_cnt, 0, CNT_N * sizeof(uint32_t), ps));
-    k_prof_keys<<<(n + 255) / 256, 256, 0, ps>>>(c->d_detail, c->dlay, rb, ix, pv, sink, c->d_keys[0], L.d_cnt + CNT_OV);
-    hipcub::DoubleBuffer<uint64_t> dk(c->d_keys[0], c->d_keys[1]);
-    size_t tb = c->sort_tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, tb, dk, (int64_t)n, 0, 64, ps));
-    const uint64_t *d_keys = dk.Current(); // (the keys of the reads that do not reach the duplicate check are ~0 and sort behind the others)
-    // the counters of the second half start at zero, but for the two the first half hands over: the keys' number, the break-point records'
-    static_assert(CNT_OV < CNT_N && CNT_TASKS < CNT_N, "counter indices");
-    k_zero_but<<<1, 64, 0, ps>>>(L.d_cnt, CNT_N, CNT_OV, CNT_TASKS);
-    k_prof_admit<<<(n + 255) / 256, 256, 0, ps>>>(d_keys, 0, pv, c->d_admit, 0u, n, L.d_cnt + CNT_OV);
-    k_prof_count<<<(n + 255) / 256, 256, 0, ps>>>(d_keys, 0, pv, L.d_cnt + CNT_OV);
-    ColList cols; cols.items = c->d_prof_items; cols.n = L.d_cnt + CNT_RTASK; cols.cap = c->prof_items_cap;
-    // (a smaller grid for the two — 512 to 4096 workgroups, the batch walked in strides — changes nothing: 28.8-29.3 ms per batch either way; what the bookkeeping
-    //  and the mapping beside it share is the memory system's rate of scattered line transfers, not the CUs)
-    k_prof_accum<<<(n + 255) / 256, 256, 0, ps>>>(c->d_detail, c->dlay, rb, ix, pv, sink, c->d_admit, br.paired, cols);
-    k_prof_cols<<<4096, 256, 0, ps>>>(c->d_detail, c->dlay, rb, ix, pv, sink, cols);
-    if (br.paired) k_prof_disc<<<(n / 2 + 255) / 256, 256, 0, ps>>>(c->d_detail, c->dlay, n / 2, br.read_base / 2, L.d_ev, L.d_cnt + CNT_RESCUE, L.ev_cap);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_cnt, L.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-    HIP_TRY(hipEventRecord(L.done, ps));
-    L.pending = true; L.t_queued = std::chrono::steady_clock::now();
-    std::swap(c->d_detail, L.d_detail_alt); std::swap(c->d_admit, L.d_admit_alt); // the next batch's mapping writes the other set,
-    std::swap(L.d_keep_bases, L.d_keep_bases_alt); std::swap(L.d_keep_off, L.d_keep_off_alt); // its reads are kept in the other copy
-    return 0;
-}
-
-// break points, clip gate, and the sorted (start position, read) keys of the reads that reach the duplicate check
-static int profile_keys(mcx_ctx *c)
-{
-    BatchRun &br = c->run;
-    hipStream_t s = c->stream;
-    const IndexView &ix = c->idx->view;
-    ProfView pv; pv.pl = planes_view(c->prof_planes, ix.G); pv.match = c->d_prof_match; pv.G = ix.G; pv.max_dup = c->prof_max_dup; pv.max_clip = c->prof_max_clip;
-    SparseSink sink; sink.recs = c->d_sparse; sink.n = c->d_cnt + CNT_TASKS; sink.cap = c->sparse_cap; sink.refused = c->d_cnt + CNT_UNSUP;
-    const uint32_t n = br.rb.n_reads;
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-    k_prof_keys<<<(n + 255) / 256, 256, 0, s>>>(c->d_detail, c->dlay, br.rb, ix, pv, sink, c->d_keys[0], c->d_cnt + CNT_OV);
-    hipcub::DoubleBuffer<uint64_t> dk(c->d_keys[0], c->d_keys[1]);
-    size_t tb = c->sort_tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, tb, dk, (int64_t)n, 0, 64, s));
-    HIP_TRY(hipMemcpyAsync(c->h_cnt, c->d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    br.d_sorted_keys = dk.Current();
-    br.n_keys = c->h_cnt[CNT_OV];       // the keys of the other reads are ~0 and sort behind them
-    br.n_sparse_keys = c->h_cnt[CNT_TASKS]; // break-point records so far; the accumulation appends behind them
-    return 0;
-}
-
-// the keys of a round this shard has no reads in: only the run's readCount moves
-static int profile_foreign(mcx_ctx *c, const uint64_t *h_all, uint64_t n_all)
-{
-    if (n_all == 0) return 0;
-    hipStream_t s = c->stream;
-    ProfView pv; pv.pl = planes_view(c->prof_planes, c->idx->view.G); pv.match = c->d_prof_match; pv.G = c->idx->view.G; pv.max_dup = c->prof_max_dup; pv.max_clip = c->prof_max_clip;
-    int rc = sort_reserve(c, n_all);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_keys[0], h_all, n_all * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    hipcub::DoubleBuffer<uint64_t> dk(c->d_keys[0], c->d_keys[1]);
-    size_t tb = c->sort_tmp_bytes;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, tb, dk, (int64_t)n_all, 0, 64, s));
-    k_prof_count<<<(unsigned)((n_all + 255) / 256), 256, 0, s>>>(dk.Current(), n_all, pv);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-// the archived records leave HBM: through the two halves of a page-locked bounce buffer (a copy from HBM straight into
-// pageable memory runs at ~1 GB/s), the next piece in flight while this one is copied out
-static int archive_flush(mcx_ctx *c, mcx_ctx::Archive &a)
-{
-    if (a.n == 0) return 0;
-    hipStream_t s = c->stream;
-    std::vector<mcx_sparse_rec> &host = *a.host;
-    const bool tallies = &a == &c->arch;
-    if (tallies) host.resize(c->n_tally); // (what the last mcx_profile_sparse* call appended for its caller goes again)
-    host.reserve(host.size() + a.n); // (no resize: that would be one thread zeroing fresh pages before the copy touches them again)
-    const uint64_t half = c->sparse_pin_recs / 2;
-    const uint64_t n_piece = (a.n + half - 1) / half;
-    auto start = [&](uint64_t k) -> hipError_t {
-        const uint64_t lo = k * half, m = std::min<uint64_t>(half, a.n - lo);
-        return hipMemcpyAsync(c->h_sparse_pin + (k & 1) * half, a.d + lo, m * sizeof(SparseRec), hipMemcpyDeviceToHost, s);
-    };
-    HIP_TRY(start(0));
-    for (uint64_t k = 0; k < n_piece; k++) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (k + 1 < n_piece) HIP_TRY(start(k + 1));
-        const uint64_t lo = k * half, m = std::min<uint64_t>(half, a.n - lo);
-        const mcx_sparse_rec *piece = (const mcx_sparse_rec *)(c->h_sparse_pin + (k & 1) * half);
-        host.insert(host.end(), piece, piece + m);
-    }
-    a.n = 0;
-    if (tallies) c->n_tally = host.size();
-    return 0;
-}
-
-static int sparse_flush(mcx_ctx *c)
-{
-    if (int rc = profile_collect(c)) return rc;
-    c->h_sparse.resize(c->n_tally);
-    if (int rc = archive_flush(c, c->arch)) return rc;
-    return archive_flush(c, c->arch_ev);
-}
-
-// n records at d_src join an archive (on the stream); an archive that cannot grow any more goes to the host first
-static int archive_append(mcx_ctx *c, mcx_ctx::Archive &a, const SparseRec *d_src, uint64_t n, hipStream_t on)
-{
-    if (n == 0) return 0;
-    hipStream_t s = on ? on : c->stream;
-    if (a.n + n > a.cap) {
-        const uint64_t want = std::max<uint64_t>({2 * a.cap, a.n + n, &a == &c->arch ? (uint64_t)1 << 22 : (uint64_t)1 << 18});
-        SparseRec *grown = nullptr;
-        if (want <= c->arch_limit && hipMalloc((void **)&grown, want * sizeof(SparseRec)) == hipSuccess) {
-            if (a.n) HIP_TRY(hipMemcpyAsync(grown, a.d, a.n * sizeof(SparseRec), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (a.d) (void)hipFree(a.d);
-            a.d = grown; a.cap = want;
-        } else {
-            (void)hipGetLastError();
-            if (c->kn.timing) fprintf(stderr, "[mcx profile] no room in HBM for a larger record archive (%llu records wanted): what it holds goes to the host now, batch by batch from here on\n", (unsigned long long)want);
-            int rc = archive_flush(c, a); // no room for a larger archive: what it holds goes to the host now
-            if (rc) return rc;
-            if (n > a.cap) {
-                if (a.d) (void)hipFree(a.d);
-                a.d = nullptr; a.cap = 0;
-                HIP_TRY(hipMalloc((void **)&a.d, (size_t)n * sizeof(SparseRec)));
-                a.cap = n;
-            }
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(a.d + a.n, d_src, (size_t)n * sizeof(SparseRec), hipMemcpyDeviceToDevice, s));
-    a.n += n;
-    return 0;
-}
-
-// admission over `all` keys (null: the batch's own, already sorted on the device), then the accumulation of the own reads
-static int profile_accumulate(mcx_ctx *c, const uint64_t *h_all, uint64_t n_all, uint32_t slot_stride, uint32_t own_slot)
-{
-    if (c->prof_settled) return fail(MCX_ERR_ARG, "the profile has been settled (mcx_profile_settle / _finalize): attach it again before mapping more reads");
-    BatchRun &br = c->run;
-    hipStream_t s = c->stream;
-    const IndexView &ix = c->idx->view;
-    ProfView pv; pv.pl = planes_view(c->prof_planes, ix.G); pv.match = c->d_prof_match; pv.G = ix.G; pv.max_dup = c->prof_max_dup; pv.max_clip = c->prof_max_clip;
-    SparseSink sink; sink.recs = c->d_sparse; sink.n = c->d_cnt + CNT_TASKS; sink.cap = c->sparse_cap; sink.refused = c->d_cnt + CNT_UNSUP;
-    const uint32_t n = br.rb.n_reads;
-    const int paired = br.paired;
-    const uint64_t *d_keys = br.d_sorted_keys;
-    uint64_t nk = br.n_keys;
-    uint32_t own_lo = 0;
-    if (h_all) {
-        int rc = sort_reserve(c, std::max<uint64_t>(n_all, 1)); // (invalidates br.d_sorted_keys: the own keys are part of h_all)
-        if (rc) return rc;
-        if (n_all) HIP_TRY(hipMemcpyAsync(c->d_keys[0], h_all, n_all * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        hipcub::DoubleBuffer<uint64_t> dk(c->d_keys[0], c->d_keys[1]);
-        size_t tb = c->sort_tmp_bytes;
-        if (n_all) HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->d_sort_tmp, tb, dk, (int64_t)n_all, 0, 64, s));
-        d_keys = dk.Current(); nk = n_all; own_lo = own_slot * slot_stride;
-    }
-    HIP_TRY(hipMemsetAsync(c->d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-    HIP_TRY(hipMemcpyAsync(c->d_cnt + CNT_TASKS, &br.n_sparse_keys, sizeof(uint32_t), hipMemcpyHostToDevice, s)); // (pageable source: copied before the call returns)
-    if (nk) {
-        k_prof_admit<<<(unsigned)((nk + 255) / 256), 256, 0, s>>>(d_keys, nk, pv, c->d_admit, own_lo, n);
-        k_prof_count<<<(unsigned)((nk + 255) / 256), 256, 0, s>>>(d_keys, nk, pv);
-    }
-    ColList cols; cols.items = c->d_prof_items; cols.n = c->d_cnt + CNT_RTASK; cols.cap = c->prof_items_cap;
-    k_prof_accum<<<(n + 255) / 256, 256, 0, s>>>(c->d_detail, c->dlay, br.rb, ix, pv, sink, c->d_admit, paired, cols); // (bit 1 of a flag byte: k_pack_reads')
-    k_prof_cols<<<4096, 256, 0, s>>>(c->d_detail, c->dlay, br.rb, ix, pv, sink, cols);
-    SparseRec *d_ev = (SparseRec *)c->d_tasks; // the SA task list is idle now
-    const uint32_t ev_cap = (uint32_t)std::min<uint64_t>((uint64_t)c->task_cap * sizeof(uint2) / sizeof(SparseRec), 0x7fffffffu);
-    if (paired) k_prof_disc<<<(n / 2 + 255) / 256, 256, 0, s>>>(c->d_detail, c->dlay, n / 2, br.read_base / 2, d_ev, c->d_cnt + CNT_RESCUE, ev_cap);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_cnt, c->d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t n_sp = c->h_cnt[CNT_TASKS], n_ev = c->h_cnt[CNT_RESCUE];
-    if (n_sp > c->sparse_cap || n_ev > ev_cap) return fail(MCX_ERR_CAPACITY, "profile: sparse record list overflow");
-    if (c->h_cnt[CNT_UNSUP]) return fail(MCX_ERR_UNSUPPORTED, "an insertion or deletion of more than 255 bases in an alignment: its string does not fit a tally record");
-    // the records stay in HBM until somebody asks for them (mcx_profile_sparse*)
-    const auto t_app = std::chrono::steady_clock::now();
-    if (int rc = archive_append(c, c->arch, c->d_sparse, n_sp)) return rc;
-    const int rc_ev = archive_append(c, c->arch_ev, d_ev, n_ev);
-    if (c->kn.timing) fprintf(stderr, "[mcx profile] %u tally records, %u events, %u listed fragments; archives %.2f ms\n", n_sp, n_ev, c->h_cnt[CNT_RTASK],
-                                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_app).count());
-    return rc_ev;
-}
-
-// the planes kept as differences become counts (mcx_profile.h): once per run, after its last batch
-extern "C" int mcx_profile_settle(mcx_ctx *c)
-{
-    if (!c) return fail(MCX_ERR_ARG, "mcx_profile_settle: null argument");
-    if (c->prof_broken) return fail(MCX_ERR_DEVICE, "an earlier mcx_profile_settle failed half way: the planes are neither differences nor counts; attach the profile again");
-    if (!c->prof_planes || c->prof_settled) return 0;
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (int rc = profile_collect(c)) return rc; // (the last batch's bookkeeping)
-    hipStream_t s = c->stream;
-    const IndexView &ix = c->idx->view;
-    const size_t G = (size_t)ix.G;
-    const PlanesView pl = planes_view(c->prof_planes, ix.G);
-    size_t tb = 0, tb16 = 0;
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, pl.multi, pl.multi, G, s));
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb16, c->d_prof_match, c->d_prof_match, G, s));
-    tb = std::max(tb, tb16);
-    void *tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, tb + 256)); // (nothing touched yet: a retry is safe)
-    hipError_t e = hipcub::DeviceScan::InclusiveSum(tmp, tb, pl.multi, pl.multi, G, s);
-    // the 16-bit difference planes: their words back to two differences each (mcx_planes.h), then the scan modulo 2^16
-    uint16_t *diffs[5] = {pl.h(kPlF1), pl.h(kPlR2), pl.h(kPlF2), pl.h(kPlR1), c->d_prof_match};
-    for (int k = 0; k < 5 && e == hipSuccess; k++) {
-        k_prof_decode<<<8192, 256, 0, s>>>((uint32_t *)diffs[k], pl.stride / 2);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(tmp, tb, diffs[k], diffs[k], G, s);
-    }
-    if (e == hipSuccess) {
-        ProfView pv; pv.pl = pl; pv.match = c->d_prof_match; pv.G = ix.G; pv.max_dup = c->prof_max_dup; pv.max_clip = c->prof_max_clip;
-        k_prof_fold<<<8192, 256, 0, s>>>(ix, pv);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) { c->prof_broken = c->prof_settled = true; HIP_TRY(e); } // (a second settle must not scan the scanned planes again)
-    (void)hipFree(c->d_prof_match); c->d_prof_match = nullptr; // (6 GB at 3.1 Gbp: the variant caller's scans want the room)
-    c->prof_settled = true;
-    return 0;
-}
-
-extern "C" int mcx_profile_finalize(mcx_ctx *c, uint32_t *d_planes)
-{
-    if (!c || !d_planes) return fail(MCX_ERR_ARG, "mcx_profile_finalize: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (d_planes == c->prof_planes) { if (int rc = mcx_profile_settle(c)) return rc; }
-    k_prof_finalize<<<dim3(4096, kPlanes), 256, 0, c->stream>>>(planes_view(d_planes, c->idx->view.G), c->prof_max_dup);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int mcx_profile_sparse(mcx_ctx *c, const mcx_sparse_rec **recs, uint64_t *n)
-{
-    if (!c || !recs || !n) return fail(MCX_ERR_ARG, "mcx_profile_sparse: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (int rc = sparse_flush(c)) return rc;
-    mcx_disc_resolve(c->h_events.data(), c->h_events.size(), c->idx->view.G, c->h_sparse); // (appended behind the tallies: no second copy of them)
-    *recs = c->h_sparse.data(); *n = c->h_sparse.size();
-    return 0;
-}
-
-extern "C" int mcx_profile_sparse_shard(mcx_ctx *c, const mcx_sparse_rec **recs, uint64_t *n)
-{
-    if (!c || !recs || !n) return fail(MCX_ERR_ARG, "mcx_profile_sparse_shard: null argument");
-    HIP_TRY(hipSetDevice(c->idx->device));
-    if (int rc = sparse_flush(c)) return rc;
-    c->h_sparse.insert(c->h_sparse.end(), c->h_events.begin(), c->h_events.end());
-    *recs = c->h_sparse.data(); *n = c->h_sparse.size();
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4889,82 +3023,13 @@ extern "C" int mcx_bwt_search_batch(mcx_ctx *c, const uint8_t *seqs, const uint3
     HIP_TRY(hipMemcpy(d_seq, seqs, nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_off, seq_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice));
-    k_bwt_search<<<(n + 255) / 256, 256, 0, c->stream>>>(c->idx->view, d_seq, d_off, d_start, n, d_len, d_freq, d_loc);
+    k_bwt_search<<<(n + 255) / 256, 256, 0, c->t0.stream>>>(c->idx->view, d_seq, d_off, d_start, n, d_len, d_freq, d_loc);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->t0.stream));
     HIP_TRY(hipMemcpy(len, d_len, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(freq, d_freq, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(loc, d_loc, (size_t)n * kOccThr * 8, hipMemcpyDeviceToHost));
     (void)hipFree(d_seq); (void)hipFree(d_off); (void)hipFree(d_start); (void)hipFree(d_len); (void)hipFree(d_freq); (void)hipFree(d_loc);
-    return 0;
-}
-
-// stand-alone extension (nw_alignment / ksw2_alignment as a batch): strings come from user buffers
-struct ExtArgs {
-    const uint8_t *q, *t;
-    const uint32_t *q_off, *t_off;
-    uint8_t *ops; int32_t *ops_len, *score;
-    uint32_t n;
-    int use_nw;
-};
-
-template <int K>
-__global__ void __launch_bounds__(64) k_extend(ExtArgs a, uint8_t *scratch, uint64_t stride, int t_lo, int t_hi)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kDpLdsSeq + kDpLdsDir];
-    uint8_t *spill = scratch + (uint64_t)blockIdx.x * stride;
-    const int lane = threadIdx.x;
-    for (uint32_t jb = blockIdx.x; jb < a.n; jb += gridDim.x) {
-        const int m = (int)(a.q_off[jb + 1] - a.q_off[jb]), n = (int)(a.t_off[jb + 1] - a.t_off[jb]);
-        if (n <= t_lo || n > t_hi || m <= 0) continue;
-        const DpBuf b = dp_buffers(m, n, lds, spill);
-        for (int i = lane; i < m; i += 64) b.q[i] = (uint8_t)nt4_code(a.q[a.q_off[jb] + i]);
-        for (int i = lane; i < n; i += 64) b.t[i] = (uint8_t)nt4_code(a.t[a.t_off[jb] + i]);
-        __syncthreads();
-        uint8_t *dst = a.ops + a.q_off[jb] + a.t_off[jb];
-        int score = 0;
-        const int w = dp_core<K, 64, true>(a.use_nw != 0, m, n, b, dst, &score, nullptr, 0u);
-        const int L = m + n - w;
-        for (int base = 0; base < L; base += 64) { // move the string to the front of its area
-            uint8_t v = base + lane < L ? dst[w + base + lane] : 0;
-            __syncthreads();
-            if (base + lane < L) dst[base + lane] = v;
-            __syncthreads();
-        }
-        if (lane == 0) { a.ops_len[jb] = L; a.score[jb] = score; }
-    }
-}
-
-extern "C" int mcx_extend_batch(mcx_ctx *c, int alg, const uint8_t *q, const uint32_t *q_off, const uint8_t *t,
-                                const uint32_t *t_off, uint32_t n, uint8_t *ops, int32_t *ops_len, int32_t *score)
-{
-    if (!c || !q || !q_off || !t || !t_off || !ops || !ops_len || !score) return fail(MCX_ERR_ARG, "mcx_extend_batch: null argument");
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(c->idx->device));
-    for (uint32_t i = 0; i < n; i++) {
-        if (t_off[i + 1] - t_off[i] > 1024 || q_off[i + 1] - q_off[i] > 2048 || t_off[i + 1] == t_off[i] || q_off[i + 1] == q_off[i])
-            return fail(MCX_ERR_UNSUPPORTED, "mcx_extend_batch: fragments must be 1..2048 (read) x 1..1024 (genome)");
-    }
-    ExtArgs a; a.n = n; a.use_nw = alg == 0;
-    uint8_t *d_q = nullptr, *d_t = nullptr, *d_ops = nullptr; uint32_t *d_qo = nullptr, *d_to = nullptr; int32_t *d_len = nullptr, *d_sc = nullptr;
-    const size_t nq = q_off[n], nt = t_off[n];
-    int rc = 0;
-    if ((rc = dmalloc(&d_q, nq + 16)) || (rc = dmalloc(&d_t, nt + 16)) || (rc = dmalloc(&d_ops, nq + nt + 16)) ||
-        (rc = dmalloc(&d_qo, (size_t)n + 1)) || (rc = dmalloc(&d_to, (size_t)n + 1)) || (rc = dmalloc(&d_len, n)) || (rc = dmalloc(&d_sc, n))) return rc;
-    HIP_TRY(hipMemcpy(d_q, q, nq, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_t, t, nt, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_qo, q_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_to, t_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
-    a.q = d_q; a.t = d_t; a.q_off = d_qo; a.t_off = d_to; a.ops = d_ops; a.ops_len = d_len; a.score = d_sc;
-    k_extend<1><<<c->dp_blocks[0], 64, 0, c->stream>>>(a, c->d_dp_scratch[0], c->dp_stride[0], 0, 64);
-    k_extend<4><<<c->dp_blocks[1], 64, 0, c->stream>>>(a, c->d_dp_scratch[1], c->dp_stride[1], 64, 256);
-    k_extend<16><<<c->dp_blocks[2], 64, 0, c->stream>>>(a, c->d_dp_scratch[2], c->dp_stride[2], 256, 1024);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(ops, d_ops, nq + nt, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ops_len, d_len, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(score, d_sc, (size_t)n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d_q); (void)hipFree(d_t); (void)hipFree(d_ops); (void)hipFree(d_qo); (void)hipFree(d_to); (void)hipFree(d_len); (void)hipFree(d_sc);
     return 0;
 }
 
@@ -4984,6 +3049,6 @@ bool mcx_ctx_has_profile(const mcx_ctx *c) { return c->prof_planes != nullptr; }
 uint64_t mcx_ctx_max_reads(const mcx_ctx *c) { return c->max_reads; }
 void **mcx_ctx_files_slot(mcx_ctx *c, void (*drop)(void *)) { c->files_drop = drop; return &c->files_state; }
 void **mcx_ctx_sam_slot(mcx_ctx *c, void (*drop)(void *)) { c->sam_drop = drop; return &c->sam_state; }
-void *mcx_ctx_stream(mcx_ctx *c) { return (void *)c->stream; }
+void *mcx_ctx_stream(mcx_ctx *c) { return (void *)c->t0.stream; }
 void *mcx_pinned_alloc(size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess ? p : nullptr; }
 void mcx_pinned_free(void *p) { if (p) (void)hipHostFree(p); }

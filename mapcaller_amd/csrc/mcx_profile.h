@@ -22,6 +22,9 @@
 // position, in input order (AlignmentProfile.cpp:76-77) — is decided before accumulation by
 // sorting (start, read index) keys.  Insert / delete strings and break points are sparse
 // records appended to a list that the host folds into maps.
+//
+// This header keeps the types and the device functions (k_simple and k_finish write the detail records they read); the kernels
+// and their host side are mcx_profile.hip.
 #ifndef MCX_PROFILE_H
 #define MCX_PROFILE_H
 #include "mcx_glue.h"
@@ -79,76 +82,6 @@ static __device__ __forceinline__ void wave_sparse_flush(const WaveSparse &w, co
 static __device__ __forceinline__ const DetailHdr &detail_hdr(const uint8_t *detail, const DetailLayout &dl, uint32_t r)
 {
     return *(const DetailHdr *)(detail + (uint64_t)r * dl.stride);
-}
-
-// pass 1: break points, clip gate, and the (start position, read) key of every read that reaches
-// the duplicate check (AlignmentProfile.cpp:53-77); n_valid counts them (the others get ~0 and sort last)
-__global__ void k_prof_keys(const uint8_t *detail, DetailLayout dl, ReadBatch rb, IndexView ix, ProfView pv, SparseSink sink,
-                            uint64_t *keys, uint32_t *n_valid)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t key = ~0ull;
-    if (r < rb.n_reads) {
-        const uint8_t *rec = detail + (uint64_t)r * dl.stride;
-        const DetailHdr &d = *(const DetailHdr *)rec;
-        if (d.type == 1) {
-            const Frag *f = (const Frag *)(rec + sizeof(DetailHdr)) + d.frag0;
-            const Frag &a = f[0], &b = f[d.n_frags - 1];
-            const int rlen = (int)(rb.off[r + 1] - rb.off[r]);
-            bool go = true;
-            if (a.rLen == 0 && a.gLen == 0) {
-                if (a.rPos > 20) { SparseRec s; s.pos = a.gPos < ix.G ? a.gPos : ix.G2 - 1 - a.gPos; s.type = 'B'; s.len = 0; sparse_put(sink, s); }
-                if (a.rPos > pv.max_clip) go = false;
-            }
-            if (go && b.rLen == 0 && b.gLen == 0) {
-                if (rlen - b.rPos > 20) { SparseRec s; s.pos = b.gPos < ix.G ? b.gPos : ix.G2 - 1 - b.gPos; s.type = 'B'; s.len = 0; sparse_put(sink, s); }
-                if (rlen - b.rPos > pv.max_clip) go = false;
-            }
-            if (go) {
-                const int64_t g = d.fwd ? a.gPos : ix.G2 - (a.gPos + a.gLen);
-                key = ((uint64_t)g << 32) | r;
-            }
-        }
-        keys[r] = key;
-    }
-    const uint64_t m = __ballot(key != ~0ull);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_valid, (uint32_t)__popcll(m));
-}
-
-// pass 2 (keys sorted by (start position, read number in input order), the reads of every shard of the
-// round among them): a read is admitted when fewer than max_dup reads were admitted at its start position
-// before it — earlier rounds (readCount plane) plus earlier reads of this round.  Only the reads
-// [own_lo, own_lo + n_own) are this shard's: their flags are written.
-// (n_dev: the number of keys where the host has not looked at it — a batch's bookkeeping queued behind its mapping; the grid then covers the batch's reads)
-__global__ void k_prof_admit(const uint64_t *keys, uint64_t n, ProfView pv, uint8_t *admit, uint32_t own_lo, uint32_t n_own, const uint32_t *n_dev = nullptr)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n_dev) n = *n_dev;
-    if (j >= n) return;
-    const uint64_t key = keys[j];
-    const uint32_t idx = (uint32_t)key - own_lo;
-    if (idx >= n_own) return;
-    const uint64_t g = key >> 32;
-    int rank = 0;
-    for (int k = 1; k <= pv.max_dup && (uint64_t)k <= j; k++) { if ((keys[j - k] >> 32) == g) rank++; else break; }
-    const uint32_t before = pv.pl.h(kPlReadCount)[g];
-    admit[idx] = (uint8_t)((admit[idx] & 2) | ((before + (uint32_t)rank < (uint32_t)pv.max_dup) ? 1 : 0)); // (bit 1: k_pack_reads')
-}
-
-// pass 2b (after every flag is out): the first key of each start position adds the round's admissions to
-// readCount — the count of the whole run, the same on every shard (`readCount < iMaxDuplicate` then ++, :76-77)
-__global__ void k_prof_count(const uint64_t *keys, uint64_t n, ProfView pv, const uint32_t *n_dev = nullptr)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n_dev) n = *n_dev;
-    if (j >= n) return;
-    const uint64_t g = keys[j] >> 32;
-    if (j > 0 && (keys[j - 1] >> 32) == g) return;
-    uint32_t run = 1;
-    while (run < (uint32_t)pv.max_dup && j + run < n && (keys[j + run] >> 32) == g) run++;
-    uint16_t *cnt = &pv.pl.h(kPlReadCount)[g]; // (a 16-bit store: the neighbouring position's half of the word is another thread's)
-    const uint32_t v = (uint32_t)*cnt + run;
-    *cnt = (uint16_t)(v < (uint32_t)pv.max_dup ? v : (uint32_t)pv.max_dup);
 }
 
 // the character the reference sees at alignment-string index xi of a fragment's read string
@@ -288,87 +221,6 @@ static __device__ __forceinline__ void prof_read(const uint8_t *detail, const De
             else here = true;
         }
         if (here) prof_walk<1>(rd, f, fwd, rec + dl.off_ops, ix, pv, sink, ws, 0, 0);
-    }
-}
-
-// (the reads in the order of their sorted start keys instead — the lanes of a wavefront then add to neighbouring stretches of the planes —
-//  was measured in round 5: 30.38 against 30.46 ms per batch; the kernel is bound by the lines its atomics open, ~24 G line fills and
-//  write-backs a second, wherever they lie)
-__global__ void __launch_bounds__(256) k_prof_accum(const uint8_t *detail, DetailLayout dl, ReadBatch rb, IndexView ix, ProfView pv,
-                                                    SparseSink sink, const uint8_t *admit, int paired, ColList cols)
-{
-    __shared__ SparseRec s_buf[4][96];
-    __shared__ uint32_t s_cnt[4];
-    WaveSparse ws; ws.buf = s_buf[threadIdx.x >> 6]; ws.cnt = &s_cnt[threadIdx.x >> 6]; ws.cap = 96;
-    if ((threadIdx.x & 63) == 0) *ws.cnt = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    prof_read(detail, dl, rb, ix, pv, sink, ws, admit, paired, cols, r);
-    wave_sparse_flush(ws, sink);
-}
-
-// pass 3b: the listed fragments, one per group of sixteen lanes
-__global__ void __launch_bounds__(256) k_prof_cols(const uint8_t *detail, DetailLayout dl, ReadBatch rb, IndexView ix, ProfView pv,
-                                                   SparseSink sink, ColList cols)
-{
-    __shared__ SparseRec s_buf[4][64];
-    __shared__ uint32_t s_cnt[4];
-    WaveSparse ws; ws.buf = s_buf[threadIdx.x >> 6]; ws.cnt = &s_cnt[threadIdx.x >> 6]; ws.cap = 64;
-    if ((threadIdx.x & 63) == 0) *ws.cnt = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-    const uint32_t n = *cols.n < cols.cap ? *cols.n : cols.cap;
-    const uint32_t group = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, n_groups = (gridDim.x * blockDim.x) >> 4;
-    const int me = threadIdx.x & 15, grp_shift = threadIdx.x & 48;
-    const uint32_t first = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 4; // (the wavefront's first group: its lanes leave the loop together)
-    for (uint32_t k0 = first; k0 < n; k0 += n_groups) {
-        const uint32_t k = k0 + (group - first);
-        if (k < n) {
-            const ColItem it = cols.items[k];
-            ReadRef rd;
-            rd.ascii = rb.bases + it.off; rd.rlen = it.rlen; rd.flipped = (it.flags & 2) ? 1 : 0;
-            prof_walk<16>(rd, it.f, (it.flags & 1) != 0, detail + (uint64_t)it.read * dl.stride + dl.off_ops, ix, pv, sink, ws, me, grp_shift);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (*ws.cnt >= ws.cap / 2) wave_sparse_flush(ws, sink);
-    }
-    wave_sparse_flush(ws, sink);
-}
-
-// mcx_profile_settle, before the scans: the words of a 16-bit difference plane back to two differences modulo 2^16 (mcx_planes.h)
-__global__ void __launch_bounds__(256) k_prof_decode(uint32_t *words, uint64_t n)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t w = words[i];
-        if (w) words[i] = planes_decode(w);
-    }
-}
-
-// mcx_profile_settle, after the scans: the exact-seed coverage joins the plane of the reference's base
-__global__ void __launch_bounds__(256) k_prof_fold(IndexView ix, ProfView pv)
-{
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pv.G; p += (int64_t)gridDim.x * blockDim.x) {
-        const uint16_t m = pv.match[p];
-        if (m) pv.pl.h(ref_code(ix, p))[p] += m; // (a 16-bit read-modify-write of the thread's own position)
-    }
-}
-
-// field widths of MappingRecord_t, applied once all contributions are in (and, on several GPUs,
-// after the all-reduce): 12-bit saturation, 16-bit wrap, duplicate cap
-__global__ void k_prof_finalize(PlanesView pl, int max_dup)
-{
-    const int k = blockIdx.y; // one plane per grid row: no division per element (the strand planes are 16-bit words already: nothing to do)
-    if (k == kPlMulti) {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pl.G; i += (int64_t)gridDim.x * blockDim.x) { const uint32_t v = pl.multi[i]; if (v > 4095u) pl.multi[i] = 4095u; }
-        return;
-    }
-    if (k > kPlReadCount) return;
-    const uint16_t top = (uint16_t)(k == kPlReadCount ? max_dup : 4095);
-    // two positions per thread: a word of the plane at a time
-    uint32_t *w = (uint32_t *)pl.h(k);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pl.stride / 2; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t v = w[i];
-        const uint32_t lo = v & 0xFFFFu, hi = v >> 16;
-        if (lo > top || hi > top) w[i] = (lo < top ? lo : top) | ((hi < top ? hi : top) << 16);
     }
 }
 
