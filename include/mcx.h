@@ -443,6 +443,37 @@ int mcx_sam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *text, uint64_t cap,
  * batch; *n_bytes their size, MCX_ERR_CAPACITY (nothing written) when cap is smaller. */
 int mcx_sam_header(const mcx_index *, char *out, uint64_t cap, uint64_t *n_bytes);
 
+/* ---- BGZF input inflated on the device -------------------------------------------------------------
+ * bgzip's container is a row of independent gzip members of at most 64 KB of text, each of which says how long it is ('BC' extra
+ * field) and carries the CRC-32 and the length of its text.  An inflater takes the raw deflate streams of many members at once — a
+ * wavefront per member: stored, fixed and dynamic blocks (RFC 1951), the CRC-32 taken on the device as well — and is an object of
+ * its own, with a stream of its own (non-blocking): reader threads use one beside a context that maps.  One host thread per object.
+ * A member: src[src_off .. src_off + src_len) -> dst[dst_off .. dst_off + isize), isize <= 65536, any alignment; behind the last
+ * member's bytes src must be readable for 8 bytes more (src_bytes includes them).  status[i] is an mcx_inflate_status; a member
+ * that fails writes nothing outside its own bytes of dst.  Bytes behind the final block inside src_len are ignored. */
+enum mcx_inflate_status {
+    MCX_INFLATE_OK = 0,
+    MCX_INFLATE_DAMAGED = 1, /* no deflate stream: block type 3, LEN != ~NLEN, an invalid code or set of codes, a distance before the start */
+    MCX_INFLATE_INPUT = 2,   /* the input ran out before the final block ended */
+    MCX_INFLATE_LENGTH = 3,  /* the stream ends short of isize or runs past it */
+    MCX_INFLATE_CRC = 4      /* the text is not the one the CRC-32 was taken of */
+};
+typedef struct mcx_inflater mcx_inflater;
+typedef struct mcx_deflate_member {   /* 32 bytes */
+    uint64_t src_off;  uint64_t dst_off;   /* any alignment */
+    uint32_t src_len, isize, crc32, reserved;
+} mcx_deflate_member;
+/* Capacities of one launch through host buffers (mcx_inflate): compressed bytes, bytes of text, members; 0: defaults (8 MB of text). */
+int  mcx_inflater_create(int device, uint64_t max_src_bytes, uint64_t max_dst_bytes, uint32_t max_members, mcx_inflater **out);
+void mcx_inflater_free(mcx_inflater *);
+/* device pointers; runs on the inflater's own stream and returns when the text is there; 0, or MCX_ERR_IO when any member failed (d_status says which).
+ * MCX_ERR_ARG before any launch: a member outside src_bytes (its 8 bytes of slack included) or dst_cap, isize > 65536, n > max_members. */
+int  mcx_inflate_dev(mcx_inflater *, const uint8_t *d_src, uint64_t src_bytes, const mcx_deflate_member *d_members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap, uint32_t *d_status);
+/* host buffers, staged through the object's page-locked buffers, in as many launches as its capacities require (no slack needed behind src) */
+int  mcx_inflate(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *dst, uint64_t dst_cap, uint32_t *status);
+/* the BGZF reader by itself, the twin of mcx_gz_inflate: whole length of the text, -1 unreadable / first bytes are no BGZF member, -2 a damaged member (*n_out: bytes delivered before it) */
+int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t cap, uint64_t *n_out);
+
 /* ---- files: MapCaller -i <prefix> -f A [-f2 B] -alg nw|ksw2 -sam out (src/main.cpp:212-321) */
 int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_path, mcx_stats *stats);
 /* The same with the remaining switches of the reference's file loop (src/ReadMapping.cpp:689-760):
@@ -458,13 +489,17 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * of the whole input).
  * device_sam (mapcaller-mi355x -gpu_sam): the names and NUL-padded qualities of a batch part follow its reads to HBM, the part's text is
  * made there from the records, the CIGAR pool and the -m extras still in the slot, and comes back as text for the one writer; the
- * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then. */
+ * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then.
+ * device_inflate (mapcaller-mi355x -gpu_inflate): a read file that is BGZF is inflated by an mcx_inflater of its own on the context's device, a stretch of
+ * 8 MB of text per call, the next stretch's bytes staged meanwhile; the reader's pool of inflate threads is not created.  Same reads, same end of
+ * the input at a damaged member.  Ordinary .gz, plain files and FASTA are read as before. */
 typedef struct mcx_file_opts {
     int32_t interleaved_pairs, host_threads, append_sam;
     int32_t device_sam; /* 1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
     int64_t *avg_state; /* int64_t[4], see mcx_avg_init */
     int32_t shard_rank, shard_count; /* 0, 0: the whole input */
-    const char *reserved1;
+    int32_t device_inflate; /* 1: BGZF input is inflated and CRC-checked on the device (mcx_inflate's kernel) instead of by a pool of host threads; 0: as before */
+    int32_t reserved2;
     const mcx_exchange *exchange;    /* required when shard_count > 1: the shards walk ONE insert-size trajectory and
                                         decide the duplicate cap over ONE input order, so that SAM and profile equal the
                                         single-stream run's (rank/size must equal shard_rank/shard_count) */

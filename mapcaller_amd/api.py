@@ -70,6 +70,7 @@ SYMBOLS = [
     "mcx_stream_map32", "mcx_stream_mapped32",
     "mcx_ctx_set_multi", "mcx_multi_lines", "mcx_multi_copy", "mcx_stream_multi",
     "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
+    "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -237,9 +238,9 @@ def dist_exchange(device=None) -> Exchange:
 
 
 class FileOpts(C.Structure):
-    """mcx_file_opts: -p, -t, library append, -gpu_sam, insert-size state across libraries, sharding."""
+    """mcx_file_opts: -p, -t, library append, -gpu_sam, insert-size state across libraries, sharding, -gpu_inflate."""
     _fields_ = [("interleaved_pairs", C.c_int32), ("host_threads", C.c_int32), ("append_sam", C.c_int32), ("device_sam", C.c_int32),
-                ("avg_state", C.POINTER(C.c_int64)), ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("reserved1", C.c_char_p),
+                ("avg_state", C.POINTER(C.c_int64)), ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("device_inflate", C.c_int32), ("reserved2", C.c_int32),
                 ("exchange", C.POINTER(Exchange))]
 
 
@@ -249,7 +250,10 @@ class SamIn(C.Structure):
                [("n_reads", C.c_uint32), ("paired", C.c_int32)]
 
 
+ERR_IO, ERR_ARG = -1, -2  # MCX_ERR_IO, MCX_ERR_ARG
 ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
+# mcx_deflate_member: one BGZF member's raw deflate stream src[src_off:][:src_len] -> dst[dst_off:][:isize], with the CRC-32 of its text
+MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 
 
 class VcfOpts(C.Structure):
@@ -363,6 +367,17 @@ def lib() -> C.CDLL:
         f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_sam_header.restype = C.c_int
     L.mcx_sam_header.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_inflater_create.restype = C.c_int
+    L.mcx_inflater_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mcx_inflater_free.restype = None
+    L.mcx_inflater_free.argtypes = [C.c_void_p]
+    for f in (L.mcx_inflate_dev, L.mcx_inflate):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.mcx_inflate_last_ms.restype = C.c_int
+    L.mcx_inflate_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_bgzf_inflate.restype = C.c_int64
+    L.mcx_bgzf_inflate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -529,20 +544,22 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
         final place in ``sam`` (the same path on every shard; shard 0 creates it).  The insert-size state
         (self.avg) carries over from call to call like the reference's globals (a new library starts a
         new 200-read chunk); ``append_sam``: a further library of the same run; ``device_sam`` = -gpu_sam: the
-        SAM text is made on the device (the same bytes)."""
+        SAM text is made on the device (the same bytes); ``device_inflate`` = -gpu_inflate: read files that are BGZF are inflated on the
+        device (the same reads; other input is read as before)."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
         fo.device_sam = int(device_sam)
+        fo.device_inflate = int(device_inflate)
         if self.avg[3] % 200:
             self.avg[3] += 200 - self.avg[3] % 200
         fo.avg_state = C.cast(self.avg, C.POINTER(C.c_int64))
@@ -842,6 +859,58 @@ class Mapper:
             self.close()
         except Exception:
             pass
+
+
+class Inflater:
+    """mcx_inflater: BGZF members (raw deflate streams of at most 64 KB of text each) inflated and CRC-checked on the device, a wavefront per
+    member, on a stream of the object's own.  The capacities are those of one launch through host buffers (0: defaults, 8 MB of text)."""
+
+    def __init__(self, device: int = 0, max_src_bytes: int = 0, max_dst_bytes: int = 0, max_members: int = 0):
+        self._h = C.c_void_p()
+        _check(lib().mcx_inflater_create(device, max_src_bytes, max_dst_bytes, max_members, C.byref(self._h)), "mcx_inflater_create")
+
+    def close(self):
+        if self._h:
+            lib().mcx_inflater_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def inflate_dev(self, d_src, d_members, n: int, d_dst, d_status) -> int:
+        """mcx_inflate_dev on torch tensors of the inflater's device: d_src uint8, d_members n records of MEMBER_DTYPE as bytes, d_dst uint8,
+        d_status n 32-bit words (mcx_inflate_status).  Returns 0, ERR_IO when a member failed, ERR_ARG for members that break the contract."""
+        rc = lib().mcx_inflate_dev(self._h, d_src.data_ptr(), d_src.numel(), d_members.data_ptr(), n, d_dst.data_ptr(), d_dst.numel(), d_status.data_ptr())
+        if rc not in (0, ERR_IO, ERR_ARG):
+            _check(rc, "mcx_inflate_dev")
+        return rc
+
+    def inflate(self, src, members: np.ndarray, dst: np.ndarray):
+        """mcx_inflate on host buffers: src bytes, members of MEMBER_DTYPE, dst uint8 (written in place).  Returns (rc, status words)."""
+        src = np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src
+        members = np.ascontiguousarray(members, dtype=MEMBER_DTYPE)
+        status = np.zeros(members.size, dtype=np.uint32)
+        rc = lib().mcx_inflate(self._h, src.ctypes.data, src.size, members.ctypes.data, members.size, dst.ctypes.data, dst.size, status.ctypes.data)
+        if rc not in (0, ERR_IO, ERR_ARG):
+            _check(rc, "mcx_inflate")
+        return rc, status
+
+    def last_ms(self) -> float:
+        """the last inflate_dev's kernel, in ms by events on the inflater's stream"""
+        ms = C.c_float()
+        _check(lib().mcx_inflate_last_ms(self._h, C.byref(ms)), "mcx_inflate_last_ms")
+        return float(ms.value)
+
+
+def bgzf_inflate(path: str, device: int = 0, cap: int = 0):
+    """mcx_bgzf_inflate: (the text's whole length | -1 no BGZF file | -2 a damaged member, the first min(cap, delivered) bytes of the text)."""
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_uint64()
+    total = int(lib().mcx_bgzf_inflate(path.encode(), device, out.ctypes.data, cap, C.byref(n)))
+    return total, out[:min(cap, n.value)].tobytes()
 
 
 def _pool_of(aln: np.ndarray, cigars):

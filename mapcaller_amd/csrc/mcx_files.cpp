@@ -331,16 +331,35 @@ private:
     uint64_t lines_ = 0;
 };
 
+// a BGZF member at p (n bytes left in the file): its whole size and the length of its extra field; 0 if it is not one
+size_t bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen)
+{
+    if (n < 28 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
+    xlen = (size_t)p[10] | ((size_t)p[11] << 8);
+    if (12 + xlen + 8 > n) return 0;
+    for (size_t o = 12; o + 4 <= 12 + xlen;) { // the subfields of the extra field: SI1 SI2 SLEN(2) data
+        const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
+        if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
+            const size_t size = ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1;
+            return (size >= 12 + xlen + 8 && size <= n) ? size : 0;
+        }
+        o += 4 + slen;
+    }
+    return 0;
+}
+
 // The sequential reader: .gz through zlib, FASTA (multi-line records).
 class Parser {
 public:
-    bool open(const std::string &path, std::string &err)
+    // inflate_device >= 0: a BGZF file is inflated on that device (mcx_inflate.hip) instead of by a pool of host threads; any other input is read as before
+    bool open(const std::string &path, std::string &err, int inflate_device = -1)
     {
         gz_mode_ = path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0; // ReadMapping.cpp:709
         for (int k = 0; k < 4; k++) { std::unique_ptr<Block> b(new Block); b->d.resize(kHead + kBlockBytes); free_.push(std::move(b)); } // (one with the feeder, one with the splitter, two on their way)
         if (gz_mode_ && map_bgzf(path)) {
             // BGZF (bgzip, samtools): a gzip file made of independent members of at most 64 KB, each saying how long it is — the
-            // members of a stretch are inflated side by side by a few threads
+            // members of a stretch are inflated side by side by a few threads — or, with -gpu_inflate, by a wavefront each on the device
+            if (inflate_device >= 0 && mcx_inflater_create(inflate_device, 0, 0, 0, &inflater_) != 0) { err = std::string("-gpu_inflate: ") + mcx_last_error(); return false; }
             feeder_ = std::thread([this] { feed_bgzf(); });
         } else if (gz_mode_ && !getenv("MCX_GZ_SERIAL") && map_gz(path)) {
             // an ordinary gzip stream (what real FASTQ comes as): no entry points, so block starts are searched for and the stretches between them
@@ -376,6 +395,7 @@ public:
             feeder_.join();
         }
         if (gz_) gzclose(gz_);
+        if (inflater_) mcx_inflater_free(inflater_); // (waits for what is still on the device: it reads the staging buffers, not the file)
         if (map_) munmap((void *)map_, map_size_);
     }
     bool fastq() const { return fastq_; }
@@ -413,24 +433,10 @@ private:
     std::thread feeder_;
     std::atomic<bool> stop_{false};
     const uint8_t *map_ = nullptr; // a BGZF file, mapped
+    mcx_inflater *inflater_ = nullptr; // -gpu_inflate: the file's members are inflated on the device
     size_t map_size_ = 0;
 
-    // a BGZF member at p (n bytes left in the file): its whole size and the length of its extra field; 0 if it is not one
-    static size_t bgzf_member(const uint8_t *p, size_t n, size_t &xlen)
-    {
-        if (n < 28 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-        xlen = (size_t)p[10] | ((size_t)p[11] << 8);
-        if (12 + xlen + 8 > n) return 0;
-        for (size_t o = 12; o + 4 <= 12 + xlen;) { // the subfields of the extra field: SI1 SI2 SLEN(2) data
-            const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
-            if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
-                const size_t size = ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1;
-                return (size >= 12 + xlen + 8 && size <= n) ? size : 0;
-            }
-            o += 4 + slen;
-        }
-        return 0;
-    }
+    static size_t bgzf_member(const uint8_t *p, size_t n, size_t &xlen) { return bgzf_member_at(p, n, xlen); }
     bool map_bgzf(const std::string &path)
     {
         const int fd = ::open(path.c_str(), O_RDONLY);
@@ -494,17 +500,14 @@ private:
     }
     void feed_bgzf()
     {
-        Pool pool((int)std::max(2u, std::min(8u, mcx_usable_cpus() / 2)));
         struct Task { const uint8_t *src; uint32_t clen, isize, crc; size_t dst; };
         std::vector<Task> tasks;
         size_t o = 0;
-        std::atomic<int> bad(0);
         bool last = false; // what follows is not a BGZF member: the input ends there, as it does where gzread gives up
-        while (o < map_size_ && !stop_.load() && !bad.load() && !last) {
-            std::unique_ptr<Block> b = free_.pop();
+        auto walk = [&](size_t &total) { // as many members as a block of the pipe holds
             tasks.clear();
-            size_t total = 0;
-            while (o < map_size_) { // as many members as a block of the pipe holds
+            total = 0;
+            while (o < map_size_) {
                 size_t xlen = 0;
                 const uint8_t *p = map_ + o;
                 const size_t size = bgzf_member(p, map_size_ - o, xlen);
@@ -517,6 +520,14 @@ private:
                 tasks.push_back(t);
                 total += isize; o += size;
             }
+        };
+        if (inflater_) { feed_bgzf_device(walk, tasks, o, last); return; }
+        Pool pool((int)std::max(2u, std::min(8u, mcx_usable_cpus() / 2)));
+        std::atomic<int> bad(0);
+        while (o < map_size_ && !stop_.load() && !bad.load() && !last) {
+            std::unique_ptr<Block> b = free_.pop();
+            size_t total = 0;
+            walk(total);
             char *out = b->text();
             pool.run((int)tasks.size(), [&](int k) {
                 const Task &t = tasks[(size_t)k];
@@ -539,6 +550,62 @@ private:
             if (end) return;
         }
         std::unique_ptr<Block> b = free_.pop(); // the end of the input
+        b->n = 0;
+        ready_.push(std::move(b));
+    }
+    // The same stretches with the zlib calls replaced: a stretch's compressed bytes go to the inflater's page-locked staging and on to the device (one launch;
+    // more only when a stretch holds more members or bytes than a launch does), its text comes back into the block.  The next stretch is walked and staged while
+    // this one is on the device.  A stretch with a member that failed is not handed on and the input ends there: the host path's consequence.
+    template <class Walk, class Tasks> void feed_bgzf_device(Walk &walk, Tasks &tasks, size_t &o, bool &last)
+    {
+        uint64_t max_src = 0, max_dst = 0; uint32_t max_members = 0;
+        mcx_inflater_caps(inflater_, &max_src, &max_dst, &max_members);
+        struct Launch { size_t total; bool closes; }; // a launch on the device: its stretch's bytes of text, and whether it is the stretch's last
+        std::deque<Launch> flying;
+        std::vector<mcx_deflate_member> members;
+        std::unique_ptr<Block> b; // the block of the stretch whose launches are being collected
+        bool bad = false;
+        auto collect = [&]() -> bool { // the oldest launch; false: the input has ended
+            if (!b) b = free_.pop();
+            if (mcx_inflate_end(inflater_, (uint8_t *)b->text(), nullptr, nullptr) != 0) bad = true;
+            const Launch l = flying.front();
+            flying.pop_front();
+            if (!l.closes) return true;
+            const size_t total = bad ? 0 : l.total; // (a damaged stretch is not handed on)
+            b->n = total;
+            b->look_for_nul();
+            ready_.push(std::move(b));
+            return total != 0;
+        };
+        while (o < map_size_ && !stop_.load() && !last) {
+            size_t total = 0;
+            walk(total);
+            if (total == 0) { if (!last && o < map_size_) continue; break; } // (empty members in the middle of a file; else the end)
+            members.clear();
+            for (const auto &t : tasks) {
+                if (t.isize == 0) continue; // (the empty member that ends a BGZF file)
+                mcx_deflate_member m; memset(&m, 0, sizeof m);
+                m.src_off = (uint64_t)(t.src - map_); m.dst_off = t.dst; m.src_len = t.clen; m.isize = t.isize; m.crc32 = t.crc;
+                members.push_back(m);
+            }
+            for (size_t at = 0; at < members.size();) {
+                size_t k = at;
+                uint64_t so = 0, to = 0;
+                while (k < members.size() && k - at < max_members && so + members[k].src_len <= max_src && to + members[k].isize <= max_dst) { so += members[k].src_len; to += members[k].isize; k++; }
+                while (flying.size() >= 2) if (!collect()) return;
+                if (k == at || mcx_inflate_begin(inflater_, map_, map_size_, members.data() + at, (uint32_t)(k - at), kBlockBytes) != 0) {
+                    fprintf(stderr, "[mcx_map_files] -gpu_inflate: %s\n", k == at ? "a member larger than a launch holds" : mcx_last_error());
+                    while (!flying.empty()) if (!collect()) return;
+                    last = true; // (the input ends here)
+                    break;
+                }
+                flying.push_back(Launch{total, k == members.size()});
+                at = k;
+            }
+            while (flying.size() > 1) if (!collect()) return; // (one launch stays on the device while the next stretch is walked and staged)
+        }
+        while (!flying.empty()) if (!collect()) return;
+        if (!b) b = free_.pop(); // the end of the input
         b->n = 0;
         ready_.push(std::move(b));
     }
@@ -1097,8 +1164,9 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             mf[f].finish();
         }
     } else {
-        if (!ps[0].open(fq1, err)) rc = mcx_set_error(MCX_ERR_IO, err);
-        if (rc == 0 && two && !ps[1].open(fq2, err)) rc = mcx_set_error(MCX_ERR_IO, err);
+        const int inflate_device = opt.device_inflate ? idx->device : -1; // -gpu_inflate: BGZF files are inflated on the context's device
+        if (!ps[0].open(fq1, err, inflate_device)) rc = mcx_set_error(MCX_ERR_IO, err);
+        if (rc == 0 && two && !ps[1].open(fq2, err, inflate_device)) rc = mcx_set_error(MCX_ERR_IO, err);
         if (rc == 0 && two && ps[0].fastq() != ps[1].fastq()) rc = mcx_set_error(MCX_ERR_IO, std::string(fq1) + " and " + fq2 + " are with different format");
         if (sharded && (rc = sh.agree(rc))) return rc;
         if (rc) return rc;
@@ -1695,4 +1763,65 @@ extern "C" int64_t mcx_gz_inflate(const char *path, int threads, uint64_t stretc
     }
     munmap(m, (size_t)st.st_size);
     return total;
+}
+
+// The BGZF reader by itself (tests, scripts/bgzf_rate.py): the members of `path` inflated on `device`, a stretch of up to 8 MB of text per call of mcx_inflate;
+// the text goes to out[0 .. cap) as far as it fits.  Returns the text's whole length (what is no member ends the input, as in the file front end), -1 when the
+// file cannot be mapped or does not begin with a BGZF member, -2 when a member is damaged (*n_out: the bytes delivered before its stretch).
+extern "C" int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t cap, uint64_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!path) return -1;
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return -1;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 28) { close(fd); return -1; }
+    const size_t size = (size_t)st.st_size;
+    void *mm = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (mm == MAP_FAILED) return -1;
+    const uint8_t *map = (const uint8_t *)mm;
+    size_t xlen = 0;
+    mcx_inflater *inf = nullptr;
+    if (!bgzf_member_at(map, size, xlen) || mcx_inflater_create(device, 0, 0, 0, &inf) != 0) { munmap(mm, size); return -1; }
+    const uint64_t stretch = 8u << 20;
+    std::vector<mcx_deflate_member> members;
+    std::vector<uint8_t> text;
+    int64_t total = 0;
+    bool bad = false;
+    for (size_t o = 0; o < size && !bad;) {
+        members.clear();
+        uint64_t bytes = 0;
+        bool last = false;
+        while (o < size) {
+            const uint8_t *p = map + o;
+            const size_t msize = bgzf_member_at(p, size - o, xlen);
+            if (!msize) { last = true; break; }
+            const uint32_t isize = (uint32_t)p[msize - 4] | ((uint32_t)p[msize - 3] << 8) | ((uint32_t)p[msize - 2] << 16) | ((uint32_t)p[msize - 1] << 24);
+            const uint32_t crc = (uint32_t)p[msize - 8] | ((uint32_t)p[msize - 7] << 8) | ((uint32_t)p[msize - 6] << 16) | ((uint32_t)p[msize - 5] << 24);
+            if (isize > 65536) { last = true; break; }
+            if (bytes + isize > stretch) break;
+            if (isize) {
+                mcx_deflate_member m; memset(&m, 0, sizeof m);
+                m.src_off = o + 12 + xlen; m.dst_off = bytes; m.src_len = (uint32_t)(msize - 12 - xlen - 8); m.isize = isize; m.crc32 = crc;
+                members.push_back(m);
+            }
+            bytes += isize; o += msize;
+        }
+        if (bytes) {
+            const bool fits = out && (uint64_t)total + bytes <= cap;
+            if (!fits) text.resize(bytes);
+            uint8_t *dst = fits ? out + total : text.data();
+            if (mcx_inflate(inf, map, size, members.data(), (uint32_t)members.size(), dst, bytes, nullptr) != 0) bad = true;
+            else {
+                if (!fits && out && (uint64_t)total < cap) memcpy(out + total, dst, (size_t)(cap - (uint64_t)total));
+                total += (int64_t)bytes;
+            }
+        }
+        if (last) break;
+    }
+    if (n_out) *n_out = (uint64_t)total;
+    mcx_inflater_free(inf);
+    munmap(mm, size);
+    return bad ? -2 : total;
 }
