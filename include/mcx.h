@@ -474,6 +474,59 @@ int  mcx_inflate(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const m
 /* the BGZF reader by itself, the twin of mcx_gz_inflate: whole length of the text, -1 unreadable / first bytes are no BGZF member, -2 a damaged member (*n_out: bytes delivered before it) */
 int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- FASTQ text parsed on the device ---------------------------------------------------------------
+ * Replaces the host reader's parse and pack of plain FASTQ (MappedFastq::parse, header_of and mcx_pack_row; the reference's GetNextEntry,
+ * GetData.cpp:3-20, :32-55) for text that lies in HBM already — what mcx_inflate_dev delivers — and produces exactly the arrays
+ * mcx_map_batch_dev, mcx_sam_in and mcx_stream_submit_packed take.  FASTQ UNDER THE PLAIN RULE ONLY: a line is what getline gives (up to and
+ * including '\n', the text's last line possibly without one); the .gz readers' rule (gzgets with a 1024-byte buffer) and FASTA are not covered.
+ * Record k of a text is its lines 4k .. 4k+3 counted from the text's first byte, whatever they hold: the name by the reference's header rule, rlen =
+ * the sequence line's length less one (its last byte goes, newline or not), the '+' line skipped, q_take = min(quality line with its newline, rlen),
+ * 0 when that line is absent.  A text's records end at the first of: max_records taken (MORE); with final == 0 a record whose four lines do not all
+ * end in '\n' inside the text (MORE); no header line (END); no sequence line or rlen == 0, which is what ends the reference's input (EMPTY);
+ * rlen > max_read_len (TOO_LONG).  The records before a stop count.
+ * A parser is an object of its own like an inflater: one device, a non-blocking stream of its own, scratch in HBM (about 64 bytes per record of
+ * max_records and 4 bytes per 4 KB of text) and page-locked staging for the host form, both growing on demand.  One host thread per object.
+ *   n_records[t], stop[t]   records taken of text t and why no more (an mcx_fastq_stop)
+ *   consumed[t]             offset of the first byte that belongs to no taken record: a streaming caller carries text[consumed ..) over
+ *   n_reads                 n_records[0] for one text, 2 * min(n_records[0], n_records[1]) for two (read 2i is record i of text[0], read 2i+1
+ *                           record i of text[1]); both counts are reported and a mismatch is the caller's to judge
+ *   longest, n_bases, n_name_bytes, n_odd   over the n_reads reads: the longest rlen, the sums of rlen and name_len, the bytes that are not upper-case ACGT
+ * Outputs, each group optional (NULL: not produced):
+ *   recs[t]                 max_records records of text t's capacity; n_records[t] written; offsets into text t
+ *   bases, off, qual        the layout of mcx_map_batch_dev / mcx_sam_in: the reads' bases back to back, n_reads + 1 offsets, and read r's rlen
+ *                           quality bytes at off[r]: q_take bytes, then NUL.  bases and qual 16-byte aligned with room for bases_cap bytes each, off
+ *                           for 2 * max_records + 1 words (max_records + 1 for one text); needs bases_cap >= n_bases + 32 (nothing is written behind
+ *                           n_bases).  qual NULL: bases and off alone.  bases_cap = bytes[0] + bytes[1] + 32 always suffices.
+ *   names, name_off         the names back to back (names_cap >= n_name_bytes) and n_reads + 1 offsets (capacity as off)
+ *   rows, len, odd          the arguments of mcx_stream_submit_packed: row_words words per read (capacity 2 * max_records rows, max_records for one
+ *                           text), the lengths, and the odd bytes in (read, position) order, the same bytes on every run (odd_cap >= n_odd entries)
+ * MCX_ERR_ARG before any launch: a text of 4 GiB or more (the two of a pair together: off[] holds 32-bit offsets), rows with row_words < ceil(max_read_len / 16).  A bases_cap, names_cap or odd_cap that is too
+ * small: MCX_ERR_CAPACITY, info filled with the sizes needed, nothing written to THAT group (the others are complete).  The call runs on the
+ * parser's stream, waits once in the middle (the capacities are judged by the host) and returns when the results are there. */
+typedef struct mcx_fastq_parser mcx_fastq_parser;
+int  mcx_fastq_parser_create(int device, uint64_t max_text_bytes, uint32_t max_records, mcx_fastq_parser **out); /* 0: defaults; grows on demand */
+void mcx_fastq_parser_free(mcx_fastq_parser *);
+
+typedef struct mcx_fastq_rec { uint32_t name, name_len, seq, rlen, qual, q_take; } mcx_fastq_rec; /* 24 bytes; offsets into the record's own text */
+enum mcx_fastq_stop { MCX_FASTQ_MORE = 0, MCX_FASTQ_END = 1, MCX_FASTQ_EMPTY = 2, MCX_FASTQ_TOO_LONG = 3 };
+
+typedef struct mcx_fastq_in {
+    const uint8_t *text[2]; uint64_t bytes[2];  /* text[1] NULL: one file.  Two: read 2i is record i of text[0], read 2i+1 record i of text[1]; each < 4 GiB; any alignment */
+    uint32_t max_records;                       /* per text */
+    int32_t max_read_len;
+    int32_t final;                              /* 0: more text follows, only records whose four lines all end in '\n' inside the text are taken */
+} mcx_fastq_in;
+typedef struct mcx_fastq_out {                  /* any group may be NULL: not produced */
+    mcx_fastq_rec *recs[2];
+    uint8_t *bases; uint32_t *off; uint8_t *qual; uint64_t bases_cap;   /* the layout of mcx_map_batch_dev / mcx_sam_in: 16-byte aligned, bases_cap >= bases + 32 */
+    uint8_t *names; uint32_t *name_off; uint64_t names_cap;
+    uint32_t *rows; uint32_t row_words; uint32_t *len; uint64_t *odd; uint32_t odd_cap;  /* the arguments of mcx_stream_submit_packed */
+} mcx_fastq_out;
+typedef struct mcx_fastq_info { uint32_t n_records[2], stop[2]; uint64_t consumed[2]; uint32_t n_reads, longest, n_odd, pad; uint64_t n_bases, n_name_bytes; } mcx_fastq_info;
+
+int mcx_fastq_parse_dev(mcx_fastq_parser *, const mcx_fastq_in *d_in, const mcx_fastq_out *d_out, mcx_fastq_info *info); /* structs in host memory, pointers in them device pointers */
+int mcx_fastq_parse(mcx_fastq_parser *, const mcx_fastq_in *in, const mcx_fastq_out *out, mcx_fastq_info *info);         /* host buffers, staged inside */
+
 /* ---- files: MapCaller -i <prefix> -f A [-f2 B] -alg nw|ksw2 -sam out (src/main.cpp:212-321) */
 int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_path, mcx_stats *stats);
 /* The same with the remaining switches of the reference's file loop (src/ReadMapping.cpp:689-760):
@@ -492,14 +545,18 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then.
  * device_inflate (mapcaller-mi355x -gpu_inflate): a read file that is BGZF is inflated by an mcx_inflater of its own on the context's device, a stretch of
  * 8 MB of text per call, the next stretch's bytes staged meanwhile; the reader's pool of inflate threads is not created.  Same reads, same end of
- * the input at a damaged member.  Ordinary .gz, plain files and FASTA are read as before. */
+ * the input at a damaged member.  Ordinary .gz, plain files and FASTA are read as before.
+ * device_parse (mapcaller-mi355x -gpu_parse): where the input is plain FASTQ that the front end maps into memory, the byte range of each of this shard's batches goes
+ * through page-locked staging to an mcx_fastq_parser of its own on the context's device — about 0.3 KB of HBM per read of a batch, taken after the context's —, and
+ * records, 2-bit rows, lengths and odd bytes come back: the reader's threads only copy.  Same reads, same end of the input, same error texts.  .gz, BGZF and FASTA
+ * are read as before. */
 typedef struct mcx_file_opts {
     int32_t interleaved_pairs, host_threads, append_sam;
     int32_t device_sam; /* 1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
     int64_t *avg_state; /* int64_t[4], see mcx_avg_init */
     int32_t shard_rank, shard_count; /* 0, 0: the whole input */
     int32_t device_inflate; /* 1: BGZF input is inflated and CRC-checked on the device (mcx_inflate's kernel) instead of by a pool of host threads; 0: as before */
-    int32_t reserved2;
+    int32_t device_parse; /* 1: plain FASTQ input is parsed and packed to 2-bit rows on the device (mcx_fastq_parse's kernels) instead of by the reader's pool of host threads; 0: as before */
     const mcx_exchange *exchange;    /* required when shard_count > 1: the shards walk ONE insert-size trajectory and
                                         decide the duplicate cap over ONE input order, so that SAM and profile equal the
                                         single-stream run's (rank/size must equal shard_rank/shard_count) */

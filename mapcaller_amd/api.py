@@ -71,6 +71,7 @@ SYMBOLS = [
     "mcx_ctx_set_multi", "mcx_multi_lines", "mcx_multi_copy", "mcx_stream_multi",
     "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
     "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
+    "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -238,9 +239,9 @@ def dist_exchange(device=None) -> Exchange:
 
 
 class FileOpts(C.Structure):
-    """mcx_file_opts: -p, -t, library append, -gpu_sam, insert-size state across libraries, sharding, -gpu_inflate."""
+    """mcx_file_opts: -p, -t, library append, -gpu_sam, insert-size state across libraries, sharding, -gpu_inflate, -gpu_parse."""
     _fields_ = [("interleaved_pairs", C.c_int32), ("host_threads", C.c_int32), ("append_sam", C.c_int32), ("device_sam", C.c_int32),
-                ("avg_state", C.POINTER(C.c_int64)), ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("device_inflate", C.c_int32), ("reserved2", C.c_int32),
+                ("avg_state", C.POINTER(C.c_int64)), ("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("device_inflate", C.c_int32), ("device_parse", C.c_int32),
                 ("exchange", C.POINTER(Exchange))]
 
 
@@ -254,6 +255,31 @@ ERR_IO, ERR_ARG = -1, -2  # MCX_ERR_IO, MCX_ERR_ARG
 ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
 # mcx_deflate_member: one BGZF member's raw deflate stream src[src_off:][:src_len] -> dst[dst_off:][:isize], with the CRC-32 of its text
 MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
+# mcx_fastq_rec: one FASTQ record as offsets into its own text; mcx_fastq_stop
+REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
+FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
+
+
+class FastqIn(C.Structure):
+    """mcx_fastq_in (pointers as integers: host or device)"""
+    _fields_ = [("text", C.c_void_p * 2), ("bytes", C.c_uint64 * 2), ("max_records", C.c_uint32), ("max_read_len", C.c_int32), ("final", C.c_int32)]
+
+
+class FastqOut(C.Structure):
+    """mcx_fastq_out (pointers as integers: host or device)"""
+    _fields_ = [("recs", C.c_void_p * 2), ("bases", C.c_void_p), ("off", C.c_void_p), ("qual", C.c_void_p), ("bases_cap", C.c_uint64),
+                ("names", C.c_void_p), ("name_off", C.c_void_p), ("names_cap", C.c_uint64),
+                ("rows", C.c_void_p), ("row_words", C.c_uint32), ("len", C.c_void_p), ("odd", C.c_void_p), ("odd_cap", C.c_uint32)]
+
+
+class FastqInfo(C.Structure):
+    """mcx_fastq_info"""
+    _fields_ = [("n_records", C.c_uint32 * 2), ("stop", C.c_uint32 * 2), ("consumed", C.c_uint64 * 2), ("n_reads", C.c_uint32), ("longest", C.c_uint32),
+                ("n_odd", C.c_uint32), ("pad", C.c_uint32), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"n_records": list(self.n_records), "stop": list(self.stop), "consumed": list(self.consumed), "n_reads": self.n_reads, "longest": self.longest,
+                "n_odd": self.n_odd, "n_bases": self.n_bases, "n_name_bytes": self.n_name_bytes}
 
 
 class VcfOpts(C.Structure):
@@ -374,6 +400,17 @@ def lib() -> C.CDLL:
     for f in (L.mcx_inflate_dev, L.mcx_inflate):
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.mcx_fastq_parser_create.restype = C.c_int
+    L.mcx_fastq_parser_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mcx_fastq_parser_free.restype = None
+    L.mcx_fastq_parser_free.argtypes = [C.c_void_p]
+    for f in (L.mcx_fastq_parse_dev, L.mcx_fastq_parse):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(FastqIn), C.POINTER(FastqOut), C.POINTER(FastqInfo)]
+    L.mcx_fastq_last_ms.restype = C.c_int
+    L.mcx_fastq_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_fastq_grown.restype = C.c_int
+    L.mcx_fastq_grown.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.mcx_inflate_last_ms.restype = C.c_int
     L.mcx_inflate_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_bgzf_inflate.restype = C.c_int64
@@ -544,7 +581,7 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -552,7 +589,8 @@ class Mapper:
         (self.avg) carries over from call to call like the reference's globals (a new library starts a
         new 200-read chunk); ``append_sam``: a further library of the same run; ``device_sam`` = -gpu_sam: the
         SAM text is made on the device (the same bytes); ``device_inflate`` = -gpu_inflate: read files that are BGZF are inflated on the
-        device (the same reads; other input is read as before)."""
+        device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files are parsed and packed to 2-bit rows on
+        the device (the same reads, the same end of the input; other input is read as before)."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
@@ -560,6 +598,7 @@ class Mapper:
         fo.append_sam = int(append_sam)
         fo.device_sam = int(device_sam)
         fo.device_inflate = int(device_inflate)
+        fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
             self.avg[3] += 200 - self.avg[3] % 200
         fo.avg_state = C.cast(self.avg, C.POINTER(C.c_int64))
@@ -903,6 +942,82 @@ class Inflater:
         ms = C.c_float()
         _check(lib().mcx_inflate_last_ms(self._h, C.byref(ms)), "mcx_inflate_last_ms")
         return float(ms.value)
+
+
+class FastqParser:
+    """mcx_fastq_parser: plain FASTQ text parsed on the device — record boundaries, names, bases, NUL-padded qualities, 2-bit rows and the list of
+    bytes that are not ACGT — on a stream of the object's own.  max_text_bytes / max_records size the first scratch (0: defaults); it grows on demand.
+    Both calls take the texts (one, or the two of a pair) and the outputs by keyword: recs (a list, one array of REC_DTYPE records per text), bases,
+    off, qual, names, name_off, rows, len, odd — a group that is left out is not produced.  A capacity defaults to its array's size (bases_cap,
+    names_cap in bytes, odd_cap in entries), row_words to the rows' second dimension and a text's length to its array's size (text_bytes: a list
+    that says otherwise).  They return (rc, info): rc 0, ERR_ARG or ERR_CAPACITY;
+    info a dict of mcx_fastq_info."""
+
+    def __init__(self, device: int = 0, max_text_bytes: int = 0, max_records: int = 0):
+        self._h = C.c_void_p()
+        _check(lib().mcx_fastq_parser_create(device, max_text_bytes, max_records, C.byref(self._h)), "mcx_fastq_parser_create")
+
+    def close(self):
+        if self._h:
+            lib().mcx_fastq_parser_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _structs(ptr, size, texts, max_records, max_read_len, final, o):
+        fi, fo = FastqIn(), FastqOut()
+        text_bytes = o.get("text_bytes")
+        for t, x in enumerate(texts):
+            fi.text[t], fi.bytes[t] = ptr(x), size(x) if text_bytes is None else text_bytes[t]
+        fi.max_records, fi.max_read_len, fi.final = max_records, max_read_len, int(final)
+        for t, x in enumerate(o.get("recs") or []):
+            fo.recs[t] = ptr(x) if x is not None else None
+        for k in ("bases", "off", "qual", "names", "name_off", "rows", "len", "odd"):
+            if o.get(k) is not None:
+                setattr(fo, k, ptr(o[k]))
+        fo.bases_cap = o.get("bases_cap", size(o["bases"]) if o.get("bases") is not None else 0)
+        fo.names_cap = o.get("names_cap", size(o["names"]) if o.get("names") is not None else 0)
+        fo.odd_cap = o.get("odd_cap", size(o["odd"]) if o.get("odd") is not None else 0)
+        fo.row_words = o.get("row_words", o["rows"].shape[1] if o.get("rows") is not None and len(o["rows"].shape) == 2 else 0)
+        return fi, fo
+
+    def _call(self, f, name, fi, fo):
+        info = FastqInfo()
+        rc = f(self._h, C.byref(fi), C.byref(fo), C.byref(info))
+        if rc not in (0, ERR_ARG, ERR_CAPACITY):
+            _check(rc, name)
+        return rc, info.as_dict()
+
+    def parse_dev(self, texts, max_records: int, max_read_len: int, final: bool = True, **out):
+        """mcx_fastq_parse_dev on torch tensors of the parser's device: texts uint8 (any alignment: a slice will do), recs uint8 tensors of 24 bytes a
+        record, off / name_off / rows / len int32, odd int64.  The second text of a pair counts as long as it has an address: give an empty one as an empty
+        slice of a larger tensor."""
+        fi, fo = self._structs(lambda x: x.data_ptr() or None, lambda x: x.numel(), texts, max_records, max_read_len, final, out)
+        return self._call(lib().mcx_fastq_parse_dev, "mcx_fastq_parse_dev", fi, fo)
+
+    def parse(self, texts, max_records: int, max_read_len: int, final: bool = True, **out):
+        """mcx_fastq_parse on host buffers: texts bytes or uint8 arrays, the outputs numpy arrays written in place."""
+        keep = [np.frombuffer(x, dtype=np.uint8) if not isinstance(x, np.ndarray) else x for x in texts]
+        keep = [x if x.size else np.zeros(1, dtype=np.uint8)[:0] for x in keep]
+        fi, fo = self._structs(lambda x: x.ctypes.data, lambda x: x.size, keep, max_records, max_read_len, final, out)
+        return self._call(lib().mcx_fastq_parse, "mcx_fastq_parse", fi, fo)
+
+    def last_ms(self) -> float:
+        """the last parse_dev on the device, in ms by events on the parser's stream"""
+        ms = C.c_float()
+        _check(lib().mcx_fastq_last_ms(self._h, C.byref(ms)), "mcx_fastq_last_ms")
+        return float(ms.value)
+
+    def grown(self) -> int:
+        """how often one of the parser's buffers had to be replaced by a larger one"""
+        n = C.c_uint32()
+        _check(lib().mcx_fastq_grown(self._h, C.byref(n)), "mcx_fastq_grown")
+        return int(n.value)
 
 
 def bgzf_inflate(path: str, device: int = 0, cap: int = 0):

@@ -1141,6 +1141,9 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     Pool fpool(threads);       // format + write (threads of its own: the two stages overlap)
     MappedFastq mf[2];
     Parser ps[2];
+    struct FqFree { void operator()(mcx_fastq_parser *q) const { mcx_fastq_parser_free(q); } };
+    std::unique_ptr<mcx_fastq_parser, FqFree> fq_parser; // -gpu_parse on plain FASTQ
+    struct PinnedRecs { mcx_fastq_rec *p[2] = {nullptr, nullptr}; mcx_fastq_rec *&operator[](int f) { return p[f]; } ~PinnedRecs() { mcx_pinned_free(p[0]); mcx_pinned_free(p[1]); } } fq_recs; // a batch's records as the device hands them out
     bool fastq = true;
     if (mapped_input) {
         for (int f = 0; f < (two ? 2 : 1) && rc == 0; f++) if (!mf[f].open(f ? fq2 : fq1, err)) rc = mcx_set_error(MCX_ERR_IO, err);
@@ -1162,6 +1165,18 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 }
             }
             mf[f].finish();
+        }
+        // -gpu_parse: this shard's batches are parsed and packed by an mcx_fastq_parser of its own on the context's device (its HBM is taken after the context's)
+        if (opt.device_parse) {
+            mcx_fastq_parser *q = nullptr;
+            const uint64_t per = two ? batch_reads / 2 : batch_reads;
+            if (mcx_fastq_parser_create(idx->device, (uint64_t)std::min<uint64_t>(mf[0].bytes(), per * 200 + 65536), (uint32_t)std::min<uint64_t>(per, 0xFFFFFFFFu), &q) != 0)
+                rc = mcx_set_error(MCX_ERR_DEVICE, std::string("-gpu_parse: ") + mcx_last_error());
+            fq_parser.reset(q);
+            for (int f = 0; f < (two ? 2 : 1) && rc == 0; f++)
+                if (!(fq_recs[f] = (mcx_fastq_rec *)mcx_pinned_alloc((size_t)std::max<uint64_t>(per, 1) * sizeof(mcx_fastq_rec)))) rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_parse: cannot allocate pinned host memory");
+            if (sharded && (rc = sh.agree(rc))) return rc;
+            if (rc) return rc;
         }
     } else {
         const int inflate_device = opt.device_inflate ? idx->device : -1; // -gpu_inflate: BGZF files are inflated on the context's device
@@ -1250,7 +1265,71 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             t_p_wait += secs(tw, t0);
             b->two_files = two; b->fastq = fastq; b->n = 0; b->last = false; b->error.clear(); b->number = number;
             b->in[0].clear(); b->in[1].clear(); b->n_odd[0] = b->n_odd[1] = 0; b->n_pair_reads = 0;
-            if (mapped_input) {
+            bool dev_parsed = false;   // -gpu_parse: the batch's records came from the device, and its rows will
+            mcx_fastq_info fq_info;
+            memset(&fq_info, 0, sizeof fq_info);
+            if (mapped_input && fq_parser && mine) {
+                // The byte ranges of records [r0, r1) of each file — from the line index, as above — go to the parser's page-locked staging through the pool and are
+                // parsed as whole texts (final): the same records, the same stops as MappedFastq::parse gives.
+                dev_parsed = true;
+                const uint64_t r0 = number * per_file;
+                const int nf = two ? 2 : 1;
+                uint64_t cnt[2] = {0, 0}, r1[2] = {0, 0}, bytes[2] = {0, 0};
+                size_t p0[2] = {0, 0};
+                for (int f = 0; f < nf; f++) {
+                    b->in[f].base = mf[f].data();
+                    r1[f] = std::min<uint64_t>(r0 + per_file, total_recs[f]);
+                    cnt[f] = r1[f] > r0 ? r1[f] - r0 : 0;
+                    if (cnt[f]) { p0[f] = mf[f].line_start(4 * r0); bytes[f] = mf[f].line_start(4 * r1[f]) - p0[f]; }
+                }
+                std::string perr;
+                uint8_t *h[2] = {nullptr, nullptr};
+                if (bytes[0] + bytes[1]) {
+                    if (mcx_fastq_stage(fq_parser.get(), bytes, h) != 0) perr = std::string("-gpu_parse: ") + mcx_last_error();
+                    else {
+                        const uint64_t piece = 1u << 20, n0 = (bytes[0] + piece - 1) / piece, n1 = (bytes[1] + piece - 1) / piece;
+                        pool.run((int)(n0 + n1), [&](int t) {
+                            const int f = (uint64_t)t < n0 ? 0 : 1;
+                            const uint64_t at = ((uint64_t)t - (f ? n0 : 0)) * piece;
+                            memcpy(h[f] + at, mf[f].data() + p0[f] + at, (size_t)std::min<uint64_t>(piece, bytes[f] - at));
+                        });
+                        mcx_fastq_out recs_only;
+                        memset(&recs_only, 0, sizeof recs_only);
+                        recs_only.recs[0] = fq_recs[0]; recs_only.recs[1] = two ? fq_recs[1] : nullptr;
+                        if (mcx_fastq_staged_sizes(fq_parser.get(), bytes, two ? 1 : 0, (uint32_t)std::max(cnt[0], cnt[1]), max_len, 1, &fq_info) != 0 ||
+                            mcx_fastq_staged_out(fq_parser.get(), &recs_only, &fq_info) != 0) perr = std::string("-gpu_parse: ") + mcx_last_error();
+                    }
+                }
+                for (int f = 0; f < nf; f++) {
+                    View &v = b->in[f];
+                    if (!perr.empty()) { v.error = perr; continue; }
+                    const uint64_t got = std::min<uint64_t>(fq_info.n_records[f], cnt[f]);
+                    const bool stopped = got < cnt[f];
+                    if (!v.recs.resize((size_t)got)) { v.error = "out of memory"; continue; }
+                    const mcx_fastq_rec *src = fq_recs[f];
+                    Rec *dst = v.recs.data();
+                    const uint64_t at = p0[f];
+                    const int slices = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)pool.size(), got / 4096));
+                    pool.run(slices, [&](int k) { // the offsets rebased to the mapped file: the formatter and -gpu_sam's gather read names and qualities where they lie
+                        for (uint64_t i = got * (uint64_t)k / (uint64_t)slices; i < got * (uint64_t)(k + 1) / (uint64_t)slices; i++) {
+                            const mcx_fastq_rec &e = src[i];
+                            Rec rec; memset(&rec, 0, sizeof rec);
+                            rec.name = at + e.name; rec.name_len = e.name_len; rec.seq = at + e.seq; rec.rlen = e.rlen;
+                            rec.qual = e.qual ? at + e.qual : 0; rec.q_take = e.q_take; // (no quality line: offset 0, nothing taken, as the host reader has it)
+                            dst[i] = rec;
+                        }
+                    });
+                    if (stopped && fq_info.stop[f] == MCX_FASTQ_TOO_LONG) { // the name of the read that is too long, by the host's header rule at the first byte that was not taken
+                        const char *l = mf[f].data() + at + fq_info.consumed[f];
+                        const char *e = find_nl(l, mf[f].data() + mf[f].bytes());
+                        const size_t len = e ? (size_t)(e - l) + 1 : (size_t)(mf[f].data() + mf[f].bytes() - l);
+                        int q1, q2;
+                        header_of(l, (int)len, q1, q2);
+                        v.error = "read " + std::string(l + q1, q2 > q1 ? (size_t)(q2 - q1) : 0) + " is longer than max_read_len";
+                    }
+                    v.last = stopped || cnt[f] < per_file || r1[f] >= total_recs[f];
+                }
+            } else if (mapped_input) {
                 // the records of both files in one pass of the pool, every share written where it belongs
                 const uint64_t r0 = number * per_file;
                 const int nf = two ? 2 : 1;
@@ -1320,8 +1399,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 uint32_t npr = paired ? n : 0; // reads mapped as pairs; the odd tail of an interleaved file is mapped read by read
                 if (paired && (n & 1)) npr = n / kReadChunkSize * kReadChunkSize;
                 b->n_pair_reads = npr;
-                uint32_t longest = 0;
-                {
+                uint32_t longest = fq_info.longest;
+                if (!dev_parsed) {
                     const int slices = (int)std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)pool.size(), n / 4096));
                     std::vector<uint32_t> most((size_t)slices, 0);
                     pool.run(slices, [&](int k) {
@@ -1333,7 +1412,23 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 }
                 b->row_words = (longest + 15) / 16;
                 if (!b->reserve(std::max<size_t>(n, batch_reads), std::max<size_t>(b->row_words, ((size_t)max_len + 15) / 16))) b->error = "cannot allocate pinned host memory";
-                else {
+                else if (dev_parsed) {
+                    // rows, lengths and the sorted list of odd bytes straight into the batch's page-locked buffers; the list is split at the first read of the
+                    // single-read part, whose reads are numbered from 0 like a batch of its own
+                    mcx_fastq_out o;
+                    memset(&o, 0, sizeof o);
+                    if (fq_info.n_reads != n) b->error = "-gpu_parse: the device counted " + std::to_string(fq_info.n_reads) + " reads, the reader " + std::to_string(n);
+                    else if (fq_info.n_odd && !b->reserve_odd(fq_info.n_odd)) b->error = "cannot allocate pinned host memory";
+                    else {
+                        o.rows = b->rows; o.row_words = 0; o.len = b->lens; o.odd = b->odd; o.odd_cap = fq_info.n_odd;
+                        if (mcx_fastq_staged_out(fq_parser.get(), &o, &fq_info) != 0) b->error = std::string("-gpu_parse: ") + mcx_last_error();
+                        else {
+                            const uint64_t *cut = std::lower_bound(b->odd, b->odd + fq_info.n_odd, (uint64_t)npr << 32);
+                            b->n_odd[0] = (uint32_t)(cut - b->odd); b->n_odd[1] = fq_info.n_odd - b->n_odd[0];
+                            for (uint64_t *w = b->odd + b->n_odd[0]; w < b->odd + fq_info.n_odd; w++) *w -= (uint64_t)npr << 32;
+                        }
+                    }
+                } else {
                     std::vector<uint64_t> all_odd[2];
                     for (int part = 0; part < 2; part++) { // (a part's reads are numbered from 0: it is a batch of its own on the device)
                         const uint32_t first = part ? npr : 0, cnt = part ? n - npr : npr;

@@ -47,6 +47,12 @@ int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint3
 int mcx_inflate_begin(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint64_t dst_cap);
 int mcx_inflate_end(mcx_inflater *, uint8_t *dst, uint32_t *status, uint32_t *n_bad);
 void mcx_inflater_caps(const mcx_inflater *, uint64_t *max_src, uint64_t *max_dst, uint32_t *max_members);
+// -gpu_parse (mcx_fastq.hip): the host form of mcx_fastq_parse in three steps — stage hands out the parser's page-locked staging for two texts of these sizes
+// (the reader's pool copies the batch's byte ranges into it); staged_sizes sends them to HBM and parses: *info says how many reads, odd bytes, how long the longest;
+// staged_out brings the groups of `out` (HOST pointers, page-locked ones without a further copy) back — rows with row_words 0 come ceil(longest / 16) words wide.
+int mcx_fastq_stage(mcx_fastq_parser *, const uint64_t bytes[2], uint8_t *h[2]);
+int mcx_fastq_staged_sizes(mcx_fastq_parser *, const uint64_t bytes[2], int two, uint32_t max_records, int32_t max_read_len, int32_t final, mcx_fastq_info *info);
+int mcx_fastq_staged_out(mcx_fastq_parser *, const mcx_fastq_out *out, const mcx_fastq_info *info);
 void *mcx_pinned_alloc(size_t bytes); // page-locked host memory (null on failure); mcx_pinned_free accepts null
 void mcx_pinned_free(void *);
 

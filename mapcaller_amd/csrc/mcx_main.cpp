@@ -53,6 +53,7 @@ static void usage(const char *prog)
             "         -m            output multiple alignments: a SAM line for every alignment with the best score\n"
             "         -gpu_sam      make the SAM text on the GPU instead of with host threads (same bytes; nothing without -sam)\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
+            "         -gpu_parse    parse plain FASTQ read files and pack their reads on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "         -gvcf         GVCF mode\n"
             "         -monomorphic  report all loci which do not have any potential alternates\n"
             "         -ploidy INT   number of sets of chromosomes in a cell (1:monoploid, 2:diploid) [2]\n"
@@ -152,6 +153,7 @@ int main(int argc, char **argv)
         else if (p == "-m") multi = true; // bUnique = false, main.cpp:308
         else if (p == "-gpu_sam") fo.device_sam = 1;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
+        else if (p == "-gpu_parse") fo.device_parse = 1;
         else if (p == "-bam") { fprintf(stderr, "Error! %s is not supported by mapcaller-mi355x (DESIGN.md, deliberate deviations)\n", argv[i]); return 1; }
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
     }
