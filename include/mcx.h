@@ -246,6 +246,13 @@ int mcx_stream_submit(mcx_ctx *, const uint8_t *bases, const uint32_t *off, uint
  * mcx_stream_mapped / _mapped32 — by the mcx_stream_collect that hands the batch's records over (the slot is released either way; its records are not results). */
 int mcx_stream_submit_packed(mcx_ctx *, const uint32_t *codes, uint32_t row_words, const uint32_t *len, uint32_t n_reads, const uint64_t *odd,
                              uint32_t n_odd);
+/* The same with the three arrays in HBM already, on the context's device — what mcx_fastq_parse_dev's rows / len / odd are: the copies into the slot are
+ * device-to-device on the slot's copy-in stream, everything behind them (the bytes restored, the lengths checked, the deferred error, mcx_stream_next / _map /
+ * _map32 / _collect, the -m extras) is mcx_stream_submit_packed's.  bytes_in does not count such a batch: nothing of it crossed the device boundary.
+ * The call returns at once.  THE CALLER'S BUFFERS must hold their contents — written and complete when the call is made: the copies do not wait for any
+ * stream of the caller's — until mcx_stream_next / mcx_stream_map / mcx_stream_map32 has handed the batch out. */
+int mcx_stream_submit_dev(mcx_ctx *, const uint32_t *d_codes, uint32_t row_words, const uint32_t *d_len, uint32_t n_reads, const uint64_t *d_odd,
+                          uint32_t n_odd);
 /* One read's row for mcx_stream_submit_packed, the way the file front end makes it (host code, no device involved; sixteen bases at a time where the
  * CPU has BMI2): row[0 .. row_words) written, the read's bytes that are not upper-case ACGT appended to odd[*n_odd ..] as (read << 32 | position << 8 | byte)
  * while *n_odd < odd_cap.  Returns how many such bytes the read holds (more than were room for: the caller's list was too short). */
@@ -477,13 +484,20 @@ int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t ca
 /* ---- FASTQ text parsed on the device ---------------------------------------------------------------
  * Replaces the host reader's parse and pack of plain FASTQ (MappedFastq::parse, header_of and mcx_pack_row; the reference's GetNextEntry,
  * GetData.cpp:3-20, :32-55) for text that lies in HBM already — what mcx_inflate_dev delivers — and produces exactly the arrays
- * mcx_map_batch_dev, mcx_sam_in and mcx_stream_submit_packed take.  FASTQ UNDER THE PLAIN RULE ONLY: a line is what getline gives (up to and
- * including '\n', the text's last line possibly without one); the .gz readers' rule (gzgets with a 1024-byte buffer) and FASTA are not covered.
+ * mcx_map_batch_dev, mcx_sam_in and mcx_stream_submit_packed / mcx_stream_submit_dev take.  FASTQ only (FASTA is not covered), under one of two rules
+ * (mcx_fastq_parser_set_rule).  THE PLAIN RULE, the default: a line is what getline gives (up to and including '\n', the text's last line possibly without one).
  * Record k of a text is its lines 4k .. 4k+3 counted from the text's first byte, whatever they hold: the name by the reference's header rule, rlen =
  * the sequence line's length less one (its last byte goes, newline or not), the '+' line skipped, q_take = min(quality line with its newline, rlen),
  * 0 when that line is absent.  A text's records end at the first of: max_records taken (MORE); with final == 0 a record whose four lines do not all
  * end in '\n' inside the text (MORE); no header line (END); no sequence line or rlen == 0, which is what ends the reference's input (EMPTY);
  * rlen > max_read_len (TOO_LONG).  The records before a stop count.
+ * THE GZ RULE (MCX_FASTQ_RULE_GZ) is the .gz readers' (the reference's gzGetNextEntry, GetData.cpp:101-128: gzgets with a 1024-byte buffer, C strings): the text
+ * is cut into PIECES from its first byte — the piece at s is the bytes up to and including the first '\n' within text[s, s + 1023); without one, those 1023 bytes
+ * when there are as many, else the rest of the text (unfinished, the text's last) — and record k is pieces 4k .. 4k+3, each taken up to its first NUL (its C
+ * length).  Header: C length 0 or a first byte other than '@' and '>' ends the input (EMPTY); the name by the header rule over the C length.  rlen = C length of
+ * the sequence piece less one (0 for 0); q_take = min(C length of the fourth piece, rlen).  The stops are the plain rule's with pieces for lines; with final == 0
+ * a record is taken only when its four pieces are complete (each ends in '\n' or is 1023 bytes long).  consumed[t] is always a piece start of its line, so a
+ * caller that carries text[consumed ..) forward gets the same pieces again.  Texts without any NUL do not pay for the C lengths.
  * A parser is an object of its own like an inflater: one device, a non-blocking stream of its own, scratch in HBM (about 64 bytes per record of
  * max_records and 4 bytes per 4 KB of text) and page-locked staging for the host form, both growing on demand.  One host thread per object.
  *   n_records[t], stop[t]   records taken of text t and why no more (an mcx_fastq_stop)
@@ -506,6 +520,8 @@ int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t ca
 typedef struct mcx_fastq_parser mcx_fastq_parser;
 int  mcx_fastq_parser_create(int device, uint64_t max_text_bytes, uint32_t max_records, mcx_fastq_parser **out); /* 0: defaults; grows on demand */
 void mcx_fastq_parser_free(mcx_fastq_parser *);
+enum mcx_fastq_rule { MCX_FASTQ_RULE_PLAIN = 0, MCX_FASTQ_RULE_GZ = 1 };
+int  mcx_fastq_parser_set_rule(mcx_fastq_parser *, int rule); /* the rule of the parser's following calls; MCX_ERR_ARG: no such rule */
 
 typedef struct mcx_fastq_rec { uint32_t name, name_len, seq, rlen, qual, q_take; } mcx_fastq_rec; /* 24 bytes; offsets into the record's own text */
 enum mcx_fastq_stop { MCX_FASTQ_MORE = 0, MCX_FASTQ_END = 1, MCX_FASTQ_EMPTY = 2, MCX_FASTQ_TOO_LONG = 3 };
@@ -549,7 +565,17 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * device_parse (mapcaller-mi355x -gpu_parse): where the input is plain FASTQ that the front end maps into memory, the byte range of each of this shard's batches goes
  * through page-locked staging to an mcx_fastq_parser of its own on the context's device — about 0.3 KB of HBM per read of a batch, taken after the context's —, and
  * records, 2-bit rows, lengths and odd bytes come back: the reader's threads only copy.  Same reads, same end of the input, same error texts.  .gz, BGZF and FASTA
- * are read as before. */
+ * are read as before.
+ * device_inflate AND device_parse, THE RESIDENT ROUTE: where every read file of the call is BGZF FASTQ (named .gz, first text byte '@': one file, or two as pairs),
+ * the run is not sharded, -p is off and the SAM text — if any is made — is device_sam's, the reads stay in HBM from the compressed bytes to the records: the host
+ * walks the members and stages the compressed bytes; an inflater per file takes several 8 MB stretches per launch and leaves their text in a buffer in HBM; one
+ * mcx_fastq_parser under the GZ rule finds a batch's records in it (final = 0, text[consumed ..) carried to the next batch), packs rows, lengths and odd bytes
+ * into device buffers that travel with the batch object, which enter the slot through mcx_stream_submit_dev; names and NUL-padded qualities reach the SAM
+ * kernels from the same buffers.  Only the records, or the SAM text, come back.  Same reads, same end of the input (a damaged stretch, garbage behind a member,
+ * a header that is none, an empty or too long read, file 2 shorter or longer), same error texts.  HBM, taken after the context's: see DESIGN §5b.  Any other
+ * combination runs exactly as without the route; mcx_files_route says which stages ran on the device.
+ * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
+ * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
 typedef struct mcx_file_opts {
     int32_t interleaved_pairs, host_threads, append_sam;
     int32_t device_sam; /* 1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
@@ -563,6 +589,15 @@ typedef struct mcx_file_opts {
 } mcx_file_opts;
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
+/* Which stages of the context's last mcx_map_files* call ran on the device, per read file (route[1] = 0 for one file): the opt-in switches that do not apply
+ * to an input are ignored without a word, and the output is the same bytes by design.  MCX_TIMING=1 prints it. */
+enum mcx_route {
+    MCX_ROUTE_INFLATE = 1, /* the file's BGZF members were inflated on the device */
+    MCX_ROUTE_PARSE = 2,   /* its records were found and packed on the device */
+    MCX_ROUTE_ROWS = 4,    /* its batches entered their slots from HBM (mcx_stream_submit_dev): the resident route */
+    MCX_ROUTE_SAM = 8      /* the SAM text was made on the device */
+};
+int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,7 @@ SYMBOLS = [
     "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
     "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
+    "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -256,6 +257,8 @@ ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
 # mcx_deflate_member: one BGZF member's raw deflate stream src[src_off:][:src_len] -> dst[dst_off:][:isize], with the CRC-32 of its text
 MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 # mcx_fastq_rec: one FASTQ record as offsets into its own text; mcx_fastq_stop
+FASTQ_RULE_PLAIN, FASTQ_RULE_GZ = 0, 1  # mcx_fastq_rule
+ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
 
@@ -369,6 +372,12 @@ def lib() -> C.CDLL:
     L.mcx_exchange_local_free.restype = None
     L.mcx_stream_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.mcx_stream_submit_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.mcx_stream_submit_dev.restype = C.c_int
+    L.mcx_stream_submit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.mcx_files_route.restype = C.c_int
+    L.mcx_files_route.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mcx_fastq_parser_set_rule.restype = C.c_int
+    L.mcx_fastq_parser_set_rule.argtypes = [C.c_void_p, C.c_int]
     L.mcx_stream_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_map32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_mapped32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -590,7 +599,9 @@ class Mapper:
         new 200-read chunk); ``append_sam``: a further library of the same run; ``device_sam`` = -gpu_sam: the
         SAM text is made on the device (the same bytes); ``device_inflate`` = -gpu_inflate: read files that are BGZF are inflated on the
         device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files are parsed and packed to 2-bit rows on
-        the device (the same reads, the same end of the input; other input is read as before)."""
+        the device (the same reads, the same end of the input; other input is read as before).  ``device_inflate`` and ``device_parse`` together, on BGZF
+        FASTQ files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
+        parse, pack, map and SAM text all in HBM.  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
@@ -610,6 +621,18 @@ class Mapper:
         _check(lib().mcx_map_files_ex(self._h, fq1.encode(), (fq2 or "").encode() or None, C.byref(fo), (sam or "").encode() or None,
                                       C.byref(st)), "mcx_map_files_ex")
         return st.as_dict()
+
+    def last_route(self) -> Tuple[int, int]:
+        """mcx_files_route: per read file of the last map_files call, the stages that ran on the device as a sum of ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS
+        (the batches entered their slots from HBM) and ROUTE_SAM; the second entry is 0 for one file."""
+        r = (C.c_uint32 * 2)()
+        _check(lib().mcx_files_route(self._h, r), "mcx_files_route")
+        return int(r[0]), int(r[1])
+
+    def submit_dev(self, d_codes_ptr: int, row_words: int, d_len_ptr: int, n_reads: int, d_odd_ptr: int, n_odd: int) -> None:
+        """mcx_stream_submit_dev: mcx_stream_submit_packed's arguments as device pointers on the mapper's device (e.g. what FastqParser.parse_dev wrote to
+        rows / len / odd); the buffers must hold their contents until the batch has been handed out (mcx_stream_next / mcx_stream_map*)."""
+        _check(lib().mcx_stream_submit_dev(self._h, d_codes_ptr, row_words, d_len_ptr, n_reads, d_odd_ptr or None, n_odd), "mcx_stream_submit_dev")
 
     def map_batch(self, bases: np.ndarray, off: np.ndarray, paired: bool):
         """Host buffers: bases uint8 ASCII (concatenated), off uint32 [n+1].  Returns (aln, cigars): the records and, per
@@ -945,7 +968,7 @@ class Inflater:
 
 
 class FastqParser:
-    """mcx_fastq_parser: plain FASTQ text parsed on the device — record boundaries, names, bases, NUL-padded qualities, 2-bit rows and the list of
+    """mcx_fastq_parser: FASTQ text parsed on the device (set_rule: the plain rule — getline's lines, the default — or the .gz readers', FASTQ_RULE_GZ) — record boundaries, names, bases, NUL-padded qualities, 2-bit rows and the list of
     bytes that are not ACGT — on a stream of the object's own.  max_text_bytes / max_records size the first scratch (0: defaults); it grows on demand.
     Both calls take the texts (one, or the two of a pair) and the outputs by keyword: recs (a list, one array of REC_DTYPE records per text), bases,
     off, qual, names, name_off, rows, len, odd — a group that is left out is not produced.  A capacity defaults to its array's size (bases_cap,
@@ -967,6 +990,10 @@ class FastqParser:
 
     def __exit__(self, *exc):
         self.close()
+
+    def set_rule(self, rule: int) -> None:
+        """mcx_fastq_parser_set_rule: FASTQ_RULE_PLAIN or FASTQ_RULE_GZ for the calls that follow"""
+        _check(lib().mcx_fastq_parser_set_rule(self._h, rule), "mcx_fastq_parser_set_rule")
 
     @staticmethod
     def _structs(ptr, size, texts, max_records, max_read_len, final, o):

@@ -1,4 +1,4 @@
-// mapcaller_amd/csrc/mcx_fastq.h — the reader's rules for plain FASTQ text, once, for the device (mcx_fastq.hip) and for the host
+// mapcaller_amd/csrc/mcx_fastq.h — the reader's rules for FASTQ text (plain, and the .gz readers'), once, for the device (mcx_fastq.hip) and for the host
 // (tests/hostemu/fastq_check.cpp).
 //
 // Restated from MappedFastq::parse and header_of of mcx_files.cpp, which every golden SAM pins to the reference (GetNextEntry, GetData.cpp:32-55;
@@ -10,7 +10,17 @@
 //   quality    the '+' line is skipped; q_take = min(length of the quality line with its newline, rlen), 0 when the line is absent
 //   stops      no header line (END); no sequence line or rlen == 0 (EMPTY: what ends the reference's input, GetData.cpp:91); rlen > max_read_len
 //   rows       A 0, C 1, G 2, T 3, sixteen bases to a word, the first in the top bits; any other byte has code 0 and is listed
-// PLAIN RULE ONLY: the .gz readers' lines (gzgets with a 1024-byte buffer, strlen semantics, GetData.cpp:101-128) and FASTA are not covered.
+// THE GZ RULE (MCX_FASTQ_RULE_GZ), restated from Parser::line / Parser::entry of mcx_files.cpp in gz_mode_ with FASTQ input (gzGetNextEntry: gzgets with a
+// 1024-byte buffer, strlen semantics, GetData.cpp:101-128):
+//   a piece    what gzgets(buffer, 1024) gives: at s, the bytes up to and including the first '\n' within text[s, s + 1023); without one, those 1023 bytes
+//              when there are as many, else the rest of the text (unfinished, the text's last).  The next piece begins right behind: the pieces tile the
+//              text as the lines do, a line of L bytes (newline included) in ceil(L / 1023) of them — so the piece table has the line table's form
+//   C length   a piece's bytes before its first NUL (strlen), all of them when it has none
+//   record k   pieces 4k .. 4k+3.  Header: C length 0 or a first byte other than '@' and '>' ends the input (EMPTY); the name is header_of over the C
+//              length.  rlen = C length of the sequence piece less one (0 for 0); q_take = min(C length of the fourth piece, rlen), 0 when it is absent
+//   stops      as under the plain rule, with pieces for lines
+//   final == 0 a record is taken only when its four pieces are complete: each ends in '\n' or is 1023 bytes long
+// FASTA is covered by neither rule.
 #ifndef MCX_FASTQ_H
 #define MCX_FASTQ_H
 #include "mcx_types.h"
@@ -61,6 +71,72 @@ static inline MCX_HD uint32_t record_of(const uint8_t *text, uint32_t bytes, con
 
 // with final == 0: record k is taken only when its four lines all end in '\n' inside the text
 static inline MCX_HD bool record_whole(uint64_t n_nl, uint32_t k) { return n_nl >= 4ull * k + 4; }
+
+// ---- the GZ rule ----------------------------------------------------------------------------------------------
+enum : uint32_t { kGzPiece = 1023 }; // gzgets(buffer, 1024)
+// pieces of a line of len bytes (its newline included; the text's last line may lack one), and where piece j of the line that starts at s begins
+static inline MCX_HD uint32_t gz_pieces_of(uint32_t len) { return (len + kGzPiece - 1) / kGzPiece; }
+static inline MCX_HD uint32_t gz_piece_start(uint32_t s, uint32_t j) { return s + j * kGzPiece; }
+// The lines that can hold pieces 0 .. 4 * eff_max: the text's, at most 4 * eff_max of them (every line holds a piece at least).  ls[] as line_of takes it.
+static inline MCX_HD uint32_t gz_lines_counted(const uint32_t *ls, uint64_t n_nl, uint32_t bytes, uint32_t eff_max)
+{
+    const uint64_t cap = 4ull * eff_max;
+    if (n_nl >= cap) return (uint32_t)cap;
+    return (uint32_t)n_nl + (ls[n_nl] < bytes ? 1u : 0u); // (an unterminated last line counts)
+}
+// pieces of line L (0 from the counted lines on): what the exclusive sums po[] are taken of
+static inline MCX_HD uint32_t gz_line_pieces(const uint32_t *ls, uint64_t n_nl, uint32_t bytes, uint32_t n_counted, uint32_t L)
+{
+    if (L >= n_counted) return 0;
+    return gz_pieces_of((L < n_nl ? ls[L + 1] : bytes) - ls[L]);
+}
+// Entry q of the piece table, q <= 4 * eff_max: po[0 .. 4 * eff_max] the exclusive sums of gz_line_pieces, their last the number of pieces P.  Piece q < P
+// lies in the line found by search over the sums; entry P is the end of the counted lines (where piece P begins, if the text has one); false behind it.
+static inline MCX_HD bool gz_piece_entry(const uint32_t *ls, uint64_t n_nl, uint32_t bytes, const uint32_t *po, uint32_t eff_max, uint32_t n_counted, uint32_t q, uint32_t &start)
+{
+    const uint32_t n = 4u * eff_max, P = po[n];
+    if (q > P) return false;
+    if (q == P) { start = n_counted <= n_nl ? ls[n_counted] : bytes; return true; }
+    uint32_t lo = 0, hi = n_counted; // the last line L < n_counted with po[L] <= q (po rises strictly over the counted lines)
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (po[mid] <= q) lo = mid; else hi = mid; }
+    start = gz_piece_start(ls[lo], q - po[lo]);
+    return true;
+}
+// pieces in the table ps[] (ps[that many]: the end of the last one), as the record functions take it in n_nl's place
+static inline MCX_HD uint64_t gz_pieces_counted(const uint32_t *po, uint32_t eff_max) { const uint32_t n = 4u * eff_max; return po[n] < n ? po[n] : n; }
+static inline MCX_HD uint32_t gz_c_len(const uint8_t *p, uint32_t len, bool any_nul)
+{
+    if (any_nul) for (uint32_t i = 0; i < len; i++) if (p[i] == 0) return i; // (a text without any NUL does not pay for the search)
+    return len;
+}
+// record_of under the GZ rule: ps[] / n_p the piece table in the place of ls[] / n_nl; any_nul: the text holds a NUL somewhere
+static inline MCX_HD uint32_t gz_record_of(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k, int32_t max_read_len, bool any_nul, mcx_fastq_rec &rec)
+{
+    const uint64_t L = 4ull * k;
+    uint32_t s, len;
+    if (!line_of(ps, n_p, bytes, L, s, len)) return MCX_FASTQ_END;
+    uint32_t cl = gz_c_len(text + s, len, any_nul);
+    if (cl == 0 || (text[s] != '@' && text[s] != '>')) return MCX_FASTQ_EMPTY; // (entry() returns false: the input ends)
+    uint32_t p1, p2;
+    header_of(text + s, cl, p1, p2);
+    rec.name = s + p1; rec.name_len = p2 > p1 ? p2 - p1 : 0;
+    if (!line_of(ps, n_p, bytes, L + 1, s, len)) return MCX_FASTQ_EMPTY; // no sequence piece
+    cl = gz_c_len(text + s, len, any_nul);
+    rec.seq = s; rec.rlen = cl ? cl - 1 : 0;
+    uint32_t q, ql;
+    if (line_of(ps, n_p, bytes, L + 3, q, ql)) ql = gz_c_len(text + q, ql, any_nul); else { q = 0; ql = 0; }
+    rec.qual = q; rec.q_take = ql < rec.rlen ? ql : rec.rlen;
+    if (rec.rlen == 0) return MCX_FASTQ_EMPTY;
+    if ((int64_t)rec.rlen > (int64_t)max_read_len) return MCX_FASTQ_TOO_LONG;
+    return MCX_FASTQ_MORE;
+}
+// with final == 0: record k is taken only when its four pieces are complete — the first three are when the fourth exists (an unfinished piece is the text's last)
+static inline MCX_HD bool gz_record_whole(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k)
+{
+    uint32_t s, len;
+    if (!line_of(ps, n_p, bytes, 4ull * k + 3, s, len)) return false;
+    return len == kGzPiece || text[s + len - 1] == '\n';
+}
 
 static inline MCX_HD uint32_t code_of(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; } // 4: not upper-case ACGT
 static inline MCX_HD uint64_t odd_entry(uint32_t read, uint32_t pos, uint8_t c) { return ((uint64_t)read << 32) | ((uint64_t)pos << 8) | c; }

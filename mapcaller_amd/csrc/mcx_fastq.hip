@@ -1,4 +1,4 @@
-// mapcaller_amd/csrc/mcx_fastq.hip — plain FASTQ text parsed on the device (mcx_fastq_parser_create / _free, mcx_fastq_parse_dev, mcx_fastq_parse; the file
+// mapcaller_amd/csrc/mcx_fastq.hip — FASTQ text parsed on the device (mcx_fastq_parser_create / _free / _set_rule, mcx_fastq_parse_dev, mcx_fastq_parse; the file
 // front end's -gpu_parse goes through mcx_fastq_stage / mcx_fastq_staged_sizes / mcx_fastq_staged_out).
 //
 // Replaces, for text that lies in HBM, the reader's MappedFastq::parse + pack_row (mcx_files.cpp); the rules are mcx_fastq.h's.  Per call, on the
@@ -6,6 +6,8 @@
 //   k_count     newlines per 4 KB block of the text: a 16-byte load per lane, byte compares, a wave reduction
 //   (hipCUB)    exclusive sum of the block counts; its last entry is the text's number of newlines
 //   k_lines     the 32-bit start of every line up to 4 * max_records: a lane's rank in its block from a scan of the lanes' counts
+//   (GZ rule)   k_count notes as well whether the text holds a NUL; k_line_pieces a lane per line: its pieces of 1023 bytes; an exclusive sum; k_pieces a lane
+//               per piece: its line by search over the sums, its start — the piece table, which the kernels below take in the line table's place
 //   k_records   one lane per record: record_of; the records that end the text feed a wave-min and one atomicMin per wave
 //   k_finish    records taken, why no more, bytes consumed, reads
 //   k_lens      rlen and name_len per read in output order; k_odd<false> the bytes per read that are not ACGT; three exclusive sums
@@ -46,20 +48,24 @@ struct Text { // one text of a call, as the kernels see it
     uint32_t eff_max;        // min(max_records, bytes / 3 + 1): a record that is taken holds three bytes at least
     uint32_t *cnt, *pre;     // [n_blocks + 1] newlines per block, their exclusive sums (pre[n_blocks]: all of them)
     uint32_t *ls;            // [4 * eff_max + 1] line starts
+    uint32_t *pc, *po, *ps;  // GZ rule, [4 * eff_max + 1] each: pieces per line, their exclusive sums, piece starts
     mcx_fastq_rec *recs;     // [eff_max]
 };
 struct Job {
     Text t[2];
     uint32_t nt, upper;      // texts; nt * eff_max(largest): the reads a call can give
     int32_t max_read_len, final;
+    int32_t rule;            // MCX_FASTQ_RULE_*
 };
 struct DevInfo { // what the kernels tell the host
     unsigned long long stop_key[2]; // (first record that ends the text << 8 | why), minimum over the records
+    uint32_t any_nul[2];            // GZ rule: the text holds a NUL somewhere (k_count)
     mcx_fastq_info info;
 };
 
-// the 16 bytes at blocks' position v (a multiple of 16) as a mask of its newlines; bytes outside the text count as none
-__device__ __forceinline__ uint32_t newline_mask(const Text &t, uint64_t v)
+// the 16 bytes at blocks' position v (a multiple of 16) as a mask of its bytes equal to kByte; bytes outside the text count as none
+template <uint32_t kByte>
+__device__ __forceinline__ uint32_t byte_mask(const Text &t, uint64_t v)
 {
     const int64_t p0 = (int64_t)v - (int64_t)t.lead;
     uint32_t m = 0;
@@ -69,33 +75,40 @@ __device__ __forceinline__ uint32_t newline_mask(const Text &t, uint64_t v)
         MCX_UNROLL
         for (int i = 0; i < 4; i++) {
             MCX_UNROLL
-            for (int j = 0; j < 4; j++) m |= (((w[i] >> (8 * j)) & 0xFFu) == (uint32_t)'\n' ? 1u : 0u) << (4 * i + j);
+            for (int j = 0; j < 4; j++) m |= (((w[i] >> (8 * j)) & 0xFFu) == kByte ? 1u : 0u) << (4 * i + j);
         }
     } else { // the text's head or tail (or a chunk outside it altogether)
         for (int j = 0; j < 16; j++) {
             const int64_t p = p0 + j;
-            if (p >= 0 && p < (int64_t)t.bytes && t.text[p] == '\n') m |= 1u << j;
+            if (p >= 0 && p < (int64_t)t.bytes && t.text[p] == (uint8_t)kByte) m |= 1u << j;
         }
     }
     return m;
 }
+__device__ __forceinline__ uint32_t newline_mask(const Text &t, uint64_t v) { return byte_mask<(uint32_t)'\n'>(t, v); }
 
 __global__ void k_init(DevInfo *d, Job job)
 {
     if (threadIdx.x || blockIdx.x) return;
-    for (uint32_t t = 0; t < 2; t++) d->stop_key[t] = ((unsigned long long)(t < job.nt ? job.t[t].eff_max : 0u) << 8) | MCX_FASTQ_MORE;
+    for (uint32_t t = 0; t < 2; t++) { d->stop_key[t] = ((unsigned long long)(t < job.nt ? job.t[t].eff_max : 0u) << 8) | MCX_FASTQ_MORE; d->any_nul[t] = 0; }
     d->info = mcx_fastq_info{};
     for (uint32_t t = 0; t < job.nt; t++) job.t[t].ls[0] = 0;
 }
 
-__global__ void __launch_bounds__(kThreads) k_count(Job job)
+// kGz: whether the text holds a NUL is noted on the way (the same 16 bytes; one atomicOr per workgroup that saw one — a flag, no order hangs on it)
+template <bool kGz>
+__global__ void __launch_bounds__(kThreads) k_count(Job job, DevInfo *d)
 {
     const Text &t = job.t[blockIdx.y];
     const uint32_t b = blockIdx.x;
     if (b > t.n_blocks) return; // (the whole workgroup)
     __shared__ uint32_t part[kThreads / 64];
     uint32_t c = b < t.n_blocks ? __popc(newline_mask(t, (uint64_t)b * kBlockBytes + threadIdx.x * 16u)) : 0u;
-    for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d);
+    if (kGz) {
+        const bool nul = b < t.n_blocks && byte_mask<0u>(t, (uint64_t)b * kBlockBytes + threadIdx.x * 16u) != 0;
+        if (__syncthreads_or(nul) && threadIdx.x == 0) atomicOr(&d->any_nul[blockIdx.y], 1u);
+    }
+    for (int s = 32; s; s >>= 1) c += __shfl_xor(c, s);
     if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) t.cnt[b] = part[0] + part[1] + part[2] + part[3]; // (block n_blocks: 0, so that the sums end with the total)
@@ -126,6 +139,28 @@ __global__ void __launch_bounds__(kThreads) k_lines(Job job)
     }
 }
 
+// GZ rule: a lane per line L <= 4 * eff_max: its pieces (0 behind the lines that count)
+__global__ void __launch_bounds__(kThreads) k_line_pieces(Job job)
+{
+    const Text &t = job.t[blockIdx.y];
+    const uint64_t L = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (L > 4ull * t.eff_max) return;
+    const uint64_t n_nl = t.pre[t.n_blocks];
+    t.pc[L] = gz_line_pieces(t.ls, n_nl, t.bytes, gz_lines_counted(t.ls, n_nl, t.bytes, t.eff_max), (uint32_t)L);
+}
+
+// GZ rule: a lane per entry q <= 4 * eff_max of the piece table — no lane walks a line's pieces, however long the line
+__global__ void __launch_bounds__(kThreads) k_pieces(Job job)
+{
+    const Text &t = job.t[blockIdx.y];
+    const uint64_t q = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (q > 4ull * t.eff_max) return;
+    const uint64_t n_nl = t.pre[t.n_blocks];
+    uint32_t start;
+    if (gz_piece_entry(t.ls, n_nl, t.bytes, t.po, t.eff_max, gz_lines_counted(t.ls, n_nl, t.bytes, t.eff_max), (uint32_t)q, start)) t.ps[q] = start;
+}
+
+template <bool kGz>
 __global__ void __launch_bounds__(kThreads) k_records(Job job, DevInfo *d)
 {
     const Text &t = job.t[blockIdx.y];
@@ -134,12 +169,12 @@ __global__ void __launch_bounds__(kThreads) k_records(Job job, DevInfo *d)
     bool ends = false;
     if (k64 < t.eff_max) {
         k = (uint32_t)k64;
-        const uint64_t n_nl = t.pre[t.n_blocks];
-        if (!job.final && !record_whole(n_nl, k)) ends = true;
+        const uint64_t n_nl = kGz ? gz_pieces_counted(t.po, t.eff_max) : t.pre[t.n_blocks]; // (kGz: pieces, in t.ps)
+        if (!job.final && !(kGz ? gz_record_whole(t.text, t.bytes, t.ps, n_nl, k) : record_whole(n_nl, k))) ends = true;
         else {
             mcx_fastq_rec rec;
             rec.name = rec.name_len = rec.seq = rec.rlen = rec.qual = rec.q_take = 0;
-            why = record_of(t.text, t.bytes, t.ls, n_nl, k, job.max_read_len, rec);
+            why = kGz ? gz_record_of(t.text, t.bytes, t.ps, n_nl, k, job.max_read_len, d->any_nul[blockIdx.y] != 0, rec) : record_of(t.text, t.bytes, t.ls, n_nl, k, job.max_read_len, rec);
             if (why == MCX_FASTQ_MORE) t.recs[k] = rec; else ends = true;
         }
     }
@@ -155,9 +190,10 @@ __global__ void k_finish(Job job, DevInfo *d)
     for (uint32_t i = 0; i < job.nt; i++) {
         const Text &t = job.t[i];
         const uint32_t n = (uint32_t)(d->stop_key[i] >> 8);
-        const uint64_t n_nl = t.pre[t.n_blocks];
+        const bool gz = job.rule == MCX_FASTQ_RULE_GZ;
+        const uint64_t n_nl = gz ? gz_pieces_counted(t.po, t.eff_max) : t.pre[t.n_blocks];
         f.n_records[i] = n; f.stop[i] = (uint32_t)(d->stop_key[i] & 0xFFu);
-        f.consumed[i] = 4ull * n <= n_nl ? t.ls[4ull * n] : t.bytes;
+        f.consumed[i] = 4ull * n <= n_nl ? (gz ? t.ps : t.ls)[4ull * n] : t.bytes; // (GZ rule: a piece start of its line)
     }
     f.n_reads = job.nt == 2 ? 2u * min(f.n_records[0], f.n_records[1]) : f.n_records[0];
 }
@@ -259,7 +295,8 @@ struct Buf { // device memory that grows
 struct mcx_fastq_parser {
     int device = 0;
     hipStream_t stream = nullptr;
-    Buf cnt[2], pre[2], ls[2], recs[2], rl, nl, oc, off, noff, ooff, tmp, info;
+    int rule = MCX_FASTQ_RULE_PLAIN;
+    Buf cnt[2], pre[2], ls[2], pc[2], po[2], ps[2], recs[2], rl, nl, oc, off, noff, ooff, tmp, info;
     DevInfo *h_info = nullptr; // page-locked
     // the host forms: the texts' page-locked staging and their twin in HBM; the outputs' buffers in HBM
     uint8_t *h_text = nullptr; size_t h_text_cap = 0;
@@ -297,7 +334,7 @@ extern "C" void mcx_fastq_parser_free(mcx_fastq_parser *p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    Buf *all[] = {&p->cnt[0], &p->cnt[1], &p->pre[0], &p->pre[1], &p->ls[0], &p->ls[1], &p->recs[0], &p->recs[1], &p->rl, &p->nl, &p->oc, &p->off, &p->noff, &p->ooff, &p->tmp, &p->info,
+    Buf *all[] = {&p->cnt[0], &p->cnt[1], &p->pre[0], &p->pre[1], &p->ls[0], &p->ls[1], &p->pc[0], &p->pc[1], &p->po[0], &p->po[1], &p->ps[0], &p->ps[1], &p->recs[0], &p->recs[1], &p->rl, &p->nl, &p->oc, &p->off, &p->noff, &p->ooff, &p->tmp, &p->info,
                   &p->d_text, &p->o_recs[0], &p->o_recs[1], &p->o_bases, &p->o_qual, &p->o_off, &p->o_names, &p->o_noff, &p->o_rows, &p->o_len, &p->o_odd};
     for (Buf *b : all) if (b->p) (void)hipFree(b->p);
     mcx_pinned_free(p->h_info); mcx_pinned_free(p->h_text);
@@ -319,6 +356,11 @@ int reserve(mcx_fastq_parser *p, const uint64_t bytes[2], uint32_t nt, const uin
         if ((rc = grow(p, p->cnt[t], nb * 4, "the block counts"))) break;
         if ((rc = grow(p, p->pre[t], nb * 4, "the block sums"))) break;
         if ((rc = grow(p, p->ls[t], (4ull * eff[t] + 1) * 4, "the line starts"))) break;
+        if (p->rule == MCX_FASTQ_RULE_GZ) {
+            most = std::max<uint64_t>(most, 4ull * eff[t] + 1);
+            if ((rc = grow(p, p->pc[t], (4ull * eff[t] + 1) * 4, "the lines' pieces")) || (rc = grow(p, p->po[t], (4ull * eff[t] + 1) * 4, "the pieces' sums")) ||
+                (rc = grow(p, p->ps[t], (4ull * eff[t] + 1) * 4, "the piece starts"))) break;
+        }
         rc = grow(p, p->recs[t], std::max<uint64_t>(eff[t], 1) * sizeof(mcx_fastq_rec), "the records");
     }
     if (rc) return rc;
@@ -372,10 +414,12 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
     if (nt == 2 && in->bytes[0] + in->bytes[1] >= (1ull << 32)) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": the two texts together hold less than 4 GiB (32-bit offsets into the bases)");
     Job &job = p->job;
     memset(&job, 0, sizeof job);
-    job.nt = nt; job.max_read_len = in->max_read_len; job.final = in->final;
+    job.nt = nt; job.max_read_len = in->max_read_len; job.final = in->final; job.rule = p->rule;
+    const bool gz = p->rule == MCX_FASTQ_RULE_GZ;
     uint32_t eff[2] = {0, 0}, most_blocks = 0, most_eff = 0;
     for (uint32_t t = 0; t < nt; t++) { eff[t] = eff_max_of(in->max_records, in->bytes[t]); most_eff = std::max(most_eff, eff[t]); }
     if ((uint64_t)nt * most_eff + 1 > 0x7FFFFFFFull) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": max_records is too large");
+    if (gz && 4ull * most_eff + 1 > 0x7FFFFFFFull) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": max_records is too large (the GZ rule's piece table holds 4 * max_records + 1 entries)");
     if (int rc = reserve(p, in->bytes, nt, eff)) return rc;
     for (uint32_t t = 0; t < nt; t++) {
         Text &x = job.t[t];
@@ -383,7 +427,7 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
         x.lead = (uint32_t)((uintptr_t)x.text & 15u);
         x.n_blocks = (uint32_t)(((uint64_t)x.bytes + x.lead + kBlockBytes - 1) / kBlockBytes);
         x.eff_max = eff[t];
-        x.cnt = (uint32_t *)p->cnt[t].p; x.pre = (uint32_t *)p->pre[t].p; x.ls = (uint32_t *)p->ls[t].p; x.recs = (mcx_fastq_rec *)p->recs[t].p;
+        x.cnt = (uint32_t *)p->cnt[t].p; x.pre = (uint32_t *)p->pre[t].p; x.ls = (uint32_t *)p->ls[t].p; x.pc = (uint32_t *)p->pc[t].p; x.po = (uint32_t *)p->po[t].p; x.ps = (uint32_t *)p->ps[t].p; x.recs = (mcx_fastq_rec *)p->recs[t].p;
         most_blocks = std::max(most_blocks, x.n_blocks);
     }
     job.upper = nt * most_eff;
@@ -393,11 +437,18 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
 
     HIP_TRY(hipEventRecord(p->ev[0], s));
     k_init<<<1, 64, 0, s>>>(d, job);
-    k_count<<<dim3(most_blocks + 1, nt), kThreads, 0, s>>>(job);
+    if (gz) k_count<true><<<dim3(most_blocks + 1, nt), kThreads, 0, s>>>(job, d); else k_count<false><<<dim3(most_blocks + 1, nt), kThreads, 0, s>>>(job, d);
     HIP_TRY(hipGetLastError());
     for (uint32_t t = 0; t < nt; t++) if (int rc = scan(p, job.t[t].cnt, job.t[t].pre, (uint64_t)job.t[t].n_blocks + 1)) return rc;
     if (most_blocks) k_lines<<<dim3(most_blocks, nt), kThreads, 0, s>>>(job);
-    if (most_eff) k_records<<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d);
+    if (gz) { // the piece table from the line table
+        const dim3 grid(blocks_for(4ull * most_eff + 1, kThreads), nt);
+        k_line_pieces<<<grid, kThreads, 0, s>>>(job);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t t = 0; t < nt; t++) if (int rc = scan(p, job.t[t].pc, job.t[t].po, 4ull * job.t[t].eff_max + 1)) return rc;
+        k_pieces<<<grid, kThreads, 0, s>>>(job);
+    }
+    if (most_eff) { if (gz) k_records<true><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); else k_records<false><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); }
     k_finish<<<1, 64, 0, s>>>(job, d);
     k_lens<<<blocks_for((uint64_t)job.upper + 1, kThreads), kThreads, 0, s>>>(job, d, rl, nl);
     k_odd<false><<<blocks_for((uint64_t)job.upper + 1, kThreads / 64), kThreads, 0, s>>>(job, d, oc, nullptr, nullptr);
@@ -460,6 +511,28 @@ extern "C" int mcx_fastq_parse_dev(mcx_fastq_parser *p, const mcx_fastq_in *in, 
     if (out->bases && (((uintptr_t)out->bases & 15u) || (out->qual && ((uintptr_t)out->qual & 15u)))) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parse_dev: bases and qual are 16-byte aligned");
     HIP_TRY(hipSetDevice(p->device));
     if (int rc = sizes_pass(p, in, info, "mcx_fastq_parse_dev")) return rc;
+    return output_pass(p, out, info, "mcx_fastq_parse_dev");
+}
+
+extern "C" int mcx_fastq_parser_set_rule(mcx_fastq_parser *p, int rule)
+{
+    if (!p || (rule != MCX_FASTQ_RULE_PLAIN && rule != MCX_FASTQ_RULE_GZ)) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parser_set_rule: null parser or no such rule");
+    p->rule = rule;
+    return 0;
+}
+
+// mcx_fastq_parse_dev in its two halves, for a caller inside the library that sizes its buffers between them (the resident route, mcx_resident.hip): sizes
+// parses and fills *info; out writes the groups of `out` (device pointers) for the texts of the last sizes — a group whose capacity is too small is refused
+int mcx_fastq_dev_sizes(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info)
+{
+    HIP_TRY(hipSetDevice(p->device));
+    return sizes_pass(p, in, info, "mcx_fastq_parse_dev");
+}
+int mcx_fastq_dev_out(mcx_fastq_parser *p, const mcx_fastq_out *out, const mcx_fastq_info *info)
+{
+    if (const char *why = rows_fault(out, p->job.max_read_len)) return mcx_set_error(MCX_ERR_ARG, std::string("mcx_fastq_parse_dev: ") + why);
+    if (out->bases && (((uintptr_t)out->bases & 15u) || (out->qual && ((uintptr_t)out->qual & 15u)))) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parse_dev: bases and qual are 16-byte aligned");
+    HIP_TRY(hipSetDevice(p->device));
     return output_pass(p, out, info, "mcx_fastq_parse_dev");
 }
 

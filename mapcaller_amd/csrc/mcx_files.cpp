@@ -10,7 +10,9 @@
 //     the reads' names, bases and qualities left where they lie in the file (the SAM formatter reads
 //     them there) and the bases packed to 2 bits on the way (a quarter of the bytes cross PCIe); a
 //     shard of a several-GPU run touches only the bytes of its own batches;
-//   * .gz files and FASTA go through one sequential reader per file (zlib / multi-line records);
+//   * .gz files and FASTA go through one sequential reader per file (zlib / multi-line records) — except BGZF FASTQ with -gpu_inflate -gpu_parse, whose text
+//     stays in HBM from the compressed bytes on (the resident route, mcx_resident.hip): the reader thread then only asks for the next batch, the mapper
+//     submits it from HBM (mcx_stream_submit_dev) and the SAM kernels take names and qualities where the parser left them;
 //   * batches flow through parse | copy in, map, copy out (three device slots: the copies of one
 //     batch under the kernels of its neighbours) | format + write;
 //   * SAM lines are formatted by a second pool into per-slice buffers and written with positioned
@@ -332,21 +334,7 @@ private:
 };
 
 // a BGZF member at p (n bytes left in the file): its whole size and the length of its extra field; 0 if it is not one
-size_t bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen)
-{
-    if (n < 28 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-    xlen = (size_t)p[10] | ((size_t)p[11] << 8);
-    if (12 + xlen + 8 > n) return 0;
-    for (size_t o = 12; o + 4 <= 12 + xlen;) { // the subfields of the extra field: SI1 SI2 SLEN(2) data
-        const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
-        if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
-            const size_t size = ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1;
-            return (size >= 12 + xlen + 8 && size <= n) ? size : 0;
-        }
-        o += 4 + slen;
-    }
-    return 0;
-}
+size_t bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen) { return mcx_bgzf_member_at(p, n, xlen); }
 
 // The sequential reader: .gz through zlib, FASTA (multi-line records).
 class Parser {
@@ -399,6 +387,7 @@ public:
         if (map_) munmap((void *)map_, map_size_);
     }
     bool fastq() const { return fastq_; }
+    bool device_inflated() const { return inflater_ != nullptr; } // -gpu_inflate applied: the file is BGZF
 
     // appends up to `want` reads (copied into v.own); false once the input is exhausted (View::last set)
     bool take(View &v, uint32_t want, int max_len)
@@ -754,6 +743,12 @@ struct Batch {
     uint64_t cap_sam_names = 0, cap_sam_qual = 0, cap_sam_off = 0, dev_text_cap = 0, dev_bytes = 0;
     uint64_t sam_part_names[2] = {0, 0}, sam_part_qual[2] = {0, 0};
     std::vector<uint64_t> sam_qual_at;
+    // the resident route (-gpu_inflate -gpu_parse on BGZF FASTQ): the batch's rows, lengths, odd bytes, names and qualities lie in device buffers that belong
+    // to this object (made and grown by mcx_resident_next); `rb` says where.  `in[]` then holds counts only.
+    mcx_resident_bufs *res = nullptr;
+    mcx_resident_batch rb;
+    bool resident = false;
+    int error_rc = 0; // the code that goes with `error` where it is not the reader's own (a device that ran out of room: MCX_ERR_DEVICE)
     bool reserve_sam(uint64_t reads, uint64_t names, uint64_t qual)
     {
         if (reads + 2 > cap_sam_off) { mcx_pinned_free(sam_name_off); cap_sam_off = reads + 2; sam_name_off = (uint32_t *)mcx_pinned_alloc(cap_sam_off * sizeof(uint32_t)); }
@@ -778,7 +773,7 @@ struct Batch {
         if (n > cap_odd) { mcx_pinned_free(odd); cap_odd = n + n / 2 + 1024; odd = (uint64_t *)mcx_pinned_alloc(cap_odd * sizeof(uint64_t)); }
         return odd != nullptr;
     }
-    ~Batch() { mcx_pinned_free(rows); mcx_pinned_free(lens); mcx_pinned_free(odd); mcx_pinned_free(recs); mcx_pinned_free(cig); mcx_pinned_free(sam_names); mcx_pinned_free(sam_qual); mcx_pinned_free(sam_name_off); mcx_pinned_free(dev_text); }
+    ~Batch() { mcx_resident_bufs_free(res); mcx_pinned_free(rows); mcx_pinned_free(lens); mcx_pinned_free(odd); mcx_pinned_free(recs); mcx_pinned_free(cig); mcx_pinned_free(sam_names); mcx_pinned_free(sam_qual); mcx_pinned_free(sam_name_off); mcx_pinned_free(dev_text); }
     // read r of the batch -> (file, index in that file's records)
     const Rec &rec(uint32_t r, const char *&base) const
     {
@@ -874,6 +869,26 @@ inline size_t sam_bound_read(const HostIndex &ix, const Batch &bt, uint32_t r, s
 } // namespace
 
 extern "C" void mcx_file_opts_default(mcx_file_opts *o) { memset(o, 0, sizeof *o); }
+
+// what the file front end keeps with a context from call to call: its batch objects (page-locked and device buffers: slow to get), and which stages of the
+// last call ran on the device
+namespace {
+struct Kept { std::vector<std::unique_ptr<Batch>> objects; uint32_t route[2] = {0, 0}; };
+Kept *kept_of(mcx_ctx *c)
+{
+    void **slot = mcx_ctx_files_slot(c, [](void *p) { delete (Kept *)p; });
+    if (!*slot) *slot = new Kept();
+    return (Kept *)*slot;
+}
+} // namespace
+
+extern "C" int mcx_files_route(mcx_ctx *c, uint32_t route[2])
+{
+    if (!c || !route) return mcx_set_error(MCX_ERR_ARG, "mcx_files_route: null argument");
+    const Kept *k = kept_of(c);
+    route[0] = k->route[0]; route[1] = k->route[1];
+    return 0;
+}
 
 extern "C" uint32_t mcx_pack_row(const uint8_t *seq, uint32_t rlen, uint32_t read, uint32_t *row, uint32_t row_words, uint64_t *odd, uint32_t odd_cap, uint32_t *n_odd)
 {
@@ -1106,6 +1121,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     const mcx_index *idx = mcx_ctx_index(c);
     const HostIndex &hix = idx->host;
     const int max_len = mcx_ctx_max_read_len(c);
+    Kept *kept = kept_of(c);
+    kept->route[0] = kept->route[1] = 0;
     const bool two = fq2 && fq2[0];
     const bool paired = two || opt.interleaved_pairs;
     const uint64_t shard_count = opt.shard_count > 1 ? (uint64_t)opt.shard_count : 1, shard_rank = shard_count > 1 ? (uint64_t)opt.shard_rank : 0;
@@ -1144,7 +1161,15 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     struct FqFree { void operator()(mcx_fastq_parser *q) const { mcx_fastq_parser_free(q); } };
     std::unique_ptr<mcx_fastq_parser, FqFree> fq_parser; // -gpu_parse on plain FASTQ
     struct PinnedRecs { mcx_fastq_rec *p[2] = {nullptr, nullptr}; mcx_fastq_rec *&operator[](int f) { return p[f]; } ~PinnedRecs() { mcx_pinned_free(p[0]); mcx_pinned_free(p[1]); } } fq_recs; // a batch's records as the device hands them out
+    struct ResFree { void operator()(mcx_resident *r) const { mcx_resident_close(r); } };
+    std::unique_ptr<mcx_resident, ResFree> resident; // -gpu_inflate -gpu_parse on BGZF FASTQ: the reads stay in HBM (mcx_resident.hip)
     bool fastq = true;
+    if (!mapped_input && opt.device_inflate && opt.device_parse && !sharded && !opt.interleaved_pairs && (!(sam_path && sam_path[0]) || opt.device_sam)) {
+        const char *paths[2] = {fq1, two ? fq2 : nullptr};
+        mcx_resident *r = nullptr;
+        if ((rc = mcx_resident_open(idx->device, paths, two ? 2 : 1, &r))) return rc;
+        resident.reset(r); // (null: a file is no BGZF FASTQ — the route does not apply and the files are read as without it)
+    }
     if (mapped_input) {
         for (int f = 0; f < (two ? 2 : 1) && rc == 0; f++) if (!mf[f].open(f ? fq2 : fq1, err)) rc = mcx_set_error(MCX_ERR_IO, err);
         if (sharded && (rc = sh.agree(rc))) return rc;
@@ -1178,7 +1203,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             if (sharded && (rc = sh.agree(rc))) return rc;
             if (rc) return rc;
         }
-    } else {
+    } else if (!resident) { // (the resident route opens its files itself: mcx_resident_open above)
         const int inflate_device = opt.device_inflate ? idx->device : -1; // -gpu_inflate: BGZF files are inflated on the context's device
         if (!ps[0].open(fq1, err, inflate_device)) rc = mcx_set_error(MCX_ERR_IO, err);
         if (rc == 0 && two && !ps[1].open(fq2, err, inflate_device)) rc = mcx_set_error(MCX_ERR_IO, err);
@@ -1224,6 +1249,9 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     }
 
     const bool dev_sam = opt.device_sam != 0 && sam_fd >= 0; // the text is made on the device (mcx_sam.hip); without a SAM file there is none to make
+    for (int f = 0; f < (two ? 2 : 1); f++)
+        kept->route[f] = resident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS) | (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u)
+                                  : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (mapped_input && fq_parser ? (uint32_t)MCX_ROUTE_PARSE : 0u) | (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u);
     int64_t local_avg[4];
     mcx_avg_init(local_avg);
     int64_t *avg = opt.avg_state ? opt.avg_state : local_avg;
@@ -1238,10 +1266,6 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     //  formatter's and the writer's hands; shards wait two rounds for the places of their text: sixteen.  At -batch 2 M reads an object
     //  pins ~0.5 GB of host memory — 6 GB a shard —, which is the host-memory bill of a run: see INTEGRATION.md)
     const int n_objects = shard_count > 1 ? 16 : 12;
-    struct Kept { std::vector<BatchPtr> objects; };
-    void **slot = mcx_ctx_files_slot(c, [](void *p) { delete (Kept *)p; });
-    if (!*slot) *slot = new Kept();
-    Kept *kept = (Kept *)*slot;
     Queue<BatchPtr> parsed(2), mapped(2), formatted(2), spare((size_t)n_objects);
     for (int k = 0; k < n_objects; k++) {
         if (!kept->objects.empty()) { spare.push(std::move(kept->objects.back())); kept->objects.pop_back(); }
@@ -1268,7 +1292,18 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             bool dev_parsed = false;   // -gpu_parse: the batch's records came from the device, and its rows will
             mcx_fastq_info fq_info;
             memset(&fq_info, 0, sizeof fq_info);
-            if (mapped_input && fq_parser && mine) {
+            b->resident = false; b->error_rc = 0;
+            if (resident) {
+                // the resident route: the batch is counted, cut and packed in HBM; the views hold the files' counts and ends, as Parser::take leaves them
+                b->resident = true;
+                if ((b->error_rc = mcx_resident_next(resident.get(), &b->res, per_file, max_len, dev_sam, &b->rb)) != 0) b->in[0].error = mcx_last_error();
+                else for (int f = 0; f < (two ? 2 : 1); f++) {
+                    View &v = b->in[f];
+                    if (!v.recs.resize(b->rb.n_records[f])) { v.error = "out of memory for the batch's read records"; continue; } // (counted, never read)
+                    v.last = b->rb.last[f];
+                    if (b->rb.has_too_long[f]) v.error = "read " + std::string(b->rb.too_long[f]) + " is longer than max_read_len";
+                }
+            } else if (mapped_input && fq_parser && mine) {
                 // The byte ranges of records [r0, r1) of each file — from the line index, as above — go to the parser's page-locked staging through the pool and are
                 // parsed as whole texts (final): the same records, the same stops as MappedFastq::parse gives.
                 dev_parsed = true;
@@ -1399,8 +1434,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 uint32_t npr = paired ? n : 0; // reads mapped as pairs; the odd tail of an interleaved file is mapped read by read
                 if (paired && (n & 1)) npr = n / kReadChunkSize * kReadChunkSize;
                 b->n_pair_reads = npr;
-                uint32_t longest = fq_info.longest;
-                if (!dev_parsed) {
+                uint32_t longest = b->resident ? b->rb.longest : fq_info.longest;
+                if (!dev_parsed && !b->resident) {
                     const int slices = (int)std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)pool.size(), n / 4096));
                     std::vector<uint32_t> most((size_t)slices, 0);
                     pool.run(slices, [&](int k) {
@@ -1411,8 +1446,14 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                     for (uint32_t m : most) longest = std::max(longest, m);
                 }
                 b->row_words = (longest + 15) / 16;
-                if (!b->reserve(std::max<size_t>(n, batch_reads), std::max<size_t>(b->row_words, ((size_t)max_len + 15) / 16))) b->error = "cannot allocate pinned host memory";
-                else if (dev_parsed) {
+                if (!b->reserve(std::max<size_t>(n, batch_reads), b->resident ? 1 : std::max<size_t>(b->row_words, ((size_t)max_len + 15) / 16))) b->error = "cannot allocate pinned host memory";
+                else if (b->resident) {
+                    // rows, lengths and odd bytes are in the batch's device buffers; the odd list is split at the pair / single part boundary as below — here one
+                    // of the two parts is the whole batch (two files: pairs; one: single reads, numbered from 0 as they are)
+                    if (b->rb.n_reads != n) b->error = "-gpu_parse: the device packed " + std::to_string(b->rb.n_reads) + " reads, the reader counted " + std::to_string(n);
+                    b->row_words = b->rb.row_words;
+                    b->n_odd[0] = npr ? b->rb.n_odd : 0; b->n_odd[1] = npr ? 0 : b->rb.n_odd;
+                } else if (dev_parsed) {
                     // rows, lengths and the sorted list of odd bytes straight into the batch's page-locked buffers; the list is split at the first read of the
                     // single-read part, whose reads are numbered from 0 like a batch of its own
                     mcx_fastq_out o;
@@ -1457,7 +1498,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 b->is_mate2.assign(n, 0);
                 for (uint32_t r = 1; r < npr; r += 2) b->is_mate2[r] = 1;
                 // device_sam: names and qualities as mcx_sam_in takes them, a part's qualities where the device's offsets (the running sum of the lengths) put its reads
-                if (dev_sam && b->error.empty()) {
+                if (dev_sam && b->error.empty() && !b->resident) { // (the resident route: names and qualities are in HBM already)
                     uint64_t names = 0, quals[2] = {0, 0};
                     for (uint32_t r = 0; r < n; r++) { const char *base; names += b->rec(r, base).name_len; }
                     b->sam_qual_at.resize(n);
@@ -1670,6 +1711,11 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     auto submit = [&](Batch *p) -> int {
         const uint32_t n = p->n, npr = p->n_pair_reads;
         int e = 0;
+        if (p->resident) { // the arrays lie in HBM: device-to-device into the slot (one part: npr is 0 or n)
+            e = mcx_stream_submit_dev(c, p->rb.rows, p->rb.row_words, p->rb.len, n, p->rb.n_odd ? p->rb.odd : nullptr, p->rb.n_odd);
+            if (e == 0) in_flight++;
+            return e;
+        }
         if (npr) { e = mcx_stream_submit_packed(c, p->rows, p->row_words, p->lens, npr, p->odd, p->n_odd[0]); if (e) return e; in_flight++; }
         if (npr < n) {
             e = mcx_stream_submit_packed(c, p->rows + (size_t)npr * p->row_words, p->row_words, p->lens + npr, n - npr, p->odd ? p->odd + p->n_odd[0] : nullptr, p->n_odd[1]);
@@ -1688,7 +1734,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         if (block) b = parsed.pop(); else if (!parsed.try_pop(b)) return;
         t_m_take += secs(tq, now());
         if (b->last) input_done = true;
-        if (rc == 0 && !b->error.empty()) rc = mcx_set_error(b->error.find("max_read_len") != std::string::npos ? MCX_ERR_UNSUPPORTED : MCX_ERR_IO, b->error);
+        if (rc == 0 && !b->error.empty()) rc = mcx_set_error(b->error_rc ? b->error_rc : b->error.find("max_read_len") != std::string::npos ? MCX_ERR_UNSUPPORTED : MCX_ERR_IO, b->error);
         if (rc || ended) b->n = 0;
         nxt = std::move(b); nxt_in = false;
     };
@@ -1734,7 +1780,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
             const Tick tq = now();
             const uint32_t npr = p->n_pair_reads;
             uint64_t got = 0;
-            const int e = mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
+            const int e = p->resident ? mcx_sam_part_dev(c, d_bases, d_off, cnt, second ? 0 : 1, p->rb.names, p->rb.name_off, p->rb.qual, d_aln, d_cig, &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got) :
+                          mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
                                        p->fastq ? p->sam_qual + (second ? p->sam_part_qual[0] : 0) : nullptr, p->sam_part_qual[second ? 1 : 0], d_aln, d_cig,
                                        &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got);
             if (e) rc = e; else p->dev_bytes += got;
@@ -1808,12 +1855,16 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     formatter.join();
     writer.join();
     reader.join();
-    { BatchPtr b; while (spare.try_pop(b)) kept->objects.push_back(std::move(b)); while (parsed.try_pop(b)) kept->objects.push_back(std::move(b)); while (mapped.try_pop(b)) kept->objects.push_back(std::move(b)); }
+    // (the batch objects go back to the context with their buffers; the device buffers of the resident route only for a run that took it — HBM that a context
+    //  which has gone back to another route would hold for nothing)
+    auto keep = [&](BatchPtr &b) { if (!resident && b->res) { mcx_resident_bufs_free(b->res); b->res = nullptr; } kept->objects.push_back(std::move(b)); };
+    { BatchPtr b; while (spare.try_pop(b)) keep(b); while (parsed.try_pop(b)) keep(b); while (mapped.try_pop(b)) keep(b); }
     if (getenv("MCX_TIMING")) {
         std::string e;
         for (size_t k = 0; k < each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
     }
+    if (getenv("MCX_TIMING")) fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], resident ? " — the resident route" : "");
     if (getenv("MCX_TIMING") && dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t_m_sam);
     if (getenv("MCX_TIMING"))
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",

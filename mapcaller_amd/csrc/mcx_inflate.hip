@@ -57,6 +57,7 @@ struct Set { // one set of staging buffers: what one launch of the host form tak
     uint32_t n = 0;
     uint64_t dst_bytes = 0;
     bool busy = false;
+    bool to_dev = false; // the text went to the caller's buffer in HBM (mcx_inflate_begin_dev): none to hand out
 };
 
 } // namespace
@@ -66,6 +67,7 @@ struct mcx_inflater {
     hipStream_t stream = nullptr;
     uint64_t max_src = 0, max_dst = 0;
     uint32_t max_members = 0;
+    bool text_bufs = true; // the sets hold buffers for the text (h_dst, d_dst); false: an inflater of the resident route, whose text stays in the caller's HBM
     Set set[2];
     uint32_t next = 0, oldest = 0; // the set the next mcx_inflate_begin fills; the one the next mcx_inflate_end waits for
     mcx_deflate_member *h_check = nullptr; uint32_t *h_check_status = nullptr; // mcx_inflate_dev: the caller's members and status words, looked at by the host
@@ -110,7 +112,17 @@ extern "C" void mcx_inflater_free(mcx_inflater *f)
     delete f;
 }
 
+static int create(int device, uint64_t max_src_bytes, uint64_t max_dst_bytes, uint32_t max_members, bool text_bufs, mcx_inflater **out);
 extern "C" int mcx_inflater_create(int device, uint64_t max_src_bytes, uint64_t max_dst_bytes, uint32_t max_members, mcx_inflater **out)
+{
+    return create(device, max_src_bytes, max_dst_bytes, max_members, true, out);
+}
+// an inflater whose launches leave their text in the caller's HBM (mcx_inflate_begin_dev): staging for the compressed bytes, the members and the status words only
+int mcx_inflater_create_dev(int device, uint64_t max_src_bytes, uint32_t max_members, mcx_inflater **out)
+{
+    return create(device, max_src_bytes, 65536, max_members, false, out);
+}
+static int create(int device, uint64_t max_src_bytes, uint64_t max_dst_bytes, uint32_t max_members, bool text_bufs, mcx_inflater **out)
 {
     if (!out) return mcx_set_error(MCX_ERR_ARG, "mcx_inflater_create: null argument");
     *out = nullptr;
@@ -118,7 +130,7 @@ extern "C" int mcx_inflater_create(int device, uint64_t max_src_bytes, uint64_t 
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { (void)hipGetLastError(); return mcx_set_error(MCX_ERR_DEVICE, "mcx_inflater_create: no such device"); }
     HIP_TRY(hipSetDevice(device));
     mcx_inflater *f = new mcx_inflater();
-    f->device = device;
+    f->device = device; f->text_bufs = text_bufs;
     // (a launch holds at least one member of the largest kind: 64 KB of text, and compressed bytes that did not shrink)
     f->max_dst = max_dst_bytes ? std::max<uint64_t>(max_dst_bytes, 65536) : (8ull << 20) + 65536;
     f->max_src = max_src_bytes ? std::max<uint64_t>(max_src_bytes, 65536 + 1024) : f->max_dst + f->max_dst / 64 + 4096;
@@ -128,11 +140,11 @@ extern "C" int mcx_inflater_create(int device, uint64_t max_src_bytes, uint64_t 
     for (hipEvent_t &e : f->ev) if (rc == 0 && hipEventCreate(&e) != hipSuccess) rc = MCX_ERR_DEVICE;
     for (Set &s : f->set) {
         if (rc) break;
-        s.h_src = (uint8_t *)mcx_pinned_alloc(f->max_src + 8); s.h_dst = (uint8_t *)mcx_pinned_alloc(f->max_dst);
+        s.h_src = (uint8_t *)mcx_pinned_alloc(f->max_src + 8); s.h_dst = text_bufs ? (uint8_t *)mcx_pinned_alloc(f->max_dst) : nullptr;
         s.h_mem = (mcx_deflate_member *)mcx_pinned_alloc((size_t)f->max_members * sizeof(mcx_deflate_member));
         s.h_status = (uint32_t *)mcx_pinned_alloc((size_t)f->max_members * 4);
-        if (!s.h_src || !s.h_dst || !s.h_mem || !s.h_status) { rc = MCX_ERR_DEVICE; break; }
-        if (hipMalloc((void **)&s.d_src, f->max_src + 8) != hipSuccess || hipMalloc((void **)&s.d_dst, f->max_dst) != hipSuccess ||
+        if (!s.h_src || (text_bufs && !s.h_dst) || !s.h_mem || !s.h_status) { rc = MCX_ERR_DEVICE; break; }
+        if (hipMalloc((void **)&s.d_src, f->max_src + 8) != hipSuccess || (text_bufs && hipMalloc((void **)&s.d_dst, f->max_dst) != hipSuccess) ||
             hipMalloc((void **)&s.d_mem, (size_t)f->max_members * sizeof(mcx_deflate_member)) != hipSuccess || hipMalloc((void **)&s.d_status, (size_t)f->max_members * 4) != hipSuccess ||
             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) rc = MCX_ERR_DEVICE;
     }
@@ -187,7 +199,20 @@ void mcx_inflater_caps(const mcx_inflater *f, uint64_t *max_src, uint64_t *max_d
 // bytes of slack behind them —, and copy in, kernel and copy out are queued on the stream; returns at once.  The members must fit one launch, and at most
 // two begins may be outstanding.  end: waits for the oldest begin, hands each member's text to dst + its dst_off and its status word to status[] (may be
 // null); 0, or MCX_ERR_IO when a member failed.
+static int begin(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap);
 int mcx_inflate_begin(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint64_t dst_cap)
+{
+    if (!f->text_bufs) return mcx_set_error(MCX_ERR_ARG, "mcx_inflate_begin: the inflater has no buffers for the text");
+    return begin(f, src, src_bytes, members, n, nullptr, dst_cap);
+}
+// The same with the text left in HBM: member i's goes to d_dst[dst_off .. dst_off + isize), d_dst of dst_cap bytes on the inflater's device; any number of
+// members up to a launch's, any sum of isize (several stretches in one launch).  mcx_inflate_end then hands out the status words alone (dst: null).
+int mcx_inflate_begin_dev(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap)
+{
+    if (!d_dst) return mcx_set_error(MCX_ERR_ARG, "mcx_inflate_begin_dev: null argument");
+    return begin(f, src, src_bytes, members, n, d_dst, dst_cap);
+}
+static int begin(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap)
 {
     Set &s = f->set[f->next];
     if (s.busy) return mcx_set_error(MCX_ERR_ARG, "mcx_inflate_begin: two launches are outstanding already");
@@ -197,7 +222,7 @@ int mcx_inflate_begin(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, c
         if (const char *why = member_fault(members[i], src_bytes, dst_cap)) return mcx_set_error(MCX_ERR_ARG, std::string("mcx_inflate: ") + why);
         so += members[i].src_len; to += members[i].isize;
     }
-    if (so > f->max_src || to > f->max_dst) return mcx_set_error(MCX_ERR_ARG, "mcx_inflate_begin: more bytes than a launch holds");
+    if (so > f->max_src || (!d_dst && to > f->max_dst)) return mcx_set_error(MCX_ERR_ARG, "mcx_inflate_begin: more bytes than a launch holds");
     HIP_TRY(hipSetDevice(f->device));
     s.dst_off.resize(n);
     so = to = 0;
@@ -205,17 +230,17 @@ int mcx_inflate_begin(mcx_inflater *f, const uint8_t *src, uint64_t src_bytes, c
         const mcx_deflate_member &m = members[i];
         memcpy(s.h_src + so, src + m.src_off, m.src_len);
         mcx_deflate_member &d = s.h_mem[i];
-        d.src_off = so; d.dst_off = to; d.src_len = m.src_len; d.isize = m.isize; d.crc32 = m.crc32; d.reserved = 0;
+        d.src_off = so; d.dst_off = d_dst ? m.dst_off : to; d.src_len = m.src_len; d.isize = m.isize; d.crc32 = m.crc32; d.reserved = 0;
         s.dst_off[i] = m.dst_off;
         so += m.src_len; to += m.isize;
     }
     memset(s.h_src + so, 0, 8);
-    s.n = n; s.dst_bytes = to;
+    s.n = n; s.dst_bytes = to; s.to_dev = d_dst != nullptr;
     if (n) {
         HIP_TRY(hipMemcpyAsync(s.d_src, s.h_src, so + 8, hipMemcpyHostToDevice, f->stream));
         HIP_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, (size_t)n * sizeof(mcx_deflate_member), hipMemcpyHostToDevice, f->stream));
-        if (int rc = launch(f, s.d_src, so + 8, s.d_mem, n, s.d_dst, s.d_status)) return rc;
-        if (to) HIP_TRY(hipMemcpyAsync(s.h_dst, s.d_dst, to, hipMemcpyDeviceToHost, f->stream));
+        if (int rc = launch(f, s.d_src, so + 8, s.d_mem, n, d_dst ? d_dst : s.d_dst, s.d_status)) return rc;
+        if (to && !d_dst) HIP_TRY(hipMemcpyAsync(s.h_dst, s.d_dst, to, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(hipMemcpyAsync(s.h_status, s.d_status, (size_t)n * 4, hipMemcpyDeviceToHost, f->stream));
     }
     HIP_TRY(hipEventRecord(s.done, f->stream));
@@ -234,7 +259,7 @@ int mcx_inflate_end(mcx_inflater *f, uint8_t *dst, uint32_t *status, uint32_t *n
     HIP_TRY(hipSetDevice(f->device));
     HIP_TRY(hipEventSynchronize(s.done));
     uint32_t bad = 0;
-    for (uint32_t i = 0; i < s.n;) { // members whose texts follow one another at the caller's too leave in one copy
+    for (uint32_t i = 0; i < s.n && !s.to_dev;) { // members whose texts follow one another at the caller's too leave in one copy
         uint32_t j = i;
         uint64_t bytes = 0;
         do { bytes += s.h_mem[j].isize; j++; } while (j < s.n && s.dst_off[j] == s.dst_off[i] + bytes);

@@ -47,12 +47,58 @@ int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint3
 int mcx_inflate_begin(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint64_t dst_cap);
 int mcx_inflate_end(mcx_inflater *, uint8_t *dst, uint32_t *status, uint32_t *n_bad);
 void mcx_inflater_caps(const mcx_inflater *, uint64_t *max_src, uint64_t *max_dst, uint32_t *max_members);
+// ... and for text that stays in HBM (the resident route): an inflater without buffers for the text, and a begin whose members' dst_off point into d_dst, a buffer
+// of dst_cap bytes on the inflater's device — any sum of isize, so several stretches go in one launch; mcx_inflate_end (dst: null) hands out the status words
+int mcx_inflater_create_dev(int device, uint64_t max_src_bytes, uint32_t max_members, mcx_inflater **out);
+int mcx_inflate_begin_dev(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap);
+// mcx_sam_part for names, name offsets and NUL-padded qualities in HBM (mcx_fastq_parse_dev's outputs): nothing is copied in
+int mcx_sam_part_dev(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *d_names, const uint32_t *d_name_off,
+                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
+// mcx_fastq_parse_dev in two halves: the caller sizes its buffers from *info in between
+int mcx_fastq_dev_sizes(mcx_fastq_parser *, const mcx_fastq_in *in, mcx_fastq_info *info);
+int mcx_fastq_dev_out(mcx_fastq_parser *, const mcx_fastq_out *out, const mcx_fastq_info *info);
 // -gpu_parse (mcx_fastq.hip): the host form of mcx_fastq_parse in three steps — stage hands out the parser's page-locked staging for two texts of these sizes
 // (the reader's pool copies the batch's byte ranges into it); staged_sizes sends them to HBM and parses: *info says how many reads, odd bytes, how long the longest;
 // staged_out brings the groups of `out` (HOST pointers, page-locked ones without a further copy) back — rows with row_words 0 come ceil(longest / 16) words wide.
 int mcx_fastq_stage(mcx_fastq_parser *, const uint64_t bytes[2], uint8_t *h[2]);
 int mcx_fastq_staged_sizes(mcx_fastq_parser *, const uint64_t bytes[2], int two, uint32_t max_records, int32_t max_read_len, int32_t final, mcx_fastq_info *info);
 int mcx_fastq_staged_out(mcx_fastq_parser *, const mcx_fastq_out *out, const mcx_fastq_info *info);
+// (the file front end's readers) a BGZF member at p (n bytes left in the file): its whole size and the length of its extra field; 0 if it is not one
+static inline size_t mcx_bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen)
+{
+    if (n < 28 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
+    xlen = (size_t)p[10] | ((size_t)p[11] << 8);
+    if (12 + xlen + 8 > n) return 0;
+    for (size_t o = 12; o + 4 <= 12 + xlen;) { // the subfields of the extra field: SI1 SI2 SLEN(2) data
+        const size_t slen = (size_t)p[o + 2] | ((size_t)p[o + 3] << 8);
+        if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
+            const size_t size = ((size_t)p[o + 4] | ((size_t)p[o + 5] << 8)) + 1;
+            return (size >= 12 + xlen + 8 && size <= n) ? size : 0;
+        }
+        o += 4 + slen;
+    }
+    return 0;
+}
+// The resident route (mcx_resident.hip; -gpu_inflate -gpu_parse on BGZF FASTQ): one or two read files whose text never leaves HBM.  open: *out stays null (and
+// the call returns 0) when a file is no BGZF file named .gz or its text does not begin with '@' — the route does not apply.  next: the next batch of up to
+// per_file records a file — more members inflated as needed, the records found under the GZ rule, rows / lengths / odd bytes (and, want_sam, names, their
+// offsets and NUL-padded qualities) written to *bufs, device buffers that belong to the caller's batch object (made on first use, grown on demand, freed with
+// mcx_resident_bufs_free).  One host thread per object.
+struct mcx_resident;
+struct mcx_resident_bufs;
+struct mcx_resident_batch {
+    uint32_t n_records[2];     // records each file gave: per_file, or fewer where its records ended (then `last`)
+    bool last[2];
+    char too_long[2][128];     // the name of the read that ended a file because it is longer than max_read_len (has_too_long); whole: header_of ends a name within the header's first 100 bytes
+    bool has_too_long[2];
+    uint32_t n_reads;          // reads in the buffers: n_records[0], or 2 * n_records[0] mate by mate — 0 when file 2 gave fewer than file 1 or a read is too long
+    const uint32_t *rows, *len; const uint64_t *odd; uint32_t row_words, n_odd, longest; // mcx_stream_submit_dev's arguments
+    const uint8_t *names, *qual; const uint32_t *name_off;                              // mcx_sam_part_dev's
+};
+int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_resident **out);
+void mcx_resident_close(mcx_resident *);
+int mcx_resident_next(mcx_resident *, mcx_resident_bufs **bufs, uint32_t per_file, int32_t max_read_len, bool want_sam, mcx_resident_batch *out);
+void mcx_resident_bufs_free(mcx_resident_bufs *);
 void *mcx_pinned_alloc(size_t bytes); // page-locked host memory (null on failure); mcx_pinned_free accepts null
 void mcx_pinned_free(void *);
 

@@ -290,8 +290,21 @@ extern "C" int mcx_sam_header(const mcx_index *ix, char *out, uint64_t cap, uint
 // The file front end's -gpu_sam, for one mapped part of a batch still in its slot: names (name_off: n_reads + 1) and NUL-padded qualities (null: FASTA) from
 // page-locked host memory go behind the reads, the text is made from the part's records, CIGAR pool and (-m) the context's extras, and arrives at
 // (*text)[at ..], a page-locked buffer that grows as needed (*text_cap).  On the context's stream, waited for.
+static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
+                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
 int mcx_sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
                  const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
+{
+    return sam_part(c, d_bases, d_off, n_reads, paired, names, name_off, qual, qual_bytes, false, d_aln, d_cigar, text, text_cap, at, n_bytes);
+}
+// Its twin for names, name offsets and NUL-padded qualities that lie in HBM already (the resident route: mcx_fastq_parse_dev's outputs): nothing is copied in
+int mcx_sam_part_dev(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *d_names, const uint32_t *d_name_off,
+                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
+{
+    return sam_part(c, d_bases, d_off, n_reads, paired, d_names, d_name_off, d_qual, 0, true, d_aln, d_cigar, text, text_cap, at, n_bytes);
+}
+static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
+                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
 {
     *n_bytes = 0;
     if (n_reads == 0) return 0;
@@ -300,16 +313,19 @@ int mcx_sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint
     int rc;
     if ((rc = state_of(c, &st))) return rc;
     hipStream_t s = (hipStream_t)mcx_ctx_stream(c);
-    const uint64_t name_bytes = name_off[n_reads];
-    if ((rc = grow(&st->d_names, &st->cap_names, name_bytes + 16, "the reads' names"))) return rc;
-    if ((rc = grow(&st->d_name_off, &st->cap_name_off, (uint64_t)n_reads + 1, "the reads' names"))) return rc;
-    if (qual && (rc = grow(&st->d_qual, &st->cap_qual, qual_bytes + 16, "the reads' qualities"))) return rc;
-    HIP_TRY(hipMemcpyAsync(st->d_names, names, name_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(st->d_name_off, name_off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, s));
-    if (qual) HIP_TRY(hipMemcpyAsync(st->d_qual, qual, qual_bytes, hipMemcpyHostToDevice, s));
+    if (!on_device) {
+        const uint64_t name_bytes = name_off[n_reads];
+        if ((rc = grow(&st->d_names, &st->cap_names, name_bytes + 16, "the reads' names"))) return rc;
+        if ((rc = grow(&st->d_name_off, &st->cap_name_off, (uint64_t)n_reads + 1, "the reads' names"))) return rc;
+        if (qual && (rc = grow(&st->d_qual, &st->cap_qual, qual_bytes + 16, "the reads' qualities"))) return rc;
+        HIP_TRY(hipMemcpyAsync(st->d_names, names, name_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st->d_name_off, name_off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, s));
+        if (qual) HIP_TRY(hipMemcpyAsync(st->d_qual, qual, qual_bytes, hipMemcpyHostToDevice, s));
+    }
     mcx_sam_in in;
     memset(&in, 0, sizeof in);
-    in.bases = d_bases; in.off = d_off; in.qual = qual ? st->d_qual : nullptr; in.names = st->d_names; in.name_off = st->d_name_off;
+    in.bases = d_bases; in.off = d_off;
+    in.qual = on_device ? qual : qual ? st->d_qual : nullptr; in.names = on_device ? names : st->d_names; in.name_off = on_device ? name_off : st->d_name_off;
     in.aln = d_aln; in.cigar = d_cigar; in.n_reads = n_reads; in.paired = paired;
     if (mcx_ctx_multi(c)) {
         uint32_t n_recs = 0, n_words = 0;

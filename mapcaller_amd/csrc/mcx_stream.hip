@@ -122,13 +122,15 @@ __global__ void __launch_bounds__(256) k_neutralize(uint32_t *off, uint32_t n_re
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += gridDim.x * blockDim.x) off[r] = 0;
 }
 
-extern "C" int mcx_stream_submit_packed(mcx_ctx *c, const uint32_t *codes, uint32_t row_words, const uint32_t *len, uint32_t n_reads, const uint64_t *odd,
-                                        uint32_t n_odd)
+// 2-bit rows into a free slot and back to bytes there.  kind: where the caller's arrays lie — host memory (mcx_stream_submit_packed: over the device boundary,
+// counted in bytes_in) or the context's device (mcx_stream_submit_dev: device-to-device copies on the same copy-in stream, not counted)
+static int submit_rows(mcx_ctx *c, const uint32_t *codes, uint32_t row_words, const uint32_t *len, uint32_t n_reads, const uint64_t *odd, uint32_t n_odd, hipMemcpyKind kind,
+                       const char *who)
 {
-    if (!c || !codes || !len || n_reads == 0 || row_words == 0 || (n_odd && !odd)) return mcx_set_error(MCX_ERR_ARG, "mcx_stream_submit_packed: bad argument");
+    if (!c || !codes || !len || n_reads == 0 || row_words == 0 || (n_odd && !odd)) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": bad argument");
     if (n_reads > c->max_reads) return mcx_set_error(MCX_ERR_ARG, "batch larger than max_batch_reads");
     const uint32_t row_max = (uint32_t)(c->rlen_max + 15) / 16;
-    if (row_words > row_max) return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_stream_submit_packed: rows are longer than max_read_len");
+    if (row_words > row_max) return mcx_set_error(MCX_ERR_UNSUPPORTED, std::string(who) + ": rows are longer than max_read_len");
     HIP_TRY(hipSetDevice(c->idx->device));
     mcx_ctx::Slot *sl = nullptr;
     int rc = stream_slot(c, &sl);
@@ -152,9 +154,9 @@ extern "C" int mcx_stream_submit_packed(mcx_ctx *c, const uint32_t *codes, uint3
         c->scan_tmp_bytes = need + 256;
         HIP_TRY(hipMalloc(&c->d_scan_tmp, c->scan_tmp_bytes));
     }
-    if ((rc = bulk_copy(c, sl->d_codes, codes, (size_t)n_reads * row_words * 4, hipMemcpyHostToDevice, s))) return rc;
-    if ((rc = bulk_copy(c, sl->d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s))) return rc;
-    if (n_odd && (rc = bulk_copy(c, sl->d_odd, odd, (size_t)n_odd * 8, hipMemcpyHostToDevice, s))) return rc;
+    if ((rc = bulk_copy(c, sl->d_codes, codes, (size_t)n_reads * row_words * 4, kind, s))) return rc;
+    if ((rc = bulk_copy(c, sl->d_len, len, (size_t)n_reads * 4, kind, s))) return rc;
+    if (n_odd && (rc = bulk_copy(c, sl->d_odd, odd, (size_t)n_odd * 8, kind, s))) return rc;
     HIP_TRY(hipMemsetAsync(sl->d_off, 0, 4, s));
     size_t tmp = c->scan_tmp_bytes;
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->d_scan_tmp, tmp, sl->d_len, sl->d_off + 1, (int)n_reads, s));
@@ -183,8 +185,20 @@ extern "C" int mcx_stream_submit_packed(mcx_ctx *c, const uint32_t *codes, uint3
     }
     HIP_TRY(hipEventRecord(sl->in_ready, s));
     sl->n_reads = n_reads; sl->state = 1; sl->seq = ++c->stream_seq;
-    c->stream_bytes_in += (uint64_t)n_reads * row_words * 4 + (uint64_t)n_reads * 4 + (uint64_t)n_odd * 8;
+    if (kind == hipMemcpyHostToDevice) c->stream_bytes_in += (uint64_t)n_reads * row_words * 4 + (uint64_t)n_reads * 4 + (uint64_t)n_odd * 8;
     return 0;
+}
+
+extern "C" int mcx_stream_submit_packed(mcx_ctx *c, const uint32_t *codes, uint32_t row_words, const uint32_t *len, uint32_t n_reads, const uint64_t *odd,
+                                        uint32_t n_odd)
+{
+    return submit_rows(c, codes, row_words, len, n_reads, odd, n_odd, hipMemcpyHostToDevice, "mcx_stream_submit_packed");
+}
+
+extern "C" int mcx_stream_submit_dev(mcx_ctx *c, const uint32_t *d_codes, uint32_t row_words, const uint32_t *d_len, uint32_t n_reads, const uint64_t *d_odd,
+                                     uint32_t n_odd)
+{
+    return submit_rows(c, d_codes, row_words, d_len, n_reads, d_odd, n_odd, hipMemcpyDeviceToDevice, "mcx_stream_submit_dev");
 }
 
 extern "C" int mcx_stream_submit(mcx_ctx *c, const uint8_t *bases, const uint32_t *off, uint32_t n_reads)
