@@ -1,7 +1,7 @@
 // mapcaller_amd/csrc/mcx_fastq.h — the reader's rules for FASTQ text (plain, and the .gz readers'), once, for the device (mcx_fastq.hip) and for the host
 // (tests/hostemu/fastq_check.cpp).
 //
-// Restated from MappedFastq::parse and header_of of mcx_files.cpp, which every golden SAM pins to the reference (GetNextEntry, GetData.cpp:32-55;
+// Restated from MappedFastq::parse and header_of of mcx_reader.h, which every golden SAM pins to the reference (GetNextEntry, GetData.cpp:32-55;
 // IdentifyHeaderBegPos / IdentifyHeaderEndPos, :3-20), and from pack_word of the same file:
 //   a line     what getline gives: up to and including '\n'; the text's last line may lack it
 //   record k   lines 4k .. 4k+3 counted from the text's first byte, whatever they hold
@@ -10,7 +10,7 @@
 //   quality    the '+' line is skipped; q_take = min(length of the quality line with its newline, rlen), 0 when the line is absent
 //   stops      no header line (END); no sequence line or rlen == 0 (EMPTY: what ends the reference's input, GetData.cpp:91); rlen > max_read_len
 //   rows       A 0, C 1, G 2, T 3, sixteen bases to a word, the first in the top bits; any other byte has code 0 and is listed
-// THE GZ RULE (MCX_FASTQ_RULE_GZ), restated from Parser::line / Parser::entry of mcx_files.cpp in gz_mode_ with FASTQ input (gzGetNextEntry: gzgets with a
+// THE GZ RULE (MCX_FASTQ_RULE_GZ), restated from Parser::line / Parser::entry of mcx_reader.h in gz_mode_ with FASTQ input (gzGetNextEntry: gzgets with a
 // 1024-byte buffer, strlen semantics, GetData.cpp:101-128):
 //   a piece    what gzgets(buffer, 1024) gives: at s, the bytes up to and including the first '\n' within text[s, s + 1023); without one, those 1023 bytes
 //              when there are as many, else the rest of the text (unfinished, the text's last).  The next piece begins right behind: the pieces tile the
@@ -29,7 +29,7 @@
 namespace mcx {
 namespace fq {
 
-// header_of (mcx_files.cpp): l[0 .. len) is the header line with its newline, len >= 1
+// header_of (mcx_reader.h): l[0 .. len) is the header line with its newline, len >= 1
 static inline MCX_HD void header_of(const uint8_t *l, uint32_t len, uint32_t &p1, uint32_t &p2)
 {
     const uint32_t lim = len > 100u ? 100u : len;

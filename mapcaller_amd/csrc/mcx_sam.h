@@ -1,7 +1,7 @@
 // mapcaller_amd/csrc/mcx_sam.h — one read's SAM line(s) from its record, for the device and (tests/hostemu) for the host.
 //
 // GenerateSingleSamStream / GeneratePairedSamStream (reference src/SamReport.cpp:324-488) restated from sam_line(), sam_record()
-// and comp_char() of mcx_files.cpp, which every golden SAM pins to the reference byte for byte:
+// and comp_char() of mcx_batch.h, which every golden SAM pins to the reference byte for byte:
 //   QNAME \t FLAG \t  then  "*\t0\t0\t*\t*\t0\t0\t"  for an unmapped read, or
 //                           RNAME \t POS \t MAPQ \t CIGAR  and  "\t=\t" PNEXT \t TLEN \t  (has_mate)  |  "\t*\t0\t0\t"
 //   SEQ \t QUAL  then  "\tNM:i:" nm "\tAS:i:" as "\tXS:i:" xs "\n"  |  "\tAS:i:0\tXS:i:0\n"  (unmapped)

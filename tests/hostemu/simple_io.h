@@ -1,5 +1,5 @@
 // tests/hostemu/simple_io.h — TEST HARNESS: a deliberately plain, single-threaded second
-// implementation of what the product does in mcx_files.cpp (reading FASTA/FASTQ(.gz) like
+// implementation of what the product does in its file front end (mcx_reader.h, mcx_batch.h) (reading FASTA/FASTQ(.gz) like
 // GetData.cpp, SAM text like SamReport.cpp) and of the avgDist replay the product runs on the
 // device (k_chunk_sums / k_check_est).  The harness maps with the product's device headers and
 // writes SAM through these, so the two implementations check each other against the golden files.

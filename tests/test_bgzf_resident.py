@@ -249,7 +249,7 @@ def write_ordinary_gz(path, data):
 
 
 def test_the_restatement_equals_the_products_own_reader(packer, vectors, tmp_path):
-    """The vectors as ordinary .gz files through mcx_files.cpp's Parser (tests/hostemu/parser_check.cpp): names, bases and qualities.  The reader decides FASTQ
+    """The vectors as ordinary .gz files through mcx_reader.h's Parser (tests/hostemu/parser_check.cpp): names, bases and qualities.  The reader decides FASTQ
     or FASTA by the text's first byte, so the vectors that do not begin with '@' are left to the other tests."""
     d = os.path.join(ROOT, "tests", "hostemu")
     subprocess.run(["make", "-C", d, "libparser_check.so"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

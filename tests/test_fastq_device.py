@@ -2,7 +2,7 @@
 (-gpu_parse).
 
 Expectations come from a restatement, in Python, of the reader's rules for plain FASTQ (GetData.cpp:3-20, :32-55 as MappedFastq::parse and header_of of
-mcx_files.cpp hold them): a line is what getline gives, record k is lines 4k .. 4k+3, the last byte of the sequence line goes, min(quality line, read)
+mcx_reader.h hold them): a line is what getline gives, record k is lines 4k .. 4k+3, the last byte of the sequence line goes, min(quality line, read)
 bytes of quality count; rows and odd bytes come from the library's host packer mcx_pack_row.  Nothing is expected from the code under test.
 CPU: the ABI surface; the rules compiled for the host (mapcaller_amd/csrc/mcx_fastq.h through tests/hostemu/fastq_check.cpp) on every vector and on
 the toy and var read files, with guard bytes round each output; the same file as a stand-alone program under -fsanitize=address,undefined on the

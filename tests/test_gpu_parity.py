@@ -653,6 +653,21 @@ def test_input_side_cases(api, io_golden, tmp_path):
     ix.close()
 
 
+@pytest.mark.parametrize("switch", ["MCX_SERIAL_PARSER", "MCX_SAM_MMAP"])
+def test_environment_switches_of_the_front_end(api, golden, tmp_path, monkeypatch, switch):
+    """The `toy` pair with MCX_SERIAL_PARSER=1 (plain FASTQ through the sequential reader instead of the mapped one) and with MCX_SAM_MMAP=1 (the writer
+    copies the text into a mapping of the output file instead of using positioned writes): the golden SAM, byte for byte."""
+    g = golden["toy"]
+    monkeypatch.setenv(switch, "1")
+    ix = api.Index(g["prefix"], device=0)
+    mp = api.Mapper(ix, alg="ksw2", max_batch_reads=1000)
+    out = str(tmp_path / "gpu.sam")
+    st = mp.map_files(g["r1"], g["r2"], out)
+    assert st["reads"] == 2 * open(g["r1"], "rb").read().count(b"\n") // 4
+    assert open(out, "rb").read() == open(g["sam"]["ksw2"], "rb").read(), sam_diff(g["sam"]["ksw2"], out)
+    mp.close(); ix.close()
+
+
 def test_plain_gz_pairs_through_the_parallel_reader(api, golden, tmp_path):
     """The `var` pairs as ordinary gzip files (levels 1, 6, 9): the SAM of the plain files."""
     import gzip

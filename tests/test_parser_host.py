@@ -1,4 +1,4 @@
-"""The product's sequential reader (mcx_files.cpp: Parser — ordinary .gz through the parallel inflater, bgzip's container, zlib's one thread, plain FASTA with
+"""The product's sequential reader (mcx_reader.h: Parser — ordinary .gz through the parallel inflater, bgzip's container, zlib's one thread, plain FASTA with
 multi-line records) on the host, without a GPU, through tests/hostemu/parser_check.cpp: the records it hands out against a restatement of the reference's
 text rules (GetData.cpp:3-20 header trimming, :45-55 / :101-128 record shapes, the 1024-byte line buffer of the .gz reader, the last byte of a sequence
 line dropped) in Python — on files large enough that records straddle the feeder's 8 MB blocks at arbitrary offsets, with lines longer than the room a
@@ -23,6 +23,8 @@ def parser_lib():
     L = ctypes.CDLL(os.path.join(d, "libparser_check.so"))
     L.parser_dump.restype = ctypes.c_longlong
     L.parser_dump.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+    L.mapped_dump.restype = ctypes.c_longlong
+    L.mapped_dump.argtypes = L.parser_dump.argtypes
     return L
 
 
@@ -53,12 +55,19 @@ def expect_fastq(raw, gz):
     return out
 
 
-def dump(L, path, tmp_path, per_take=777, max_len=100000):
+def dump_text(L, path, tmp_path, per_take=777, max_len=100000, mapped=False):
+    """The records of `path` from the sequential reader, or (mapped: per_take is then the pool's threads) from the mapped reader of plain FASTQ: their
+    number and the dump as it was written."""
     out = str(tmp_path / "dump.txt")
     err = ctypes.create_string_buffer(512)
-    n = L.parser_dump(path.encode(), max_len, per_take, out.encode(), err, 512)
+    n = (L.mapped_dump if mapped else L.parser_dump)(path.encode(), max_len, per_take, out.encode(), err, 512)
     assert n >= 0, err.value
-    recs = [tuple(l.split(b"\t")) for l in open(out, "rb").read().split(b"\n")[:-1]]
+    return n, open(out, "rb").read()
+
+
+def dump(L, path, tmp_path, per_take=777, max_len=100000):
+    n, text = dump_text(L, path, tmp_path, per_take, max_len)
+    recs = [tuple(l.split(b"\t")) for l in text.split(b"\n")[:-1]]
     assert len(recs) == n
     return recs
 
@@ -148,3 +157,43 @@ def test_a_nul_cuts_a_gz_line_short_in_whatever_block_it_lies(parser_lib, tmp_pa
             assert a == (b[0], lines[4 * k + 1][: cut - 1], lines[4 * k + 3][: cut - 1]), (k, a)
         else:
             assert a == b, (k, a[0], b[0])
+
+
+def both_readers(L, raw, tmp_path):
+    """The records of the plain FASTQ text `raw` from the sequential reader and from the mapped one (four threads): (number, dump) of each — the dumps as
+    bytes, since a quality line shorter than its read is taken with its newline."""
+    path = str(tmp_path / "plain.fq")
+    with open(path, "wb") as f:
+        f.write(raw)
+    return dump_text(L, path, tmp_path), dump_text(L, path, tmp_path, per_take=4, mapped=True)
+
+
+def test_mapped_and_sequential_readers_agree_on_the_golden_reads(parser_lib, tmp_path):
+    """Every FASTQ read file of the golden sets, unpacked: MappedFastq (open, count, finish, parse over the whole file) hands out the records that Parser
+    does.  MCX_SERIAL_PARSER=1 — the sequential reader on plain files, which the GPU tests hold against the golden SAM — rests on that."""
+    import glob
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "*", "*.fq.gz")))
+    assert len(files) >= 13, files
+    for fn in files:
+        raw = gzip.open(fn, "rb").read()
+        seq, mapped = both_readers(parser_lib, raw, tmp_path)
+        assert seq[0] == raw.count(b"\n") // 4, fn
+        assert mapped == seq, fn
+
+
+def _records(k):
+    return b"".join(b"@r%d words\n" % i + (b"ACGTN" * 8)[: 17 + i] + b"\n+\n" + b"I" * (20 + i) + b"\n" for i in range(k))
+
+
+@pytest.mark.parametrize("raw,n", [
+    (_records(5)[:-1], 5),                                     # a last line without a newline
+    (_records(4) + b"@last\nACGTACGT\n", 5),                    # a last record cut after its sequence line
+    (_records(4) + b"@last\nACGTACGT", 5),                      # ... whose sequence line has no newline either
+    (_records(4) + b"@last\n", 4),                              # ... and one cut after its header: no record
+    (_records(2) + b"@q\nACGTACGTAC\n+\n" + _records(3), 6),    # no quality line before the next '@': a record is four lines, whatever they hold
+], ids=["no_final_newline", "cut_after_sequence", "cut_after_sequence_no_newline", "cut_after_header", "no_quality_line"])
+def test_mapped_and_sequential_readers_agree_on_files_that_are_not_well_formed(parser_lib, tmp_path, raw, n):
+    """Hand-made plain FASTQ with a damaged end or a missing line: both readers hand out the same records (and as many as the four-line rule gives)."""
+    seq, mapped = both_readers(parser_lib, raw, tmp_path)
+    assert seq[0] == n
+    assert mapped == seq
