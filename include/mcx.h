@@ -484,8 +484,8 @@ int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t ca
 /* ---- FASTQ text parsed on the device ---------------------------------------------------------------
  * Replaces the host reader's parse and pack of plain FASTQ (MappedFastq::parse, header_of and mcx_pack_row; the reference's GetNextEntry,
  * GetData.cpp:3-20, :32-55) for text that lies in HBM already — what mcx_inflate_dev delivers — and produces exactly the arrays
- * mcx_map_batch_dev, mcx_sam_in and mcx_stream_submit_packed / mcx_stream_submit_dev take.  FASTQ only (FASTA is not covered), under one of two rules
- * (mcx_fastq_parser_set_rule).  THE PLAIN RULE, the default: a line is what getline gives (up to and including '\n', the text's last line possibly without one).
+ * mcx_map_batch_dev, mcx_sam_in and mcx_stream_submit_packed / mcx_stream_submit_dev take.  FASTQ (the default) or FASTA (mcx_fastq_parser_set_format, below),
+ * under one of two rules (mcx_fastq_parser_set_rule).  THE PLAIN RULE, the default: a line is what getline gives (up to and including '\n', the text's last line possibly without one).
  * Record k of a text is its lines 4k .. 4k+3 counted from the text's first byte, whatever they hold: the name by the reference's header rule, rlen =
  * the sequence line's length less one (its last byte goes, newline or not), the '+' line skipped, q_take = min(quality line with its newline, rlen),
  * 0 when that line is absent.  A text's records end at the first of: max_records taken (MORE); with final == 0 a record whose four lines do not all
@@ -498,6 +498,17 @@ int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t ca
  * the sequence piece less one (0 for 0); q_take = min(C length of the fourth piece, rlen).  The stops are the plain rule's with pieces for lines; with final == 0
  * a record is taken only when its four pieces are complete (each ends in '\n' or is 1023 bytes long).  consumed[t] is always a piece start of its line, so a
  * caller that carries text[consumed ..) forward gets the same pieces again.  Texts without any NUL do not pay for the C lengths.
+ * FASTA (MCX_READS_FASTA; the reference's GetNextEntry, GetData.cpp:56-77, and gzGetNextEntry, :101-128).  PLAIN RULE: line 0 of the text is a header whatever it
+ * holds, and so is every later line whose first byte is '>'; record k runs from its header to the next header or the text's end.  The name is the header rule's;
+ * the sequence is every non-header line less its last byte (newline or not) back to back — an empty line gives nothing, '\r' and a '>' inside a line are bases,
+ * a NUL does not end a line —, rlen their sum, q_take = 0.  Stops: no header line (END), rlen == 0 (EMPTY: a header behind a header, a header last), rlen >
+ * max_read_len (TOO_LONG), max_records taken (MORE).  With final == 0 a record is taken only when a later header line has begun inside the text (its sequence is
+ * known to be complete); an unfinished last record that already holds more than max_read_len bases stops with TOO_LONG, so that a streaming caller makes progress
+ * or fails; consumed[t] is the start of the first header line that belongs to no taken record: a text carried from there gives the same records.  A record's
+ * seq is the offset of the first byte behind its header line and rlen the total: the bases are NOT contiguous in the text — take the bases / off group.  The
+ * line table covers the whole text: scratch of about 24 bytes per line, grown on demand (MCX_ERR_DEVICE when HBM has no room), and one more wait inside the call.
+ * GZ RULE: record k is pieces 2k and 2k + 1 — header and one sequence piece —, otherwise as above; with final == 0 a record is taken when both pieces are complete.
+ * Under either rule there is no quality: the qual group, when given, is filled with NULs.
  * A parser is an object of its own like an inflater: one device, a non-blocking stream of its own, scratch in HBM (about 64 bytes per record of
  * max_records and 4 bytes per 4 KB of text) and page-locked staging for the host form, both growing on demand.  One host thread per object.
  *   n_records[t], stop[t]   records taken of text t and why no more (an mcx_fastq_stop)
@@ -522,6 +533,8 @@ int  mcx_fastq_parser_create(int device, uint64_t max_text_bytes, uint32_t max_r
 void mcx_fastq_parser_free(mcx_fastq_parser *);
 enum mcx_fastq_rule { MCX_FASTQ_RULE_PLAIN = 0, MCX_FASTQ_RULE_GZ = 1 };
 int  mcx_fastq_parser_set_rule(mcx_fastq_parser *, int rule); /* the rule of the parser's following calls; MCX_ERR_ARG: no such rule */
+enum mcx_reads_format { MCX_READS_FASTQ = 0, MCX_READS_FASTA = 1 };
+int  mcx_fastq_parser_set_format(mcx_fastq_parser *, int format); /* what the parser's following calls take the text for (sticky, like the rule); MCX_ERR_ARG: no such format */
 
 typedef struct mcx_fastq_rec { uint32_t name, name_len, seq, rlen, qual, q_take; } mcx_fastq_rec; /* 24 bytes; offsets into the record's own text */
 enum mcx_fastq_stop { MCX_FASTQ_MORE = 0, MCX_FASTQ_END = 1, MCX_FASTQ_EMPTY = 2, MCX_FASTQ_TOO_LONG = 3 };
@@ -561,12 +574,16 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then.
  * device_inflate (mapcaller-mi355x -gpu_inflate): a read file that is BGZF is inflated by an mcx_inflater of its own on the context's device, a stretch of
  * 8 MB of text per call, the next stretch's bytes staged meanwhile; the reader's pool of inflate threads is not created.  Same reads, same end of
- * the input at a damaged member.  Ordinary .gz, plain files and FASTA are read as before.
+ * the input at a damaged member.  Ordinary .gz and plain files are read as before.
  * device_parse (mapcaller-mi355x -gpu_parse): where the input is plain FASTQ that the front end maps into memory, the byte range of each of this shard's batches goes
  * through page-locked staging to an mcx_fastq_parser of its own on the context's device — about 0.3 KB of HBM per read of a batch, taken after the context's —, and
- * records, 2-bit rows, lengths and odd bytes come back: the reader's threads only copy.  Same reads, same end of the input, same error texts.  .gz, BGZF and FASTA
- * are read as before.
- * device_inflate AND device_parse, THE RESIDENT ROUTE: where every read file of the call is BGZF FASTQ (named .gz, first text byte '@': one file, or two as pairs),
+ * records, 2-bit rows, lengths and odd bytes come back: the reader's threads only copy.  Same reads, same end of the input, same error texts.  Plain FASTA (a
+ * regular file not named .gz whose first byte is not '@': one file, or two as pairs; not sharded, not -p) no longer goes through one sequential reader per
+ * file: the reader thread hands the files' bytes to the parser in chunks (final = 0, text[consumed ..) carried on, more bytes when a chunk holds too few
+ * records, final = 1 at the end) and a batch's bases, offsets, names and name offsets come back into the batch's own buffer, where the host formatter,
+ * device_sam and -m find them as the sequential reader leaves them; rows, lengths and odd bytes enter the slot as above (route: MCX_ROUTE_PARSE).  .gz and BGZF
+ * are read as before, and so is FASTA under -p or in a sharded run.
+ * device_inflate AND device_parse, THE RESIDENT ROUTE: where every read file of the call is BGZF (named .gz) and all are FASTQ (first text byte '@') or all FASTA (any other: GZ-rule FASTA, no qualities) — one file, or two as pairs —,
  * the run is not sharded, -p is off and the SAM text — if any is made — is device_sam's, the reads stay in HBM from the compressed bytes to the records: the host
  * walks the members and stages the compressed bytes; an inflater per file takes several 8 MB stretches per launch and leaves their text in a buffer in HBM; one
  * mcx_fastq_parser under the GZ rule finds a batch's records in it (final = 0, text[consumed ..) carried to the next batch), packs rows, lengths and odd bytes

@@ -72,7 +72,7 @@ SYMBOLS = [
     "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
     "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
-    "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route",
+    "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -258,6 +258,7 @@ ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
 MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 # mcx_fastq_rec: one FASTQ record as offsets into its own text; mcx_fastq_stop
 FASTQ_RULE_PLAIN, FASTQ_RULE_GZ = 0, 1  # mcx_fastq_rule
+READS_FASTQ, READS_FASTA = 0, 1  # mcx_reads_format
 ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
@@ -378,6 +379,8 @@ def lib() -> C.CDLL:
     L.mcx_files_route.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.mcx_fastq_parser_set_rule.restype = C.c_int
     L.mcx_fastq_parser_set_rule.argtypes = [C.c_void_p, C.c_int]
+    L.mcx_fastq_parser_set_format.restype = C.c_int
+    L.mcx_fastq_parser_set_format.argtypes = [C.c_void_p, C.c_int]
     L.mcx_stream_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_map32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_mapped32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -598,9 +601,9 @@ class Mapper:
         (self.avg) carries over from call to call like the reference's globals (a new library starts a
         new 200-read chunk); ``append_sam``: a further library of the same run; ``device_sam`` = -gpu_sam: the
         SAM text is made on the device (the same bytes); ``device_inflate`` = -gpu_inflate: read files that are BGZF are inflated on the
-        device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files are parsed and packed to 2-bit rows on
-        the device (the same reads, the same end of the input; other input is read as before).  ``device_inflate`` and ``device_parse`` together, on BGZF
-        FASTQ files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
+        device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files, and plain FASTA files (one, or two as pairs; not sharded, not
+        interleaved), are parsed and packed to 2-bit rows on the device (the same reads, the same end of the input; other input is read as before).
+        ``device_inflate`` and ``device_parse`` together, on BGZF FASTQ or FASTA files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
         parse, pack, map and SAM text all in HBM.  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
@@ -994,6 +997,10 @@ class FastqParser:
     def set_rule(self, rule: int) -> None:
         """mcx_fastq_parser_set_rule: FASTQ_RULE_PLAIN or FASTQ_RULE_GZ for the calls that follow"""
         _check(lib().mcx_fastq_parser_set_rule(self._h, rule), "mcx_fastq_parser_set_rule")
+
+    def set_format(self, fmt: int) -> None:
+        """mcx_fastq_parser_set_format: READS_FASTQ (the default) or READS_FASTA for the calls that follow (FASTA: no qualities; under the plain rule multi-line records)"""
+        _check(lib().mcx_fastq_parser_set_format(self._h, fmt), "mcx_fastq_parser_set_format")
 
     @staticmethod
     def _structs(ptr, size, texts, max_records, max_read_len, final, o):

@@ -20,7 +20,21 @@
 //              length.  rlen = C length of the sequence piece less one (0 for 0); q_take = min(C length of the fourth piece, rlen), 0 when it is absent
 //   stops      as under the plain rule, with pieces for lines
 //   final == 0 a record is taken only when its four pieces are complete: each ends in '\n' or is 1023 bytes long
-// FASTA is covered by neither rule.
+// FASTA (MCX_READS_FASTA), restated from Parser::entry of mcx_reader.h with FASTA input, which the golden SAMs pin to the reference (GetNextEntry,
+// GetData.cpp:56-77; gzGetNextEntry, :101-128).  Lines and pieces are those above.
+// PLAIN FASTA:
+//   a header   line 0 of the text whatever it holds, and every later line whose first byte is '>'
+//   record k   from its header to the next header or the text's end; the name is header_of over the header line
+//   sequence   every non-header line less its last byte (newline or not), back to back: an empty line gives nothing, '\r' and a '>' behind a line's first
+//              byte are bases, a NUL does not end a line (the host reader copies len - 1 bytes); rlen their sum, q_take = 0
+//   stops      no header line (END); rlen == 0 — a header behind a header, a header last — (EMPTY); rlen > max_read_len (TOO_LONG)
+//   final == 0 a record is taken only when a later header line has begun inside the text; an unfinished last record that holds more than max_read_len
+//              bases already stops with TOO_LONG (a streaming caller makes progress or fails); consumed is the start of the first header line that
+//              belongs to no taken record, so a text carried from there begins with a header and gives the same records
+//   rec        seq: the first byte behind the header line; rlen the total — the bases are NOT contiguous in the text: take the bases / off group
+//   tables     per line L its header flag and payload (fa_line); hn[], bo[] their exclusive sums over lines 0 .. n_lines (the last entry: the totals);
+//              hl[k] the line of header k, hl[n_headers] = n_lines — a record's rlen is a difference of two sums
+// GZ-RULE FASTA: the GZ rule with record k = pieces 2k, 2k + 1 and no quality (stride 2 for 4 below).
 #ifndef MCX_FASTQ_H
 #define MCX_FASTQ_H
 #include "mcx_types.h"
@@ -110,9 +124,10 @@ static inline MCX_HD uint32_t gz_c_len(const uint8_t *p, uint32_t len, bool any_
     return len;
 }
 // record_of under the GZ rule: ps[] / n_p the piece table in the place of ls[] / n_nl; any_nul: the text holds a NUL somewhere
-static inline MCX_HD uint32_t gz_record_of(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k, int32_t max_read_len, bool any_nul, mcx_fastq_rec &rec)
+// stride: pieces to a record, 4 (FASTQ) or 2 (FASTA: no quality)
+static inline MCX_HD uint32_t gz_record_of(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k, int32_t max_read_len, bool any_nul, mcx_fastq_rec &rec, uint32_t stride = 4)
 {
-    const uint64_t L = 4ull * k;
+    const uint64_t L = (uint64_t)stride * k;
     uint32_t s, len;
     if (!line_of(ps, n_p, bytes, L, s, len)) return MCX_FASTQ_END;
     uint32_t cl = gz_c_len(text + s, len, any_nul);
@@ -124,19 +139,51 @@ static inline MCX_HD uint32_t gz_record_of(const uint8_t *text, uint32_t bytes, 
     cl = gz_c_len(text + s, len, any_nul);
     rec.seq = s; rec.rlen = cl ? cl - 1 : 0;
     uint32_t q, ql;
-    if (line_of(ps, n_p, bytes, L + 3, q, ql)) ql = gz_c_len(text + q, ql, any_nul); else { q = 0; ql = 0; }
+    if (stride == 4 && line_of(ps, n_p, bytes, L + 3, q, ql)) ql = gz_c_len(text + q, ql, any_nul); else { q = 0; ql = 0; }
     rec.qual = q; rec.q_take = ql < rec.rlen ? ql : rec.rlen;
     if (rec.rlen == 0) return MCX_FASTQ_EMPTY;
     if ((int64_t)rec.rlen > (int64_t)max_read_len) return MCX_FASTQ_TOO_LONG;
     return MCX_FASTQ_MORE;
 }
 // with final == 0: record k is taken only when its four pieces are complete — the first three are when the fourth exists (an unfinished piece is the text's last)
-static inline MCX_HD bool gz_record_whole(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k)
+static inline MCX_HD bool gz_record_whole(const uint8_t *text, uint32_t bytes, const uint32_t *ps, uint64_t n_p, uint32_t k, uint32_t stride = 4)
 {
     uint32_t s, len;
-    if (!line_of(ps, n_p, bytes, 4ull * k + 3, s, len)) return false;
+    if (!line_of(ps, n_p, bytes, (uint64_t)stride * k + stride - 1, s, len)) return false;
     return len == kGzPiece || text[s + len - 1] == '\n';
 }
+
+// ---- plain FASTA ----------------------------------------------------------------------------------------------
+// lines of the text: its newlines, and an unterminated last line; ls[] holds the starts of lines 0 .. n_nl
+static inline MCX_HD uint32_t fa_n_lines(const uint32_t *ls, uint64_t n_nl, uint32_t bytes) { return (uint32_t)n_nl + (ls[n_nl] < bytes ? 1u : 0u); }
+// line L: whether it is a header, and the bases it gives (0, 0 from n_lines on: what the exclusive sums are taken of)
+static inline MCX_HD void fa_line(const uint8_t *text, uint32_t bytes, const uint32_t *ls, uint64_t n_nl, uint32_t n_lines, uint32_t L, uint32_t &hdr, uint32_t &pay)
+{
+    hdr = pay = 0;
+    if (L >= n_lines) return;
+    const uint32_t s = ls[L], len = (L < n_nl ? ls[L + 1] : bytes) - s;
+    if (L == 0 || text[s] == '>') hdr = 1; else pay = len - 1;
+}
+// Record k: why the records end before it, or MCX_FASTQ_MORE — with `taken` when it is one to take (final == 0: not the text's last).  n_hdr = hn[n_lines].
+static inline MCX_HD uint32_t fa_record_of(const uint8_t *text, uint32_t bytes, const uint32_t *ls, uint64_t n_nl, const uint32_t *bo, const uint32_t *hl, uint32_t n_hdr, uint32_t k,
+                                           int32_t max_read_len, int32_t final, mcx_fastq_rec &rec, bool &taken)
+{
+    taken = false;
+    if (k >= n_hdr) return final ? MCX_FASTQ_END : MCX_FASTQ_MORE;
+    const uint32_t h = hl[k], s = ls[h], len = (h < n_nl ? ls[h + 1] : bytes) - s;
+    uint32_t p1, p2;
+    header_of(text + s, len, p1, p2);
+    rec.name = s + p1; rec.name_len = p2 > p1 ? p2 - p1 : 0;
+    rec.seq = s + len; rec.rlen = bo[hl[k + 1]] - bo[h]; rec.qual = 0; rec.q_take = 0;
+    const bool too_long = (int64_t)rec.rlen > (int64_t)max_read_len;
+    if (!final && k + 1 >= n_hdr) return too_long ? MCX_FASTQ_TOO_LONG : MCX_FASTQ_MORE; // (unfinished: more of it may follow)
+    if (rec.rlen == 0) return MCX_FASTQ_EMPTY;
+    if (too_long) return MCX_FASTQ_TOO_LONG;
+    taken = true;
+    return MCX_FASTQ_MORE;
+}
+// the first byte that belongs to none of the n records taken
+static inline MCX_HD uint32_t fa_consumed(const uint32_t *ls, const uint32_t *hl, uint32_t n_hdr, uint32_t n, uint32_t bytes) { return n < n_hdr ? ls[hl[n]] : bytes; }
 
 static inline MCX_HD uint32_t code_of(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; } // 4: not upper-case ACGT
 static inline MCX_HD uint64_t odd_entry(uint32_t read, uint32_t pos, uint8_t c) { return ((uint64_t)read << 32) | ((uint64_t)pos << 8) | c; }

@@ -14,6 +14,12 @@
 // the host then reads the totals (the one wait in the middle), judges the caller's capacities, and queues
 //   k_gather    a wavefront per read: bases, NUL-padded qualities, names to their offsets
 //   k_rows      one lane per word of a row; k_odd<true> a wavefront per read writes its odd bytes in position order at the read's offset
+// FASTA (mcx_fastq_parser_set_format).  Under the GZ rule the same kernels with two pieces to a record.  Under the plain rule a record has no fixed number of
+// lines, so the line table covers the whole text — the host reads the text's newline count behind the first sum (one more wait) and grows the scratch — and
+//   k_fa_lines   a lane per line: is it a header, how many bases does it give; two exclusive sums: every header's record number, every line's base offset
+//   k_fa_heads   a lane per line: header number k lies in line hl[k]
+//   k_fa_records a lane per record: fa_record_of — rlen is a difference of two sums; the stop as in k_records
+//   k_fa_gather  a wavefront per read walks its lines into the contiguous layout, in scratch of the parser's: k_odd and k_rows then read the bases there
 // No kernel waits for another workgroup; every loop is bounded by the text's or a record's length; every load lies inside text[0 .. bytes) — the
 // 16-byte loads start at the 16-byte boundary at or before the text's first byte, and the chunks that hold the text's head and tail go byte by byte.
 #include <hip/hip_runtime.h>
@@ -49,6 +55,9 @@ struct Text { // one text of a call, as the kernels see it
     uint32_t *cnt, *pre;     // [n_blocks + 1] newlines per block, their exclusive sums (pre[n_blocks]: all of them)
     uint32_t *ls;            // [4 * eff_max + 1] line starts
     uint32_t *pc, *po, *ps;  // GZ rule, [4 * eff_max + 1] each: pieces per line, their exclusive sums, piece starts
+    uint64_t ls_last;        // the last line start anyone asks for: 4 * eff_max; plain FASTA: n_nl
+    uint32_t n_nl;           // plain FASTA: the text's newlines, as the host read them from pre[n_blocks]
+    uint32_t *fh, *fp, *hn, *bo, *hl; // plain FASTA, [n_nl + 2] each: a line's header flag and payload, their exclusive sums, the headers' lines
     mcx_fastq_rec *recs;     // [eff_max]
 };
 struct Job {
@@ -56,10 +65,13 @@ struct Job {
     uint32_t nt, upper;      // texts; nt * eff_max(largest): the reads a call can give
     int32_t max_read_len, final;
     int32_t rule;            // MCX_FASTQ_RULE_*
+    uint32_t stride;         // lines or pieces to a record: 4, FASTA under the GZ rule 2
+    int32_t fa;              // plain FASTA: the kernels of its own
 };
 struct DevInfo { // what the kernels tell the host
     unsigned long long stop_key[2]; // (first record that ends the text << 8 | why), minimum over the records
     uint32_t any_nul[2];            // GZ rule: the text holds a NUL somewhere (k_count)
+    uint32_t n_nl[2];               // (host side only) plain FASTA: where the texts' newline counts arrive
     mcx_fastq_info info;
 };
 
@@ -92,7 +104,7 @@ __global__ void k_init(DevInfo *d, Job job)
     if (threadIdx.x || blockIdx.x) return;
     for (uint32_t t = 0; t < 2; t++) { d->stop_key[t] = ((unsigned long long)(t < job.nt ? job.t[t].eff_max : 0u) << 8) | MCX_FASTQ_MORE; d->any_nul[t] = 0; }
     d->info = mcx_fastq_info{};
-    for (uint32_t t = 0; t < job.nt; t++) job.t[t].ls[0] = 0;
+    if (!job.fa) for (uint32_t t = 0; t < job.nt; t++) job.t[t].ls[0] = 0; // (plain FASTA: the line table is made once the text's lines are counted)
 }
 
 // kGz: whether the text holds a NUL is noted on the way (the same 16 bytes; one atomicOr per workgroup that saw one — a flag, no order hangs on it)
@@ -129,7 +141,7 @@ __global__ void __launch_bounds__(kThreads) k_lines(Job job)
     __syncthreads();
     uint64_t rank = (uint64_t)t.pre[b] + (inc - c); // newlines of the text before this lane's first
     for (uint32_t i = 0; i < w; i++) rank += part[i];
-    const uint64_t last = 4ull * t.eff_max; // the last line start anyone asks for
+    const uint64_t last = t.ls_last; // the last line start anyone asks for
     const uint32_t p0 = (uint32_t)(v - t.lead); // (only used where a bit is set: the byte lies inside the text)
     while (m) {
         const uint32_t j = (uint32_t)__ffs((int)m) - 1u;
@@ -170,13 +182,55 @@ __global__ void __launch_bounds__(kThreads) k_records(Job job, DevInfo *d)
     if (k64 < t.eff_max) {
         k = (uint32_t)k64;
         const uint64_t n_nl = kGz ? gz_pieces_counted(t.po, t.eff_max) : t.pre[t.n_blocks]; // (kGz: pieces, in t.ps)
-        if (!job.final && !(kGz ? gz_record_whole(t.text, t.bytes, t.ps, n_nl, k) : record_whole(n_nl, k))) ends = true;
+        if (!job.final && !(kGz ? gz_record_whole(t.text, t.bytes, t.ps, n_nl, k, job.stride) : record_whole(n_nl, k))) ends = true;
         else {
             mcx_fastq_rec rec;
             rec.name = rec.name_len = rec.seq = rec.rlen = rec.qual = rec.q_take = 0;
-            why = kGz ? gz_record_of(t.text, t.bytes, t.ps, n_nl, k, job.max_read_len, d->any_nul[blockIdx.y] != 0, rec) : record_of(t.text, t.bytes, t.ls, n_nl, k, job.max_read_len, rec);
+            why = kGz ? gz_record_of(t.text, t.bytes, t.ps, n_nl, k, job.max_read_len, d->any_nul[blockIdx.y] != 0, rec, job.stride) : record_of(t.text, t.bytes, t.ls, n_nl, k, job.max_read_len, rec);
             if (why == MCX_FASTQ_MORE) t.recs[k] = rec; else ends = true;
         }
+    }
+    uint32_t first = ends ? k : 0xFFFFFFFFu;
+    for (int s = 32; s; s >>= 1) first = min(first, (uint32_t)__shfl_xor(first, s));
+    if (ends && k == first) atomicMin(&d->stop_key[blockIdx.y], ((unsigned long long)k << 8) | why);
+}
+
+// ---- plain FASTA ----------------------------------------------------------------------------------------------
+// a lane per line L <= n_nl + 1: header flag and payload (0, 0 from the text's last line on, so that the sums end with the totals)
+__global__ void __launch_bounds__(kThreads) k_fa_lines(Job job)
+{
+    const Text &t = job.t[blockIdx.y];
+    const uint64_t L = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (L > (uint64_t)t.n_nl + 1) return;
+    uint32_t h, pay;
+    fa_line(t.text, t.bytes, t.ls, t.n_nl, fa_n_lines(t.ls, t.n_nl, t.bytes), (uint32_t)L, h, pay);
+    t.fh[L] = h; t.fp[L] = pay;
+}
+
+// a lane per line: header number hn[L] lies in line L; behind the last header, the number of lines
+__global__ void __launch_bounds__(kThreads) k_fa_heads(Job job)
+{
+    const Text &t = job.t[blockIdx.y];
+    const uint64_t L = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t n_lines = fa_n_lines(t.ls, t.n_nl, t.bytes);
+    if (L > n_lines) return;
+    if (L == n_lines || t.fh[L]) t.hl[t.hn[L]] = (uint32_t)L; // (hn[L] <= L: inside hl[0 .. n_nl + 1])
+}
+
+// one lane per record, as k_records
+__global__ void __launch_bounds__(kThreads) k_fa_records(Job job, DevInfo *d)
+{
+    const Text &t = job.t[blockIdx.y];
+    const uint64_t k64 = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    uint32_t k = 0xFFFFFFFFu, why = MCX_FASTQ_MORE;
+    bool ends = false;
+    if (k64 < t.eff_max) {
+        k = (uint32_t)k64;
+        mcx_fastq_rec rec;
+        rec.name = rec.name_len = rec.seq = rec.rlen = rec.qual = rec.q_take = 0;
+        bool taken;
+        why = fa_record_of(t.text, t.bytes, t.ls, t.n_nl, t.bo, t.hl, t.hn[fa_n_lines(t.ls, t.n_nl, t.bytes)], k, job.max_read_len, job.final, rec, taken);
+        if (taken) t.recs[k] = rec; else ends = true;
     }
     uint32_t first = ends ? k : 0xFFFFFFFFu;
     for (int s = 32; s; s >>= 1) first = min(first, (uint32_t)__shfl_xor(first, s));
@@ -191,9 +245,10 @@ __global__ void k_finish(Job job, DevInfo *d)
         const Text &t = job.t[i];
         const uint32_t n = (uint32_t)(d->stop_key[i] >> 8);
         const bool gz = job.rule == MCX_FASTQ_RULE_GZ;
-        const uint64_t n_nl = gz ? gz_pieces_counted(t.po, t.eff_max) : t.pre[t.n_blocks];
         f.n_records[i] = n; f.stop[i] = (uint32_t)(d->stop_key[i] & 0xFFu);
-        f.consumed[i] = 4ull * n <= n_nl ? (gz ? t.ps : t.ls)[4ull * n] : t.bytes; // (GZ rule: a piece start of its line)
+        if (job.fa) { f.consumed[i] = fa_consumed(t.ls, t.hl, t.hn[fa_n_lines(t.ls, t.n_nl, t.bytes)], n, t.bytes); continue; } // (the start of a header line)
+        const uint64_t n_nl = gz ? gz_pieces_counted(t.po, t.eff_max) : t.pre[t.n_blocks], at = (uint64_t)job.stride * n;
+        f.consumed[i] = at <= n_nl ? (gz ? t.ps : t.ls)[at] : t.bytes; // (GZ rule: a piece start of its line)
     }
     f.n_reads = job.nt == 2 ? 2u * min(f.n_records[0], f.n_records[1]) : f.n_records[0];
 }
@@ -217,9 +272,9 @@ __global__ void __launch_bounds__(kThreads) k_lens(Job job, DevInfo *d, uint32_t
 }
 
 // A wavefront per read.  kWrite false: oc[r] = the read's bytes that are not upper-case ACGT (0 from n_reads on, oc [upper + 1]); true: those bytes'
-// entries in position order at odd[ooff[r] ..).
+// entries in position order at odd[ooff[r] ..).  fb: the reads' bases lie back to back at fb + foff[r] (plain FASTA), not in the text.
 template <bool kWrite>
-__global__ void __launch_bounds__(kThreads) k_odd(Job job, const DevInfo *d, uint32_t *oc, const uint32_t *ooff, uint64_t *odd)
+__global__ void __launch_bounds__(kThreads) k_odd(Job job, const DevInfo *d, uint32_t *oc, const uint32_t *ooff, uint64_t *odd, const uint8_t *fb, const uint32_t *foff)
 {
     const uint64_t r64 = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
@@ -229,7 +284,7 @@ __global__ void __launch_bounds__(kThreads) k_odd(Job job, const DevInfo *d, uin
         const uint32_t r = (uint32_t)r64;
         uint32_t t;
         const mcx_fastq_rec c = rec_of(job, r, t);
-        const uint8_t *seq = job.t[t].text + c.seq;
+        const uint8_t *seq = fb ? fb + foff[r] : job.t[t].text + c.seq;
         for (uint32_t i0 = 0; i0 < c.rlen; i0 += 64) {
             const uint32_t i = i0 + lane;
             const uint8_t ch = i < c.rlen ? seq[i] : (uint8_t)'A';
@@ -271,8 +326,25 @@ __global__ void __launch_bounds__(kThreads) k_gather(Job job, uint32_t n_reads, 
     }
 }
 
+// plain FASTA, a wavefront per read: its lines' bases back to back at bases + off[r] — one line per step, the lanes side by side over its bytes (lines of
+// 60 bases keep 60 of 64 lanes busy; the starts and sums are the same words for the whole wavefront).  Bounded by the record's lines and their lengths.
+__global__ void __launch_bounds__(kThreads) k_fa_gather(Job job, const DevInfo *d, const uint32_t *off, uint8_t *bases)
+{
+    const uint64_t r64 = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (r64 >= d->info.n_reads) return; // (the whole wavefront)
+    const uint32_t tt = job.nt == 2 ? ((uint32_t)r64 & 1u) : 0u, k = job.nt == 2 ? (uint32_t)(r64 >> 1) : (uint32_t)r64;
+    const Text &t = job.t[tt];
+    const uint32_t h = t.hl[k], nx = t.hl[k + 1], b0 = t.bo[h];
+    uint8_t *dst = bases + off[r64];
+    for (uint32_t L = h + 1; L < nx; L++) {
+        const uint32_t s = t.ls[L], at = t.bo[L], n = t.bo[L + 1] - at; // (n: the line less its last byte — every load inside the line)
+        for (uint32_t i = lane; i < n; i += 64) dst[at - b0 + i] = t.text[s + i];
+    }
+}
+
 // one lane per word of the rows; the lane of a row's first word writes the read's length
-__global__ void __launch_bounds__(kThreads) k_rows(Job job, uint32_t n_reads, uint32_t row_words, uint32_t *rows, uint32_t *len)
+__global__ void __launch_bounds__(kThreads) k_rows(Job job, uint32_t n_reads, uint32_t row_words, uint32_t *rows, uint32_t *len, const uint8_t *fb, const uint32_t *foff)
 {
     const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if (g >= (uint64_t)n_reads * row_words) return;
@@ -281,7 +353,7 @@ __global__ void __launch_bounds__(kThreads) k_rows(Job job, uint32_t n_reads, ui
     const mcx_fastq_rec c = rec_of(job, r, t);
     const uint64_t i = 16ull * w;
     uint32_t word = 0;
-    if (i < c.rlen) word = pack_word(job.t[t].text + c.seq, (uint32_t)i, c.rlen - (uint32_t)i < 16u ? c.rlen - (uint32_t)i : 16u);
+    if (i < c.rlen) word = pack_word(fb ? fb + foff[r] : job.t[t].text + c.seq, (uint32_t)i, c.rlen - (uint32_t)i < 16u ? c.rlen - (uint32_t)i : 16u);
     rows[g] = word;
     if (w == 0) len[r] = c.rlen;
 }
@@ -295,7 +367,8 @@ struct Buf { // device memory that grows
 struct mcx_fastq_parser {
     int device = 0;
     hipStream_t stream = nullptr;
-    int rule = MCX_FASTQ_RULE_PLAIN;
+    int rule = MCX_FASTQ_RULE_PLAIN, format = MCX_READS_FASTQ;
+    Buf fp[2], bo[2], fa_bases; // plain FASTA: the lines' payloads and their sums (flags, their sums and the headers' lines share pc, po, ps); the reads' bases back to back
     Buf cnt[2], pre[2], ls[2], pc[2], po[2], ps[2], recs[2], rl, nl, oc, off, noff, ooff, tmp, info;
     DevInfo *h_info = nullptr; // page-locked
     // the host forms: the texts' page-locked staging and their twin in HBM; the outputs' buffers in HBM
@@ -335,7 +408,7 @@ extern "C" void mcx_fastq_parser_free(mcx_fastq_parser *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     Buf *all[] = {&p->cnt[0], &p->cnt[1], &p->pre[0], &p->pre[1], &p->ls[0], &p->ls[1], &p->pc[0], &p->pc[1], &p->po[0], &p->po[1], &p->ps[0], &p->ps[1], &p->recs[0], &p->recs[1], &p->rl, &p->nl, &p->oc, &p->off, &p->noff, &p->ooff, &p->tmp, &p->info,
-                  &p->d_text, &p->o_recs[0], &p->o_recs[1], &p->o_bases, &p->o_qual, &p->o_off, &p->o_names, &p->o_noff, &p->o_rows, &p->o_len, &p->o_odd};
+                  &p->fp[0], &p->fp[1], &p->bo[0], &p->bo[1], &p->fa_bases, &p->d_text, &p->o_recs[0], &p->o_recs[1], &p->o_bases, &p->o_qual, &p->o_off, &p->o_names, &p->o_noff, &p->o_rows, &p->o_len, &p->o_odd};
     for (Buf *b : all) if (b->p) (void)hipFree(b->p);
     mcx_pinned_free(p->h_info); mcx_pinned_free(p->h_text);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
@@ -355,7 +428,8 @@ int reserve(mcx_fastq_parser *p, const uint64_t bytes[2], uint32_t nt, const uin
         most = std::max(most, nb);
         if ((rc = grow(p, p->cnt[t], nb * 4, "the block counts"))) break;
         if ((rc = grow(p, p->pre[t], nb * 4, "the block sums"))) break;
-        if ((rc = grow(p, p->ls[t], (4ull * eff[t] + 1) * 4, "the line starts"))) break;
+        const bool fa = p->format == MCX_READS_FASTA && p->rule == MCX_FASTQ_RULE_PLAIN; // (its line table is sized once the lines are counted: reserve_lines)
+        if (!fa && (rc = grow(p, p->ls[t], (4ull * eff[t] + 1) * 4, "the line starts"))) break;
         if (p->rule == MCX_FASTQ_RULE_GZ) {
             most = std::max<uint64_t>(most, 4ull * eff[t] + 1);
             if ((rc = grow(p, p->pc[t], (4ull * eff[t] + 1) * 4, "the lines' pieces")) || (rc = grow(p, p->po[t], (4ull * eff[t] + 1) * 4, "the pieces' sums")) ||
@@ -370,6 +444,17 @@ int reserve(mcx_fastq_parser *p, const uint64_t bytes[2], uint32_t nt, const uin
     for (Buf *b : per_read) if ((rc = grow(p, *b, upper1 * 4, "the reads' lengths and offsets"))) return rc;
     size_t need = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)most, p->stream));
+    return grow(p, p->tmp, need + 16, "the sums' scratch");
+}
+
+// plain FASTA: the tables of a text of n_nl newlines, and the sums' scratch for them
+int reserve_lines(mcx_fastq_parser *p, uint32_t t, uint64_t n_nl)
+{
+    const uint64_t n = n_nl + 2;
+    Buf *per_line[] = {&p->ls[t], &p->pc[t], &p->po[t], &p->ps[t], &p->fp[t], &p->bo[t]};
+    for (Buf *b : per_line) if (int rc = grow(p, *b, n * 4, "the text's line table")) return rc;
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, p->stream));
     return grow(p, p->tmp, need + 16, "the sums' scratch");
 }
 
@@ -415,18 +500,20 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
     Job &job = p->job;
     memset(&job, 0, sizeof job);
     job.nt = nt; job.max_read_len = in->max_read_len; job.final = in->final; job.rule = p->rule;
-    const bool gz = p->rule == MCX_FASTQ_RULE_GZ;
+    const bool gz = p->rule == MCX_FASTQ_RULE_GZ, fa = p->format == MCX_READS_FASTA && !gz;
+    job.stride = gz && p->format == MCX_READS_FASTA ? 2u : 4u; job.fa = fa ? 1 : 0;
     uint32_t eff[2] = {0, 0}, most_blocks = 0, most_eff = 0;
     for (uint32_t t = 0; t < nt; t++) { eff[t] = eff_max_of(in->max_records, in->bytes[t]); most_eff = std::max(most_eff, eff[t]); }
     if ((uint64_t)nt * most_eff + 1 > 0x7FFFFFFFull) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": max_records is too large");
     if (gz && 4ull * most_eff + 1 > 0x7FFFFFFFull) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": max_records is too large (the GZ rule's piece table holds 4 * max_records + 1 entries)");
     if (int rc = reserve(p, in->bytes, nt, eff)) return rc;
+    if (fa) if (int rc = grow(p, p->fa_bases, in->bytes[0] + (nt == 2 ? in->bytes[1] : 0) + 48, "the reads' bases")) return rc; // (a text holds no more bases than bytes)
     for (uint32_t t = 0; t < nt; t++) {
         Text &x = job.t[t];
         x.text = in->text[t]; x.bytes = (uint32_t)in->bytes[t];
         x.lead = (uint32_t)((uintptr_t)x.text & 15u);
         x.n_blocks = (uint32_t)(((uint64_t)x.bytes + x.lead + kBlockBytes - 1) / kBlockBytes);
-        x.eff_max = eff[t];
+        x.eff_max = eff[t]; x.ls_last = 4ull * eff[t];
         x.cnt = (uint32_t *)p->cnt[t].p; x.pre = (uint32_t *)p->pre[t].p; x.ls = (uint32_t *)p->ls[t].p; x.pc = (uint32_t *)p->pc[t].p; x.po = (uint32_t *)p->po[t].p; x.ps = (uint32_t *)p->ps[t].p; x.recs = (mcx_fastq_rec *)p->recs[t].p;
         most_blocks = std::max(most_blocks, x.n_blocks);
     }
@@ -440,7 +527,32 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
     if (gz) k_count<true><<<dim3(most_blocks + 1, nt), kThreads, 0, s>>>(job, d); else k_count<false><<<dim3(most_blocks + 1, nt), kThreads, 0, s>>>(job, d);
     HIP_TRY(hipGetLastError());
     for (uint32_t t = 0; t < nt; t++) if (int rc = scan(p, job.t[t].cnt, job.t[t].pre, (uint64_t)job.t[t].n_blocks + 1)) return rc;
+    uint64_t most_lines = 0;
+    if (fa) { // the host reads the texts' newline counts and sizes the line tables: the whole text's lines, whatever max_records is
+        for (uint32_t t = 0; t < nt; t++) HIP_TRY(hipMemcpyAsync(&p->h_info->n_nl[t], job.t[t].pre + job.t[t].n_blocks, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t t = 0; t < nt; t++) {
+            Text &x = job.t[t];
+            x.n_nl = p->h_info->n_nl[t]; x.ls_last = x.n_nl;
+            if ((uint64_t)x.n_nl + 2 > 0x7FFFFFFFull) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": a text of more than 2^31 - 3 lines");
+            if (int rc = reserve_lines(p, t, x.n_nl)) return rc;
+            x.ls = (uint32_t *)p->ls[t].p; x.fh = (uint32_t *)p->pc[t].p; x.hn = (uint32_t *)p->po[t].p; x.hl = (uint32_t *)p->ps[t].p; x.fp = (uint32_t *)p->fp[t].p; x.bo = (uint32_t *)p->bo[t].p;
+            HIP_TRY(hipMemsetAsync(x.ls, 0, 4, s));
+            most_lines = std::max<uint64_t>(most_lines, (uint64_t)x.n_nl + 2);
+        }
+    }
     if (most_blocks) k_lines<<<dim3(most_blocks, nt), kThreads, 0, s>>>(job);
+    if (fa) {
+        const dim3 grid(blocks_for(most_lines, kThreads), nt);
+        k_fa_lines<<<grid, kThreads, 0, s>>>(job);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t t = 0; t < nt; t++) {
+            if (int rc = scan(p, job.t[t].fh, job.t[t].hn, (uint64_t)job.t[t].n_nl + 2)) return rc;
+            if (int rc = scan(p, job.t[t].fp, job.t[t].bo, (uint64_t)job.t[t].n_nl + 2)) return rc;
+        }
+        k_fa_heads<<<grid, kThreads, 0, s>>>(job);
+        if (most_eff) k_fa_records<<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d);
+    }
     if (gz) { // the piece table from the line table
         const dim3 grid(blocks_for(4ull * most_eff + 1, kThreads), nt);
         k_line_pieces<<<grid, kThreads, 0, s>>>(job);
@@ -448,12 +560,16 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
         for (uint32_t t = 0; t < nt; t++) if (int rc = scan(p, job.t[t].pc, job.t[t].po, 4ull * job.t[t].eff_max + 1)) return rc;
         k_pieces<<<grid, kThreads, 0, s>>>(job);
     }
-    if (most_eff) { if (gz) k_records<true><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); else k_records<false><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); }
+    if (most_eff && !fa) { if (gz) k_records<true><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); else k_records<false><<<dim3(blocks_for(most_eff, kThreads), nt), kThreads, 0, s>>>(job, d); }
     k_finish<<<1, 64, 0, s>>>(job, d);
     k_lens<<<blocks_for((uint64_t)job.upper + 1, kThreads), kThreads, 0, s>>>(job, d, rl, nl);
-    k_odd<false><<<blocks_for((uint64_t)job.upper + 1, kThreads / 64), kThreads, 0, s>>>(job, d, oc, nullptr, nullptr);
+    if (fa) { // the bases back to back first: the odd bytes are counted there
+        if (int rc = scan(p, rl, off, (uint64_t)job.upper + 1)) return rc;
+        if (job.upper) k_fa_gather<<<blocks_for(job.upper, kThreads / 64), kThreads, 0, s>>>(job, d, off, (uint8_t *)p->fa_bases.p);
+    }
+    k_odd<false><<<blocks_for((uint64_t)job.upper + 1, kThreads / 64), kThreads, 0, s>>>(job, d, oc, nullptr, nullptr, fa ? (const uint8_t *)p->fa_bases.p : nullptr, off);
     HIP_TRY(hipGetLastError());
-    if (int rc = scan(p, rl, off, (uint64_t)job.upper + 1)) return rc;
+    if (!fa) if (int rc = scan(p, rl, off, (uint64_t)job.upper + 1)) return rc;
     if (int rc = scan(p, nl, noff, (uint64_t)job.upper + 1)) return rc;
     if (int rc = scan(p, oc, ooff, (uint64_t)job.upper + 1)) return rc;
     k_totals<<<1, 64, 0, s>>>(job, d, off, noff, ooff);
@@ -481,11 +597,17 @@ int output_pass(mcx_fastq_parser *p, const mcx_fastq_out *out, const mcx_fastq_i
         if (out->recs[t] && info->n_records[t]) HIP_TRY(hipMemcpyAsync(out->recs[t], job.t[t].recs, (size_t)info->n_records[t] * sizeof(mcx_fastq_rec), hipMemcpyDeviceToDevice, s));
     if (do_bases) HIP_TRY(hipMemcpyAsync(out->off, off, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, s));
     if (do_names) HIP_TRY(hipMemcpyAsync(out->name_off, noff, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, s));
-    if (n && (do_bases || do_names)) k_gather<<<blocks_for(n, kThreads / 64), kThreads, 0, s>>>(job, n, off, noff, do_bases ? out->bases : nullptr, do_bases ? out->qual : nullptr, do_names ? out->names : nullptr);
+    const uint8_t *fb = job.fa ? (const uint8_t *)p->fa_bases.p : nullptr; // plain FASTA: the sizes pass has left the bases back to back there; no quality: NULs
+    if (fb && do_bases && info->n_bases) {
+        HIP_TRY(hipMemcpyAsync(out->bases, fb, info->n_bases, hipMemcpyDeviceToDevice, s));
+        if (out->qual) HIP_TRY(hipMemsetAsync(out->qual, 0, info->n_bases, s));
+    }
+    const bool g_bases = do_bases && !fb;
+    if (n && (g_bases || do_names)) k_gather<<<blocks_for(n, kThreads / 64), kThreads, 0, s>>>(job, n, off, noff, g_bases ? out->bases : nullptr, g_bases ? out->qual : nullptr, do_names ? out->names : nullptr);
     if (n && do_rows) {
-        if (out->row_words) k_rows<<<blocks_for((uint64_t)n * out->row_words, kThreads), kThreads, 0, s>>>(job, n, out->row_words, out->rows, out->len);
+        if (out->row_words) k_rows<<<blocks_for((uint64_t)n * out->row_words, kThreads), kThreads, 0, s>>>(job, n, out->row_words, out->rows, out->len, fb, off);
         else HIP_TRY(hipMemcpyAsync(out->len, p->rl.p, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        if (info->n_odd) k_odd<true><<<blocks_for(n, kThreads / 64), kThreads, 0, s>>>(job, (const DevInfo *)p->info.p, nullptr, ooff, out->odd);
+        if (info->n_odd) k_odd<true><<<blocks_for(n, kThreads / 64), kThreads, 0, s>>>(job, (const DevInfo *)p->info.p, nullptr, ooff, out->odd, fb, off);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(p->ev[1], s));
@@ -518,6 +640,13 @@ extern "C" int mcx_fastq_parser_set_rule(mcx_fastq_parser *p, int rule)
 {
     if (!p || (rule != MCX_FASTQ_RULE_PLAIN && rule != MCX_FASTQ_RULE_GZ)) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parser_set_rule: null parser or no such rule");
     p->rule = rule;
+    return 0;
+}
+
+extern "C" int mcx_fastq_parser_set_format(mcx_fastq_parser *p, int format)
+{
+    if (!p || (format != MCX_READS_FASTQ && format != MCX_READS_FASTA)) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parser_set_format: null parser or no such format");
+    p->format = format;
     return 0;
 }
 

@@ -11,9 +11,10 @@
 //     the reads' names, bases and qualities left where they lie in the file (the SAM formatter reads
 //     them there) and the bases packed to 2 bits on the way (a quarter of the bytes cross PCIe); a
 //     shard of a several-GPU run touches only the bytes of its own batches;
-//   * .gz files and FASTA go through one sequential reader per file (zlib / multi-line records) — except BGZF FASTQ with -gpu_inflate -gpu_parse, whose text
+//   * .gz files and FASTA go through one sequential reader per file (zlib / multi-line records) — except BGZF input with -gpu_inflate -gpu_parse, whose text
 //     stays in HBM from the compressed bytes on (the resident route, mcx_resident.hip): the reader thread then only asks for the next batch, the mapper
-//     submits it from HBM (mcx_stream_submit_dev) and the SAM kernels take names and qualities where the parser left them;
+//     submits it from HBM (mcx_stream_submit_dev) and the SAM kernels take names and qualities where the parser left them; and except plain FASTA with
+//     -gpu_parse, whose bytes go to HBM in chunks and whose records, bases, names, rows and odd bytes come back from the device parser;
 //   * batches flow through parse | copy in, map, copy out (three device slots: the copies of one
 //     batch under the kernels of its neighbours) | format + write;
 //   * SAM lines are formatted by a second pool into per-slice buffers and written with positioned
@@ -105,6 +106,20 @@ bool plain_fastq(const char *path)
     fclose(f);
     return ch == '@'; // CheckReadFormat, GetData.cpp:22-31
 }
+// a plain FASTA file: not named .gz, a regular file that is not empty, its first byte anything but '@'
+bool plain_fasta(const char *path)
+{
+    const std::string p(path);
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) return false;
+    if (getenv("MCX_SERIAL_PARSER")) return false; // (tests: the sequential reader)
+    struct stat st;
+    if (stat(path, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0) return false;
+    FILE *f = fopen(path, "rb");
+    if (!f) return false;
+    const int ch = fgetc(f);
+    fclose(f);
+    return ch != EOF && ch != '@';
+}
 
 // all n bytes at p: behind what was written before (stream), or at byte `at` of the file
 bool write_all(int fd, const char *p, size_t n, uint64_t at, bool stream)
@@ -128,7 +143,8 @@ struct Timing {
 
 // where a run's reads come from, chosen once (open_input)
 enum Route {
-    kResident,   // BGZF FASTQ with -gpu_inflate -gpu_parse: inflated, cut and packed in HBM (mcx_resident.hip)
+    kResident,   // BGZF FASTQ or FASTA with -gpu_inflate -gpu_parse: inflated, cut and packed in HBM (mcx_resident.hip)
+    kFastaDev,   // plain FASTA with -gpu_parse: the files' bytes go to HBM in chunks, a batch's records, bases, names, rows and odd bytes come back
     kMappedDev,  // plain FASTQ, mapped; -gpu_parse: a batch's text is parsed and packed on the device
     kMapped,     // plain FASTQ, mapped, parsed and packed by the pool
     kSequential  // .gz, FASTA: one Parser per file
@@ -235,15 +251,23 @@ struct Run {
             const char *paths[2] = {fq1, two ? fq2 : nullptr};
             mcx_resident *r = nullptr;
             if (int e = mcx_resident_open(idx->device, paths, nf, &r)) return e;
-            resident.reset(r); // (null: a file is no BGZF FASTQ — the route does not apply and the files are read as without it)
+            resident.reset(r); // (null: a file is no BGZF file, or the files differ in format — the route does not apply and the files are read as without it)
         }
-        route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
+        if (!plain && !resident && opt.device_parse && !sharded && !opt.interleaved_pairs && plain_fasta(fq1) && (!two || plain_fasta(fq2))) {
+            const char *paths[2] = {fq1, two ? fq2 : nullptr};
+            mcx_resident *r = nullptr;
+            if (int e = mcx_resident_open_plain(idx->device, paths, nf, &r)) return e;
+            resident.reset(r);
+            if (resident) route = kFastaDev;
+        }
+        if (resident) fastq = !mcx_resident_fasta(resident.get());
+        if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
         const uint32_t sam_bit = dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u;
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
-                                                          : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
+                                                          : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
         return 0;
     }
     int open_mapped()
@@ -351,7 +375,7 @@ struct Run {
     //  which has gone back to another route would hold for nothing)
     void keep_objects()
     {
-        auto keep = [&](BatchPtr &b) { if (!resident && b->res) { mcx_resident_bufs_free(b->res); b->res = nullptr; } kept->objects.push_back(std::move(b)); };
+        auto keep = [&](BatchPtr &b) { if (route != kResident && b->res) { mcx_resident_bufs_free(b->res); b->res = nullptr; } kept->objects.push_back(std::move(b)); };
         BatchPtr b;
         while (spare.try_pop(b)) keep(b);
         while (parsed.try_pop(b)) keep(b);
@@ -380,6 +404,7 @@ struct Run {
             memset(&fq_info, 0, sizeof fq_info);
             switch (route) {
             case kResident: fill_resident(*b); break;
+            case kFastaDev: fill_fasta_dev(*b); break;
             case kMappedDev: fill_mapped_dev(*b, number, mine); break;
             case kMapped: fill_mapped(*b, number, mine); break;
             case kSequential: fill_sequential(*b); break;
@@ -433,6 +458,36 @@ struct Run {
             if (!v.recs.resize(b.rb.n_records[f])) { v.error = "out of memory for the batch's read records"; continue; } // (counted, never read)
             v.last = b.rb.last[f];
             if (b.rb.has_too_long[f]) v.error = "read " + std::string(b.rb.too_long[f]) + " is longer than max_read_len";
+        }
+    }
+    // plain FASTA with -gpu_parse: the batch is counted and cut in HBM as on the resident route; its bases and names come back into the first view's own buffer
+    // (bases, then names) with the offsets as records, which is how Parser::take leaves a batch: the host formatter, device_sam and -m find them there
+    void fill_fasta_dev(Batch &b)
+    {
+        if ((b.error_rc = mcx_resident_next(resident.get(), &b.res, per_file, max_len, false, &b.rb)) != 0) { b.in[0].error = std::string("-gpu_parse: ") + mcx_last_error(); return; }
+        const uint32_t n = b.rb.n_reads;
+        std::vector<uint32_t> off((size_t)n + 1), noff((size_t)n + 1);
+        std::vector<char> &own = b.in[0].own;
+        own.resize((size_t)(b.rb.n_bases + b.rb.n_name_bytes) + 32);
+        if (n) {
+            mcx_fastq_out o;
+            memset(&o, 0, sizeof o);
+            o.bases = (uint8_t *)own.data(); o.off = off.data(); o.bases_cap = b.rb.n_bases + 32;
+            o.names = (uint8_t *)own.data() + b.rb.n_bases; o.name_off = noff.data(); o.names_cap = b.rb.n_name_bytes; // (behind the bases: copied after them)
+            if ((b.error_rc = mcx_resident_host_out(resident.get(), &o)) != 0) { b.in[0].error = std::string("-gpu_parse: ") + mcx_last_error(); return; }
+        }
+        for (int f = 0; f < nf; f++) {
+            View &v = b.in[f];
+            v.base = own.data();
+            if (!v.recs.resize(b.rb.n_records[f])) { v.error = "out of memory for the batch's read records"; continue; }
+            v.last = b.rb.last[f];
+            if (b.rb.has_too_long[f]) v.error = "read " + std::string(b.rb.too_long[f]) + " is longer than max_read_len";
+            Rec *dst = v.recs.data();
+            for (uint32_t r = (uint32_t)f; r < n; r += (uint32_t)nf) { // (records behind the batch's reads — a file ahead of the other, a batch that is not mapped — are counted, never read)
+                Rec rec; memset(&rec, 0, sizeof rec);
+                rec.name = (size_t)b.rb.n_bases + noff[r]; rec.name_len = noff[r + 1] - noff[r]; rec.seq = off[r]; rec.rlen = off[r + 1] - off[r];
+                dst[r / (uint32_t)nf] = rec;
+            }
         }
     }
     void fill_sequential(Batch &b)
@@ -560,7 +615,7 @@ struct Run {
         uint32_t npr = paired ? n : 0; // reads mapped as pairs; the odd tail of an interleaved file is mapped read by read
         if (paired && (n & 1)) npr = n / kReadChunkSize * kReadChunkSize;
         b.n_pair_reads = npr;
-        uint32_t longest = b.resident ? b.rb.longest : fq_info.longest;
+        uint32_t longest = b.resident || route == kFastaDev ? b.rb.longest : fq_info.longest;
         if (route == kMapped || route == kSequential) {
             std::vector<uint32_t> most((size_t)pool.slices(n, 4096), 0);
             pool.for_range(n, 4096, [&](int k, uint64_t lo, uint64_t hi) {
@@ -574,6 +629,7 @@ struct Run {
         if (!b.reserve(std::max<size_t>(n, batch_reads), b.resident ? 1 : std::max<size_t>(b.row_words, ((size_t)max_len + 15) / 16))) b.error = "cannot allocate pinned host memory";
         else switch (route) {
         case kResident: pack_resident(b); break;
+        case kFastaDev: pack_fasta_dev(b); break;
         case kMappedDev: pack_mapped_dev(b); break;
         case kMapped: case kSequential: pack_host(b); break;
         }
@@ -604,6 +660,24 @@ struct Run {
                 const uint64_t *cut = std::lower_bound(b.odd, b.odd + fq_info.n_odd, (uint64_t)npr << 32);
                 b.n_odd[0] = (uint32_t)(cut - b.odd); b.n_odd[1] = fq_info.n_odd - b.n_odd[0];
                 for (uint64_t *w = b.odd + b.n_odd[0]; w < b.odd + fq_info.n_odd; w++) *w -= (uint64_t)npr << 32;
+            }
+        }
+    }
+    // plain FASTA with -gpu_parse: as pack_mapped_dev, from the batch the resident object holds on the device
+    void pack_fasta_dev(Batch &b)
+    {
+        const uint32_t npr = b.n_pair_reads, n_odd = b.rb.n_odd;
+        mcx_fastq_out o;
+        memset(&o, 0, sizeof o);
+        if (b.rb.n_reads != b.n) b.error = "-gpu_parse: the device counted " + std::to_string(b.rb.n_reads) + " reads, the reader " + std::to_string(b.n);
+        else if (n_odd && !b.reserve_odd(n_odd)) b.error = "cannot allocate pinned host memory";
+        else {
+            o.rows = b.rows; o.row_words = 0; o.len = b.lens; o.odd = b.odd; o.odd_cap = n_odd;
+            if (mcx_resident_host_out(resident.get(), &o) != 0) b.error = std::string("-gpu_parse: ") + mcx_last_error();
+            else {
+                const uint64_t *cut = std::lower_bound(b.odd, b.odd + n_odd, (uint64_t)npr << 32);
+                b.n_odd[0] = (uint32_t)(cut - b.odd); b.n_odd[1] = n_odd - b.n_odd[0];
+                for (uint64_t *w = b.odd + b.n_odd[0]; w < b.odd + n_odd; w++) *w -= (uint64_t)npr << 32;
             }
         }
     }
@@ -873,7 +947,7 @@ struct Run {
         const Tick tq = now();
         const uint32_t npr = p->n_pair_reads;
         uint64_t got = 0;
-        const int e = p->resident ? mcx_sam_part_dev(c, d_bases, d_off, cnt, second ? 0 : 1, p->rb.names, p->rb.name_off, p->rb.qual, d_aln, d_cig, &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got) :
+        const int e = p->resident ? mcx_sam_part_dev(c, d_bases, d_off, cnt, second ? 0 : 1, p->rb.names, p->rb.name_off, p->fastq ? p->rb.qual : nullptr, d_aln, d_cig, &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got) :
                       mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
                                    p->fastq ? p->sam_qual + (second ? p->sam_part_qual[0] : 0) : nullptr, p->sam_part_qual[second ? 1 : 0], d_aln, d_cig,
                                    &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got);
@@ -982,7 +1056,7 @@ struct Run {
         std::string e;
         for (size_t k = 0; k < t.each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(t.each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
-        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], resident ? " — the resident route" : "");
+        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
         if (dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t.m_sam);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");

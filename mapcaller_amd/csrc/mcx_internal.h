@@ -80,7 +80,7 @@ static inline size_t mcx_bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen
     return 0;
 }
 // The resident route (mcx_resident.hip; -gpu_inflate -gpu_parse on BGZF FASTQ): one or two read files whose text never leaves HBM.  open: *out stays null (and
-// the call returns 0) when a file is no BGZF file named .gz or its text does not begin with '@' — the route does not apply.  next: the next batch of up to
+// the call returns 0) when a file is no BGZF file named .gz, has no text, or the files are not all FASTQ (first text byte '@') or all FASTA — the route does not apply.  next: the next batch of up to
 // per_file records a file — more members inflated as needed, the records found under the GZ rule, rows / lengths / odd bytes (and, want_sam, names, their
 // offsets and NUL-padded qualities) written to *bufs, device buffers that belong to the caller's batch object (made on first use, grown on demand, freed with
 // mcx_resident_bufs_free).  One host thread per object.
@@ -93,9 +93,16 @@ struct mcx_resident_batch {
     bool has_too_long[2];
     uint32_t n_reads;          // reads in the buffers: n_records[0], or 2 * n_records[0] mate by mate — 0 when file 2 gave fewer than file 1 or a read is too long
     const uint32_t *rows, *len; const uint64_t *odd; uint32_t row_words, n_odd, longest; // mcx_stream_submit_dev's arguments
-    const uint8_t *names, *qual; const uint32_t *name_off;                              // mcx_sam_part_dev's
+    const uint8_t *names, *qual; const uint32_t *name_off;                              // mcx_sam_part_dev's (qual null: FASTA)
+    uint64_t n_bases, n_name_bytes;                                                     // (plain) what mcx_resident_host_out's bases and names groups hold
 };
 int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_resident **out);
+// The same object over plain FASTA files (-gpu_parse): the files' bytes go to HBM a launch at a time, the records are plain-rule FASTA's, and next leaves the
+// batch on the device (bufs: unused): host_out brings the groups of `out` (HOST pointers; rows with row_words 0 come ceil(longest / 16) words wide) back, any
+// number of times until the next batch is asked for.  fasta: the files are FASTA (either open).
+int mcx_resident_open_plain(int device, const char *const paths[2], int n_files, mcx_resident **out);
+int mcx_resident_host_out(mcx_resident *, const mcx_fastq_out *out);
+bool mcx_resident_fasta(const mcx_resident *);
 void mcx_resident_close(mcx_resident *);
 int mcx_resident_next(mcx_resident *, mcx_resident_bufs **bufs, uint32_t per_file, int32_t max_read_len, bool want_sam, mcx_resident_batch *out);
 void mcx_resident_bufs_free(mcx_resident_bufs *);

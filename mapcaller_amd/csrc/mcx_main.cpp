@@ -53,9 +53,10 @@ static void usage(const char *prog)
             "         -m            output multiple alignments: a SAM line for every alignment with the best score\n"
             "         -gpu_sam      make the SAM text on the GPU instead of with host threads (same bytes; nothing without -sam)\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
-            "                       with -gpu_parse on BGZF FASTQ (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
+            "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
-            "         -gpu_parse    parse plain FASTQ read files and pack their reads on the GPU instead of with host threads (same reads; other input is read as before)\n"
+            "         -gpu_parse    parse plain FASTQ and plain FASTA read files and pack their reads on the GPU instead of with host threads (same reads; FASTA: one file, or two\n"
+            "                       as pairs, not -p, not -gpus N; other input is read as before)\n"
             "         -gvcf         GVCF mode\n"
             "         -monomorphic  report all loci which do not have any potential alternates\n"
             "         -ploidy INT   number of sets of chromosomes in a cell (1:monoploid, 2:diploid) [2]\n"

@@ -9,6 +9,10 @@
 //   a batch   per file: count the records in what the buffer holds (final = 0 while members follow); fewer than wanted and the file goes on: one more launch,
 //             count again.  Then one call for both files over text[0 .. consumed) with final = 1 — the same pieces, so the same records — that writes rows,
 //             lengths and odd bytes (and names, their offsets and NUL-padded qualities for the SAM kernels) into the batch object's device buffers.
+// FASTA: BGZF files whose text does not begin with '@' go the same way under GZ-rule FASTA (records of two pieces, no qualities: the SAM kernels get none).
+// PLAIN FASTA under -gpu_parse alone (mcx_resident_open_plain): the same object over plain files — `more` sends the next bytes of the mapped file to HBM instead
+// of inflating members, the parser runs under plain-rule FASTA, and the batch's arrays come back to host buffers (mcx_resident_host_out): the counting, the carry
+// and the ends of the input are this file's for both.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -21,7 +25,6 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <zlib.h>
 
 #include "../../include/mcx.h"
 #include "mcx_fastq.h"
@@ -63,6 +66,8 @@ struct File {
     size_t o = 0;            // the walk's place in the file
     bool walk_end = false;   // no member follows: the file's end, something that is no member, or a damaged stretch
     bool eof = false;        // ... and everything before that is in the text
+    bool plain = false;      // a plain file: its bytes are the text
+    uint64_t ask = 0;        // (plain) bytes the next `more` should bring, when more than a launch: what the batch in hand still lacks, by its records so far
     mcx_inflater *inf = nullptr;
     DBuf text[2]; int cur = 0;       // the file's text in HBM: text[cur][start .. have) is not consumed yet
     uint64_t start = 0, have = 0;
@@ -81,6 +86,9 @@ struct mcx_resident {
     DBuf bases, off;         // outputs of the parser that nobody reads (the qualities come in a group with them)
     uint64_t launch_bytes = 0, max_src = 0;
     uint32_t max_members = 0;
+    bool fixed_launch = false;         // MCX_RESIDENT_LAUNCH_BYTES is set: every launch is that long
+    bool fasta = false, plain = false; // FASTA text (no qualities); plain files (the results go back to the host)
+    mcx_fastq_info all;                // (plain) the last batch's combined call, for mcx_resident_host_out
 };
 struct mcx_resident_bufs {
     int device = 0;
@@ -88,32 +96,6 @@ struct mcx_resident_bufs {
 };
 
 namespace {
-
-// the first byte of the file's text, by zlib on the host (-1: there is none, or the first member with text is damaged)
-int first_text_byte(const File &f)
-{
-    for (size_t o = 0; o < f.size;) {
-        size_t xlen = 0;
-        const uint8_t *p = f.map + o;
-        const size_t size = mcx_bgzf_member_at(p, f.size - o, xlen);
-        if (!size) return -1;
-        const uint32_t isize = (uint32_t)p[size - 4] | ((uint32_t)p[size - 3] << 8) | ((uint32_t)p[size - 2] << 16) | ((uint32_t)p[size - 1] << 24);
-        if (isize > 65536) return -1;
-        if (isize) {
-            z_stream zs; memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) return -1;
-            uint8_t byte = 0;
-            zs.next_in = const_cast<Bytef *>(p + 12 + xlen); zs.avail_in = (uInt)(size - 12 - xlen - 8);
-            zs.next_out = &byte; zs.avail_out = 1;
-            const int rc = inflate(&zs, Z_SYNC_FLUSH);
-            const bool ok = (rc == Z_OK || rc == Z_STREAM_END || rc == Z_BUF_ERROR) && zs.total_out == 1;
-            inflateEnd(&zs);
-            return ok ? (int)byte : -1;
-        }
-        o += size;
-    }
-    return -1;
-}
 
 // room for `need` more bytes behind the text: what is not consumed moves to the front of the file's other buffer (device to device), which grows if it must
 int ensure_room(mcx_resident *R, File &f, uint64_t need)
@@ -135,6 +117,17 @@ int ensure_room(mcx_resident *R, File &f, uint64_t need)
 int more(mcx_resident *R, File &f)
 {
     if (f.walk_end) { f.eof = true; return 0; }
+    if (f.plain) { // the next bytes of the file, as they are
+        const uint64_t n = std::min<uint64_t>(std::max(R->launch_bytes, f.ask), f.size - f.o);
+        if (n) {
+            if (int rc = ensure_room(R, f, n)) return rc;
+            HIP_TRY(hipMemcpyAsync((uint8_t *)f.text[f.cur].p + f.have, f.map + f.o, n, hipMemcpyHostToDevice, R->stream));
+            HIP_TRY(hipStreamSynchronize(R->stream));
+            f.have += n; f.o += n;
+        }
+        f.walk_end = f.eof = f.o >= f.size;
+        return 0;
+    }
     f.members.clear(); f.stretch_of.clear(); f.stretch_at.assign(1, 0);
     uint64_t total = 0;
     while (!f.walk_end) {
@@ -256,7 +249,7 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_r
         }
         close(fd);
         size_t xlen = 0;
-        applies = applies && mcx_bgzf_member_at(f.map, f.size, xlen) != 0 && first_text_byte(f) == '@'; // BGZF, and FASTQ (CheckReadFormat, GetData.cpp:22-31)
+        applies = applies && mcx_bgzf_member_at(f.map, f.size, xlen) != 0; // BGZF
     }
     if (!applies) { mcx_resident_close(R); return 0; }
     const char *env = getenv("MCX_RESIDENT_LAUNCH_BYTES");
@@ -268,18 +261,64 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_r
     for (int i = 0; i < n_files && rc == 0; i++) rc = mcx_inflater_create_dev(device, R->max_src, R->max_members, &R->f[i].inf);
     if (rc == 0) rc = mcx_fastq_parser_create(device, 0, 0, &R->parser);
     if (rc == 0) rc = mcx_fastq_parser_set_rule(R->parser, MCX_FASTQ_RULE_GZ);
-    // What the host reader judges FASTQ by is the first byte of the first stretch it is handed: a first stretch that is damaged hands it none (and the reader
-    // then takes the file for FASTA).  The same here, from HBM; such a file is left to that reader.
+    // What the host reader judges FASTQ or FASTA by is the first byte of the first stretch it is handed ('@': FASTQ, CheckReadFormat, GetData.cpp:22-31): a first
+    // stretch that is damaged hands it none.  The same here, from HBM; a file without text, and files of two formats, are left to that reader.
+    bool fastq[2] = {true, true};
     for (int i = 0; i < n_files && rc == 0 && applies; i++) {
         File &f = R->f[i];
         while (rc == 0 && f.have == 0 && !f.eof) rc = more(R, f);
         uint8_t first = 0;
         if (rc == 0 && f.have && hipMemcpy(&first, f.text[f.cur].p, 1, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_inflate -gpu_parse: copy from the device failed"); }
-        applies = first == '@';
+        applies = f.have != 0;
+        fastq[i] = first == '@';
     }
+    if (n_files == 2 && fastq[0] != fastq[1]) applies = false;
+    R->fasta = !fastq[0];
+    if (rc == 0 && applies && R->fasta) rc = mcx_fastq_parser_set_format(R->parser, MCX_READS_FASTA);
     if (rc || !applies) { mcx_resident_close(R); return rc; }
     *out = R;
     return 0;
+}
+
+// plain FASTA files (-gpu_parse): *out stays null when a file cannot be mapped — the caller's reader then says why
+int mcx_resident_open_plain(int device, const char *const paths[2], int n_files, mcx_resident **out)
+{
+    *out = nullptr;
+    mcx_resident *R = new mcx_resident();
+    R->device = device; R->n_files = n_files; R->fasta = R->plain = true;
+    bool applies = true;
+    for (int i = 0; i < n_files && applies; i++) {
+        File &f = R->f[i];
+        f.plain = true;
+        const int fd = ::open(paths[i], O_RDONLY);
+        if (fd < 0) { applies = false; break; }
+        struct stat st;
+        applies = fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0;
+        if (applies) {
+            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) applies = false; else { f.map = (const uint8_t *)m; f.size = (size_t)st.st_size; }
+        }
+        close(fd);
+    }
+    if (!applies) { mcx_resident_close(R); return 0; }
+    const char *env = getenv("MCX_RESIDENT_LAUNCH_BYTES");
+    R->launch_bytes = env && atoll(env) > 0 ? (uint64_t)atoll(env) : (1ull << 20); // bytes of a file that go to HBM at a time, at least (every count walks all the text in hand: a batch asks for what it lacks)
+    R->fixed_launch = env && atoll(env) > 0;
+    int rc = 0;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_parse: no stream on the context's device"); }
+    if (rc == 0) rc = mcx_fastq_parser_create(device, 0, 0, &R->parser);
+    if (rc == 0) rc = mcx_fastq_parser_set_format(R->parser, MCX_READS_FASTA);
+    if (rc) { mcx_resident_close(R); return rc; }
+    *out = R;
+    return 0;
+}
+
+bool mcx_resident_fasta(const mcx_resident *R) { return R->fasta; }
+
+// (plain) groups of the last batch into HOST buffers (mcx_fastq_staged_out: row_words 0 gives rows ceil(longest / 16) words wide)
+int mcx_resident_host_out(mcx_resident *R, const mcx_fastq_out *out)
+{
+    return mcx_fastq_staged_out(R->parser, out, &R->all);
 }
 
 int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_file, int32_t max_read_len, bool want_sam, mcx_resident_batch *out)
@@ -293,6 +332,9 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
         for (;;) {
             if (int rc = count(R, f, per_file, max_read_len, &info[i])) return rc;
             if (info[i].n_records[0] >= per_file || f.eof || info[i].stop[0] != MCX_FASTQ_MORE) break; // (a stop inside whole records stands whatever follows)
+            // (plain: every count walks the whole text in hand, so the next bytes are as many as the batch still lacks, judged by its records so far)
+            const uint64_t got = info[i].n_records[0], in_hand = f.have - f.start;
+            f.ask = f.plain && !R->fixed_launch ? (got ? (uint64_t)((double)info[i].consumed[0] / (double)got * 1.05 * (double)(per_file - got)) + 65536 : 2 * in_hand) : 0;
             if (int rc = more(R, f)) return rc;
         }
         out->n_records[i] = info[i].n_records[0];
@@ -303,7 +345,7 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
             uint32_t len = (uint32_t)std::min<uint64_t>(mcx::fq::kGzPiece, f.have - at);
             HIP_TRY(hipMemcpy(piece, (const uint8_t *)f.text[f.cur].p + at, len, hipMemcpyDeviceToHost));
             if (const void *nl = memchr(piece, '\n', len)) len = (uint32_t)((const uint8_t *)nl - piece) + 1;
-            len = (uint32_t)strnlen((const char *)piece, len);
+            if (!R->plain) len = (uint32_t)strnlen((const char *)piece, len); // (a plain line is not a C string; its name ends within the first 100 bytes either way)
             uint32_t p1 = 0, p2 = 0;
             if (len) mcx::fq::header_of(piece, len, p1, p2);
             const uint32_t name_len = p2 > p1 ? std::min<uint32_t>(p2 - p1, sizeof out->too_long[i] - 1) : 0;
@@ -334,6 +376,12 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
     if (int rc = mcx_fastq_dev_sizes(R->parser, &in, &all)) return rc;
     const uint32_t n = (uint32_t)nf * n_take;
     if (all.n_reads != n) return mcx_set_error(MCX_ERR_DEVICE, "-gpu_parse: the device counted " + std::to_string(all.n_reads) + " reads where " + std::to_string(n) + " were counted before");
+    if (R->plain) { // the caller fetches what it needs into host buffers: the text stays where it is until the next batch is asked for
+        R->all = all;
+        for (int i = 0; i < nf; i++) R->f[i].start += consumed[i];
+        out->n_reads = n; out->n_odd = all.n_odd; out->longest = all.longest; out->n_bases = all.n_bases; out->n_name_bytes = all.n_name_bytes;
+        return 0;
+    }
     if (!*bufs) { *bufs = new mcx_resident_bufs(); (*bufs)->device = R->device; }
     mcx_resident_bufs &b = **bufs;
     const uint32_t row_words = ((uint32_t)max_read_len + 15) / 16;
@@ -344,10 +392,11 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
     memset(&o, 0, sizeof o);
     o.rows = (uint32_t *)b.rows.p; o.row_words = row_words; o.len = (uint32_t *)b.len.p; o.odd = (uint64_t *)b.odd.p; o.odd_cap = all.n_odd;
     if (want_sam) {
-        if ((rc = dgrow(R->bases, all.n_bases + 48, "the parser's bases")) || (rc = dgrow(R->off, ((uint64_t)n + 1) * 4, "the parser's offsets")) ||
-            (rc = dgrow(b.qual, all.n_bases + 48, "a batch's qualities")) || (rc = dgrow(b.names, all.n_name_bytes + 16, "a batch's read names")) ||
-            (rc = dgrow(b.name_off, ((uint64_t)n + 1) * 4, "a batch's name offsets"))) return rc;
-        o.bases = (uint8_t *)R->bases.p; o.off = (uint32_t *)R->off.p; o.qual = (uint8_t *)b.qual.p; o.bases_cap = all.n_bases + 32;
+        if ((rc = dgrow(b.names, all.n_name_bytes + 16, "a batch's read names")) || (rc = dgrow(b.name_off, ((uint64_t)n + 1) * 4, "a batch's name offsets"))) return rc;
+        if (!R->fasta) { // (FASTA: no qualities — the SAM kernels write '*' for a null pointer)
+            if ((rc = dgrow(R->bases, all.n_bases + 48, "the parser's bases")) || (rc = dgrow(R->off, ((uint64_t)n + 1) * 4, "the parser's offsets")) || (rc = dgrow(b.qual, all.n_bases + 48, "a batch's qualities"))) return rc;
+            o.bases = (uint8_t *)R->bases.p; o.off = (uint32_t *)R->off.p; o.qual = (uint8_t *)b.qual.p; o.bases_cap = all.n_bases + 32;
+        }
         o.names = (uint8_t *)b.names.p; o.name_off = (uint32_t *)b.name_off.p; o.names_cap = all.n_name_bytes;
     }
     if ((rc = mcx_fastq_dev_out(R->parser, &o, &all))) return rc;

@@ -38,8 +38,8 @@ def parse(argv):
     ap.add_argument("-no_vcf", action="store_true")
     ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
     ap.add_argument("-gpu_sam", dest="gpu_sam", action="store_true", help="make the SAM text on the GPU instead of with host threads (same bytes)")
-    ap.add_argument("-gpu_parse", dest="gpu_parse", action="store_true", help="parse plain FASTQ read files and pack their reads on the GPU instead of with host threads (same reads)")
-    ap.add_argument("-gpu_inflate", dest="gpu_inflate", action="store_true", help="inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads); with -gpu_parse on BGZF FASTQ (and -gpu_sam where a SAM file is written) the reads stay on the GPU from the compressed bytes to the SAM text")
+    ap.add_argument("-gpu_parse", dest="gpu_parse", action="store_true", help="parse plain FASTQ and plain FASTA read files and pack their reads on the GPU instead of with host threads (same reads)")
+    ap.add_argument("-gpu_inflate", dest="gpu_inflate", action="store_true", help="inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads); with -gpu_parse on BGZF FASTQ or FASTA (and -gpu_sam where a SAM file is written) the reads stay on the GPU from the compressed bytes to the SAM text")
     ap.add_argument("-indel", type=int, default=30, help="maximal indel size (MaxPosDiff), at most 100")
     ap.add_argument("-maxmm", type=float, default=0.05, help="maximal mismatch rate in read alignment (MaxMisMatchRate)")
     ap.add_argument("-t", dest="threads", type=int, default=0, help="host threads per process for parsing / SAM text")
