@@ -481,6 +481,28 @@ int  mcx_inflate(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const m
 /* the BGZF reader by itself, the twin of mcx_gz_inflate: whole length of the text, -1 unreadable / first bytes are no BGZF member, -2 a damaged member (*n_out: bytes delivered before it) */
 int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- text compressed to BGZF on the device --------------------------------------------------------------
+ * The way back: text that lies in HBM — the SAM text of mcx_sam_format_dev — becomes a row of BGZF blocks, each an independent gzip member of at most
+ * 65 280 bytes of text (bgzip's cut; mcx_deflater_set_block: fewer), which samtools, bgzip -d, zcat and Python's gzip read.  A wavefront per block: LZ77
+ * matches inside the block's own bytes (4 .. 258 bytes long, 1 .. 32 768 back), dynamic Huffman codes (RFC 1951 block type 2) — or the fixed codes, or the
+ * bytes stored, whichever is smallest, so a block's deflate stream never exceeds its text + 5 bytes —, the CRC-32 taken on the device.  The same text and
+ * block size give the same bytes on every run.  A deflater is an object of its own like an inflater: one device, a non-blocking stream of its own, scratch in
+ * HBM made on first use (a slot per block of a launch; a launch takes at most 128 MB of text) and, for the host form, page-locked staging.  One host thread
+ * per object.
+ * A block: the 18-byte header 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 02 00, BSIZE = the block's size - 1; the deflate stream; CRC-32; ISIZE.
+ * mcx_bgzf_deflate_dev writes complete, contiguous blocks in text order (every call starts a fresh block; no EOF block) to d_out and their bytes to *n_out;
+ * text_bytes == 0 writes nothing.  out_cap < mcx_bgzf_bound(text_bytes, the block size): MCX_ERR_CAPACITY, nothing written.  Runs on the object's stream and
+ * returns when the bytes are there. */
+typedef struct mcx_deflater mcx_deflater;
+int      mcx_deflater_create(int device, uint64_t max_text_bytes /* per launch through host buffers; 0: default (8 MB) */, mcx_deflater **out);
+void     mcx_deflater_free(mcx_deflater *);
+int      mcx_deflater_set_block(mcx_deflater *, uint32_t text_bytes);    /* 1..65280 per BGZF block, sticky; default 65280; else MCX_ERR_ARG */
+uint64_t mcx_bgzf_bound(uint64_t text_bytes, uint32_t block_text_bytes); /* bytes the blocks of that much text can take at most (every block stored: text + 31 per block) */
+int      mcx_bgzf_deflate_dev(mcx_deflater *, const uint8_t *d_text, uint64_t text_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t *n_out);
+/* host buffers, staged through the object's page-locked buffers in as many launches as max_text_bytes requires: the same bytes */
+int      mcx_bgzf_deflate(mcx_deflater *, const uint8_t *text, uint64_t text_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_out);
+int      mcx_bgzf_eof(uint8_t out[28]);                                  /* the empty block that ends a BGZF file */
+
 /* ---- FASTQ text parsed on the device ---------------------------------------------------------------
  * Replaces the host reader's parse and pack of plain FASTQ (MappedFastq::parse, header_of and mcx_pack_row; the reference's GetNextEntry,
  * GetData.cpp:3-20, :32-55) for text that lies in HBM already — what mcx_inflate_dev delivers — and produces exactly the arrays
@@ -591,11 +613,18 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * kernels from the same buffers.  Only the records, or the SAM text, come back.  Same reads, same end of the input (a damaged stretch, garbage behind a member,
  * a header that is none, an empty or too long read, file 2 shorter or longer), same error texts.  HBM, taken after the context's: see DESIGN §5b.  Any other
  * combination runs exactly as without the route; mcx_files_route says which stages ran on the device.
+ * device_sam is a bit set: bit 1 (MCX_SAM_DEVICE) is the above, bit 2 (MCX_SAM_BGZF; mapcaller-mi355x -bgzf) writes the SAM file as BGZF and implies bit 1, because the text
+ * has to be in HBM: every part's text is compressed where it lies by an mcx_deflater of the run's own (each part starts a fresh block) and only the blocks come back for
+ * the one writer; the header goes out as blocks of its own, and the 28-byte EOF block ends the file.  A library appended with append_sam starts over the previous EOF
+ * block, so a finished file has exactly one, at its end; on a stream (sam_path "-") every library ends with its own, which readers skip.  gzip -d of the file is, byte
+ * for byte, the SAM file written without the bit, and the same input gives the same file on every run.  On every input route that device_sam works on, the resident
+ * route and -m included; with shard_count > 1 the call returns MCX_ERR_UNSUPPORTED before anything is opened.  (route: MCX_ROUTE_BGZF.)
+ * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
 typedef struct mcx_file_opts {
     int32_t interleaved_pairs, host_threads, append_sam;
-    int32_t device_sam; /* 1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
+    int32_t device_sam; /* bits of mcx_sam_bits.  1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
     int64_t *avg_state; /* int64_t[4], see mcx_avg_init */
     int32_t shard_rank, shard_count; /* 0, 0: the whole input */
     int32_t device_inflate; /* 1: BGZF input is inflated and CRC-checked on the device (mcx_inflate's kernel) instead of by a pool of host threads; 0: as before */
@@ -604,6 +633,10 @@ typedef struct mcx_file_opts {
                                         decide the duplicate cap over ONE input order, so that SAM and profile equal the
                                         single-stream run's (rank/size must equal shard_rank/shard_count) */
 } mcx_file_opts;
+enum mcx_sam_bits {
+    MCX_SAM_DEVICE = 1, /* the SAM text is made on the device */
+    MCX_SAM_BGZF = 2    /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
+};
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
 /* Which stages of the context's last mcx_map_files* call ran on the device, per read file (route[1] = 0 for one file): the opt-in switches that do not apply
@@ -612,7 +645,8 @@ enum mcx_route {
     MCX_ROUTE_INFLATE = 1, /* the file's BGZF members were inflated on the device */
     MCX_ROUTE_PARSE = 2,   /* its records were found and packed on the device */
     MCX_ROUTE_ROWS = 4,    /* its batches entered their slots from HBM (mcx_stream_submit_dev): the resident route */
-    MCX_ROUTE_SAM = 8      /* the SAM text was made on the device */
+    MCX_ROUTE_SAM = 8,     /* the SAM text was made on the device */
+    MCX_ROUTE_BGZF = 16    /* ... and compressed to BGZF blocks there */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 

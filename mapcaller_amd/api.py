@@ -73,6 +73,7 @@ SYMBOLS = [
     "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
+    "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -260,6 +261,10 @@ MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u
 FASTQ_RULE_PLAIN, FASTQ_RULE_GZ = 0, 1  # mcx_fastq_rule
 READS_FASTQ, READS_FASTA = 0, 1  # mcx_reads_format
 ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
+ROUTE_BGZF = 16
+ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
+SAM_DEVICE, SAM_BGZF = 1, 2  # mcx_sam_bits (mcx_file_opts.device_sam)
+BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
 
@@ -427,6 +432,21 @@ def lib() -> C.CDLL:
     L.mcx_inflate_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_bgzf_inflate.restype = C.c_int64
     L.mcx_bgzf_inflate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_deflater_create.restype = C.c_int
+    L.mcx_deflater_create.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mcx_deflater_free.restype = None
+    L.mcx_deflater_free.argtypes = [C.c_void_p]
+    L.mcx_deflater_set_block.restype = C.c_int
+    L.mcx_deflater_set_block.argtypes = [C.c_void_p, C.c_uint32]
+    L.mcx_bgzf_bound.restype = C.c_uint64
+    L.mcx_bgzf_bound.argtypes = [C.c_uint64, C.c_uint32]
+    for f in (L.mcx_bgzf_deflate_dev, L.mcx_bgzf_deflate):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_bgzf_eof.restype = C.c_int
+    L.mcx_bgzf_eof.argtypes = [C.c_void_p]
+    L.mcx_bgzf_deflate_last_ms.restype = C.c_int
+    L.mcx_bgzf_deflate_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -593,7 +613,7 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -604,13 +624,14 @@ class Mapper:
         device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files, and plain FASTA files (one, or two as pairs; not sharded, not
         interleaved), are parsed and packed to 2-bit rows on the device (the same reads, the same end of the input; other input is read as before).
         ``device_inflate`` and ``device_parse`` together, on BGZF FASTQ or FASTA files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
-        parse, pack, map and SAM text all in HBM.  ``last_route()`` says which stages ran on the device."""
+        parse, pack, map and SAM text all in HBM.  ``bgzf_sam`` = -bgzf: the SAM file is written as BGZF, its blocks deflated on the device (implies ``device_sam``; gzip -d of the
+        file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = int(device_sam)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam else 0) | (SAM_BGZF if bgzf_sam else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -627,7 +648,7 @@ class Mapper:
 
     def last_route(self) -> Tuple[int, int]:
         """mcx_files_route: per read file of the last map_files call, the stages that ran on the device as a sum of ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS
-        (the batches entered their slots from HBM) and ROUTE_SAM; the second entry is 0 for one file."""
+        (the batches entered their slots from HBM), ROUTE_SAM and ROUTE_BGZF (the SAM text left the device as BGZF blocks); the second entry is 0 for one file."""
         r = (C.c_uint32 * 2)()
         _check(lib().mcx_files_route(self._h, r), "mcx_files_route")
         return int(r[0]), int(r[1])
@@ -1052,6 +1073,76 @@ class FastqParser:
         n = C.c_uint32()
         _check(lib().mcx_fastq_grown(self._h, C.byref(n)), "mcx_fastq_grown")
         return int(n.value)
+
+
+class Deflater:
+    """mcx_deflater: text compressed to BGZF blocks on the device, a wavefront per block of at most 65 280 bytes of text (set_block: fewer), on a stream of the
+    object's own.  max_text_bytes: what one launch through host buffers takes (0: 8 MB).  The same text and block size give the same bytes on every run."""
+
+    def __init__(self, device: int = 0, max_text_bytes: int = 0):
+        self._h = C.c_void_p()
+        self.block = BGZF_BLOCK
+        _check(lib().mcx_deflater_create(device, max_text_bytes, C.byref(self._h)), "mcx_deflater_create")
+
+    def close(self):
+        if self._h:
+            lib().mcx_deflater_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_block(self, text_bytes: int) -> int:
+        """mcx_deflater_set_block: the bytes of text per block of the following calls (1 .. 65280).  Returns 0 or ERR_ARG."""
+        rc = lib().mcx_deflater_set_block(self._h, text_bytes)
+        if rc == 0:
+            self.block = text_bytes
+        elif rc != ERR_ARG:
+            _check(rc, "mcx_deflater_set_block")
+        return rc
+
+    def bound(self, text_bytes: int) -> int:
+        return int(lib().mcx_bgzf_bound(text_bytes, self.block))
+
+    def deflate_dev(self, d_text, text_bytes: int, d_out, out_cap: Optional[int] = None):
+        """mcx_bgzf_deflate_dev on torch uint8 tensors of the deflater's device.  Returns (rc, bytes written): rc 0 or ERR_CAPACITY (nothing written)."""
+        n = C.c_uint64()
+        rc = lib().mcx_bgzf_deflate_dev(self._h, d_text.data_ptr() if text_bytes else None, text_bytes, d_out.data_ptr(), d_out.numel() if out_cap is None else out_cap, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            _check(rc, "mcx_bgzf_deflate_dev")
+        return rc, int(n.value)
+
+    def deflate(self, text) -> bytes:
+        """mcx_bgzf_deflate on host buffers: the BGZF blocks of ``text`` (no EOF block)."""
+        src = np.frombuffer(bytes(text), dtype=np.uint8)
+        out = np.zeros(max(self.bound(src.size), 1), dtype=np.uint8)
+        n = C.c_uint64()
+        _check(lib().mcx_bgzf_deflate(self._h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, out.size, C.byref(n)), "mcx_bgzf_deflate")
+        return out[:n.value].tobytes()
+
+    def last_ms(self) -> float:
+        """the last deflate_dev's kernels, in ms by events on the deflater's stream"""
+        ms = C.c_float()
+        _check(lib().mcx_bgzf_deflate_last_ms(self._h, C.byref(ms)), "mcx_bgzf_deflate_last_ms")
+        return float(ms.value)
+
+
+def bgzf_eof() -> bytes:
+    """mcx_bgzf_eof: the empty block that ends a BGZF file"""
+    out = (C.c_uint8 * 28)()
+    _check(lib().mcx_bgzf_eof(out), "mcx_bgzf_eof")
+    return bytes(out)
+
+
+def bgzf_deflate(text, block: int = 65280, device: int = 0) -> bytes:
+    """``text`` as the BGZF blocks the device makes of it (block: bytes of text per block), without the EOF block: gzip.decompress(bgzf_deflate(t) + bgzf_eof()) == t"""
+    with Deflater(device) as d:
+        if d.set_block(block) != 0:
+            raise ValueError("a BGZF block takes 1 to 65280 bytes of text")
+        return d.deflate(text)
 
 
 def bgzf_inflate(path: str, device: int = 0, cap: int = 0):

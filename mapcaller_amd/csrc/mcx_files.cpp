@@ -172,6 +172,7 @@ struct Run {
     const int threads;
     const bool wants_sam;
     const bool dev_sam;         // the text is made on the device (mcx_sam.hip); without a SAM file there is none to make
+    const bool bgzf;            // ... and compressed there: the file is BGZF (mcx_deflate.hip)
     Timing t;
     Shards sh;
     Pool pool;                  // parse + pack
@@ -196,6 +197,10 @@ struct Run {
     bool sam_stream = false; // stdout: written front to back
     uint64_t sam_base = 0;   // where the first batch's text goes
     std::atomic<int> write_rc{0};
+    struct DefFree { void operator()(mcx_deflater *d) const { mcx_deflater_free(d); } };
+    std::unique_ptr<mcx_deflater, DefFree> deflater; // -bgzf: the header's blocks (the opening thread), then every part's (the mapper's thread)
+    mcx_sam_bgzf zs = {nullptr, 65280, 0, 0, 0};
+    uint8_t bgzf_eof[28];
     std::deque<BatchPtr> waiting; // (the writer's; sharded) formatted, their place in the file not known yet
 
     // ---- between the stages -----------------------------------------------------------------------------------------------
@@ -232,7 +237,7 @@ struct Run {
           shard_count(o.shard_count > 1 ? (uint64_t)o.shard_count : 1), shard_rank(shard_count > 1 ? (uint64_t)o.shard_rank : 0), sharded(shard_count > 1),
           batch_reads(std::max<uint64_t>(kReadChunkSize, mcx_ctx_max_reads(ctx) / kReadChunkSize * kReadChunkSize)), per_file((uint32_t)(two ? batch_reads / 2 : batch_reads)),
           threads(o.host_threads > 0 ? o.host_threads : (int)std::min<unsigned>(64, std::max<unsigned>(1, mcx_usable_cpus() * 3 / 4 / (unsigned)shard_count))),
-          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), pool(threads), fpool(threads),
+          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), pool(threads), fpool(threads),
           n_objects(sharded ? 16 : 12), parsed(2), mapped(2), formatted(2), spare((size_t)n_objects),
           profile(mcx_ctx_has_profile(ctx)), multi(mcx_ctx_multi(ctx))
     {
@@ -264,7 +269,7 @@ struct Run {
         if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
-        const uint32_t sam_bit = dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u;
+        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u);
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
@@ -328,6 +333,18 @@ struct Run {
     {
         if (!wants_sam) return 0;
         int e = 0;
+        if (bgzf) { // -bgzf: a deflater of the run's own on the context's device
+            mcx_deflater *d = nullptr;
+            if (mcx_deflater_create(idx->device, 1u << 20, &d) != 0) return mcx_set_error(MCX_ERR_DEVICE, std::string("-bgzf: ") + mcx_last_error());
+            deflater.reset(d);
+            zs.deflater = d; zs.block = 65280;
+            if (const char *env = getenv("MCX_BGZF_BLOCK")) { // (debug override: the bytes of text per block)
+                const long v = atol(env);
+                if (v >= 1 && v <= 65280) zs.block = (uint32_t)v;
+            }
+            if (int e2 = mcx_deflater_set_block(d, zs.block)) return e2;
+            mcx_bgzf_eof(bgzf_eof);
+        }
         if (strcmp(sam_path, "-") == 0) {
             if (sharded) e = mcx_set_error(MCX_ERR_ARG, "a sharded run cannot write its SAM to stdout");
             sam_fd = 1; sam_stream = true;
@@ -344,11 +361,23 @@ struct Run {
             }
             struct stat st;
             if (e == 0 && opt.append_sam && fstat(sam_fd, &st) == 0) sam_base = (uint64_t)st.st_size;
+            // (-bgzf) a further library starts over the EOF block of the one before: a finished file has one, at its end
+            uint8_t tail[28];
+            if (e == 0 && bgzf && opt.append_sam && sam_base >= 28 && pread(sam_fd, tail, 28, (off_t)(sam_base - 28)) == 28 && memcmp(tail, bgzf_eof, 28) == 0) sam_base -= 28;
         }
         if (e == 0 && !opt.append_sam) {
             std::string hdr;
             sam_header(hix, hdr);
-            if (shard_rank == 0) {
+            if (bgzf) { // the header as BGZF blocks of its own
+                std::string blocks((size_t)mcx_bgzf_bound(hdr.size(), zs.block), '\0');
+                uint64_t made = 0;
+                const auto t0 = now();
+                e = mcx_bgzf_deflate(zs.deflater, (const uint8_t *)hdr.data(), hdr.size(), (uint8_t *)&blocks[0], blocks.size(), &made);
+                zs.text_bytes += hdr.size(); zs.out_bytes += made; zs.seconds += secs(t0, now());
+                blocks.resize((size_t)made);
+                hdr.swap(blocks);
+            }
+            if (e == 0 && shard_rank == 0) {
                 const ssize_t w = sam_stream ? write(sam_fd, hdr.data(), hdr.size()) : pwrite(sam_fd, hdr.data(), hdr.size(), 0);
                 if (w != (ssize_t)hdr.size()) e = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
             }
@@ -799,6 +828,7 @@ struct Run {
             }
         }
         flush_waiting(true); // the places of the last rounds' text arrive with the closing exchanges
+        if (bgzf && sam_fd >= 0 && write_rc == 0 && !write_all(sam_fd, (const char *)bgzf_eof, 28, next_place, sam_stream)) write_rc = MCX_ERR_IO; // (-bgzf is never sharded)
     }
     void flush_waiting(bool block) // batches whose place has arrived go out, oldest first
     {
@@ -947,10 +977,10 @@ struct Run {
         const Tick tq = now();
         const uint32_t npr = p->n_pair_reads;
         uint64_t got = 0;
-        const int e = p->resident ? mcx_sam_part_dev(c, d_bases, d_off, cnt, second ? 0 : 1, p->rb.names, p->rb.name_off, p->fastq ? p->rb.qual : nullptr, d_aln, d_cig, &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got) :
+        const int e = p->resident ? mcx_sam_part_dev(c, d_bases, d_off, cnt, second ? 0 : 1, p->rb.names, p->rb.name_off, p->fastq ? p->rb.qual : nullptr, d_aln, d_cig, &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got, bgzf ? &zs : nullptr) :
                       mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
                                    p->fastq ? p->sam_qual + (second ? p->sam_part_qual[0] : 0) : nullptr, p->sam_part_qual[second ? 1 : 0], d_aln, d_cig,
-                                   &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got);
+                                   &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got, bgzf ? &zs : nullptr);
         if (e) rc = e; else p->dev_bytes += got;
         t.m_sam += secs(tq, now());
     }
@@ -1056,8 +1086,10 @@ struct Run {
         std::string e;
         for (size_t k = 0; k < t.each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(t.each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
-        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
+        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
         if (dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t.m_sam);
+        if (bgzf) fprintf(stderr, "[mcx_map_files] bgzf: %llu bytes of text -> %llu bytes of blocks (%u bytes of text a block), the deflater took %.3f s of them\n",
+                          (unsigned long long)zs.text_bytes, (unsigned long long)zs.out_bytes, zs.block, zs.seconds);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");
         fprintf(stderr, "[mcx_map_files] waits: reader for room behind it %.3f | mapper for a parsed batch %.3f, for copies out %.3f | formatter for the writer %.3f || mapper's calls: submit %.3f, next %.3f, map_batch_dev %.3f, mapped %.3f\n", t.p_push, t.m_take, t.m_collect, t.f_push, t.m_submit, t.m_in, t.m_dev, t.m_out);
@@ -1075,6 +1107,8 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     if (fo) opt = *fo;
     if (opt.shard_count > 1 && (!opt.exchange || !opt.exchange->allgather || opt.exchange->size != opt.shard_count || opt.exchange->rank != opt.shard_rank))
         return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_ex: a sharded run needs mcx_file_opts.exchange with the shard's rank and count");
+    if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_BGZF))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF (-bgzf with -gpus N / -devices): map on one GPU, or without -bgzf");
     Run run(c, fq1, fq2, opt, sam_path, stats);
     if (int e = run.open_input()) return e;
     if (int e = run.open_output()) return e;

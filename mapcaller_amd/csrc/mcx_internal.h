@@ -38,9 +38,12 @@ void **mcx_ctx_files_slot(mcx_ctx *, void (*drop)(void *));
 // the same for mcx_sam.hip's device buffers, and the stream (a hipStream_t) the context's kernels run on
 void **mcx_ctx_sam_slot(mcx_ctx *, void (*drop)(void *));
 void *mcx_ctx_stream(mcx_ctx *);
-// -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory
+// -bgzf: the run's deflater with its block size, and what it has done so far (text in, blocks out, seconds of the calling thread)
+struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; };
+// -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory; bgzf (null: none): the text is
+// compressed in HBM first and its BGZF blocks arrive instead, *n_bytes their size
 int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
-                 const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
+                 const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf);
 // -gpu_inflate (mcx_inflate.hip): the host form of mcx_inflate in two halves, so that the reader stages a stretch's bytes while the stretch before is on
 // the device — begin packs the members' bytes (src_off into src) into page-locked staging and queues copy in, kernel and copy out; end waits for the oldest
 // begin and hands the text to dst + each member's dst_off (0, or MCX_ERR_IO when a member failed).  At most two begins outstanding; caps: what one holds.
@@ -53,7 +56,7 @@ int mcx_inflater_create_dev(int device, uint64_t max_src_bytes, uint32_t max_mem
 int mcx_inflate_begin_dev(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n, uint8_t *d_dst, uint64_t dst_cap);
 // mcx_sam_part for names, name offsets and NUL-padded qualities in HBM (mcx_fastq_parse_dev's outputs): nothing is copied in
 int mcx_sam_part_dev(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *d_names, const uint32_t *d_name_off,
-                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
+                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf);
 // mcx_fastq_parse_dev in two halves: the caller sizes its buffers from *info in between
 int mcx_fastq_dev_sizes(mcx_fastq_parser *, const mcx_fastq_in *in, mcx_fastq_info *info);
 int mcx_fastq_dev_out(mcx_fastq_parser *, const mcx_fastq_out *out, const mcx_fastq_info *info);

@@ -52,6 +52,8 @@ static void usage(const char *prog)
             "         -no_vcf       No VCF output\n"
             "         -m            output multiple alignments: a SAM line for every alignment with the best score\n"
             "         -gpu_sam      make the SAM text on the GPU instead of with host threads (same bytes; nothing without -sam)\n"
+            "         -bgzf         write the SAM file as BGZF (name it .sam.gz: samtools, bgzip -d, zcat read it), its blocks deflated on the GPU;\n"
+            "                       implies -gpu_sam; gzip -d gives the bytes of the plain file; not with -gpus N / -devices\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -154,7 +156,8 @@ int main(int argc, char **argv)
         else if (p == "-log" && i + 1 < argc) ++i;
         else if (p == "-v" || p == "--version") { fprintf(stderr, "MapCaller v0.9.9.41 (mapcaller-mi355x)\n\n"); return 0; } // main.cpp:310-314
         else if (p == "-m") multi = true; // bUnique = false, main.cpp:308
-        else if (p == "-gpu_sam") fo.device_sam = 1;
+        else if (p == "-gpu_sam") fo.device_sam |= MCX_SAM_DEVICE;
+        else if (p == "-bgzf") fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else if (p == "-bam") { fprintf(stderr, "Error! %s is not supported by mapcaller-mi355x (DESIGN.md, deliberate deviations)\n", argv[i]); return 1; }
@@ -164,6 +167,7 @@ int main(int argc, char **argv)
     if (!f2.empty() && f1.size() != f2.size()) { fprintf(stderr, "Warning! Paired-end reads input numbers do not match!\n"); return 0; }
     if (devices.empty()) for (int r = 0; r < n_gpus; r++) devices.push_back(n_gpus == 1 ? gpu : r);
     n_gpus = (int)devices.size();
+    if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the
     // early ones (a failed build leaves partial files behind it)
     struct TmpIndex {

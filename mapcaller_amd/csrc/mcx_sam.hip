@@ -10,6 +10,7 @@
 //                straight to its place: never cut short.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -106,11 +107,11 @@ struct SamState {
     uint64_t *h_total = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[3] = {0, 0, 0}; // the last call's length kernel, scan, write kernel
-    uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr; uint32_t *d_name_off = nullptr;
-    uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0;
+    uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
+    uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
     ~SamState()
     {
-        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_names, d_qual, d_text, d_name_off};
+        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_names, d_qual, d_text, d_name_off, d_bgzf};
         for (void *q : p) if (q) (void)hipFree(q);
         if (h_total) (void)hipHostFree(h_total);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -291,20 +292,20 @@ extern "C" int mcx_sam_header(const mcx_index *ix, char *out, uint64_t cap, uint
 // page-locked host memory go behind the reads, the text is made from the part's records, CIGAR pool and (-m) the context's extras, and arrives at
 // (*text)[at ..], a page-locked buffer that grows as needed (*text_cap).  On the context's stream, waited for.
 static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
-                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes);
+                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf);
 int mcx_sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
-                 const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
+                 const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf)
 {
-    return sam_part(c, d_bases, d_off, n_reads, paired, names, name_off, qual, qual_bytes, false, d_aln, d_cigar, text, text_cap, at, n_bytes);
+    return sam_part(c, d_bases, d_off, n_reads, paired, names, name_off, qual, qual_bytes, false, d_aln, d_cigar, text, text_cap, at, n_bytes, bgzf);
 }
 // Its twin for names, name offsets and NUL-padded qualities that lie in HBM already (the resident route: mcx_fastq_parse_dev's outputs): nothing is copied in
 int mcx_sam_part_dev(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *d_names, const uint32_t *d_name_off,
-                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
+                     const uint8_t *d_qual, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf)
 {
-    return sam_part(c, d_bases, d_off, n_reads, paired, d_names, d_name_off, d_qual, 0, true, d_aln, d_cigar, text, text_cap, at, n_bytes);
+    return sam_part(c, d_bases, d_off, n_reads, paired, d_names, d_name_off, d_qual, 0, true, d_aln, d_cigar, text, text_cap, at, n_bytes, bgzf);
 }
 static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
-                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes)
+                    const uint8_t *qual, uint64_t qual_bytes, bool on_device, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf)
 {
     *n_bytes = 0;
     if (n_reads == 0) return 0;
@@ -339,6 +340,18 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
         rc = format_dev(c, st, in, st->d_text, st->cap_text, nullptr, &total);
     }
     if (rc) return rc;
+    // -bgzf: the part's text is compressed where it lies (a fresh block at its start), and only the blocks leave the device
+    const uint8_t *d_from = st->d_text;
+    if (bgzf && total) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t bound = mcx_bgzf_bound(total, bgzf->block);
+        if ((rc = grow(&st->d_bgzf, &st->cap_bgzf, bound, "the batch's BGZF blocks"))) return rc;
+        uint64_t made = 0;
+        if ((rc = mcx_bgzf_deflate_dev(bgzf->deflater, st->d_text, total, st->d_bgzf, st->cap_bgzf, &made))) return rc;
+        bgzf->text_bytes += total; bgzf->out_bytes += made;
+        bgzf->seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        d_from = st->d_bgzf; total = made;
+    }
     if (at + total > *text_cap) {
         const uint64_t want = (at + total) + (at + total) / 8 + 4096;
         uint8_t *p = (uint8_t *)mcx_pinned_alloc(want);
@@ -347,7 +360,7 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
         mcx_pinned_free(*text);
         *text = p; *text_cap = want;
     }
-    HIP_TRY(hipMemcpyAsync(*text + at, st->d_text, total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(*text + at, d_from, total, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *n_bytes = total;
     return 0;

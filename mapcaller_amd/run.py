@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MapCaller's command line on one or several MI355X of a node.
 
-    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam]] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
+    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf]] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 -m mapcaller_amd.run -i idx -f r1.fq -f2 r2.fq -sam out.sam -vcf out.vcf
 
 One process per GPU.  The input stream is cut into batches that are dealt to the ranks in turn
@@ -38,6 +38,7 @@ def parse(argv):
     ap.add_argument("-no_vcf", action="store_true")
     ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
     ap.add_argument("-gpu_sam", dest="gpu_sam", action="store_true", help="make the SAM text on the GPU instead of with host threads (same bytes)")
+    ap.add_argument("-bgzf", dest="bgzf", action="store_true", help="write the SAM file as BGZF, its blocks deflated on the GPU (implies -gpu_sam; gzip -d gives the plain file's bytes; one process only)")
     ap.add_argument("-gpu_parse", dest="gpu_parse", action="store_true", help="parse plain FASTQ and plain FASTA read files and pack their reads on the GPU instead of with host threads (same reads)")
     ap.add_argument("-gpu_inflate", dest="gpu_inflate", action="store_true", help="inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads); with -gpu_parse on BGZF FASTQ or FASTA (and -gpu_sam where a SAM file is written) the reads stay on the GPU from the compressed bytes to the SAM text")
     ap.add_argument("-indel", type=int, default=30, help="maximal indel size (MaxPosDiff), at most 100")
@@ -92,6 +93,8 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.bgzf and world > 1:
+        sys.exit("-bgzf writes one BGZF stream from one GPU: it cannot be combined with several ranks (a sharded BGZF writer does not exist yet)")
     n_dev = torch.cuda.device_count()
     if n_dev == 0:
         sys.exit("mapcaller_amd.run needs a GPU: the hot path has no CPU fallback")
@@ -119,7 +122,7 @@ def main(argv=None):
         f2 = a.f2[k] if a.f2 else None
         # (the ranks write into the one SAM file, every batch's lines at their final place: mcx_map_files_ex)
         st = mapper.map_files(f1, f2, a.sam or None, interleaved=a.interleaved, threads=a.threads,
-                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse)
+                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf)
         for key in totals:
             totals[key] += st[key]
         if td:
