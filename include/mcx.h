@@ -450,6 +450,21 @@ int mcx_sam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *text, uint64_t cap,
  * batch; *n_bytes their size, MCX_ERR_CAPACITY (nothing written) when cap is smaller. */
 int mcx_sam_header(const mcx_index *, char *out, uint64_t cap, uint64_t *n_bytes);
 
+/* ---- BAM records ---------------------------------------------------------------------------------
+ * The same batch as uncompressed BAM records (the reference's -bam: every SAM line through htslib's sam_parse1 / sam_write1, src/ReadMapping.cpp:548-606),
+ * made in HBM from the mcx_sam_in that mcx_sam_format_dev takes — the record of the line that call would print, field for field: refID / pos - 1 / mapq / bin
+ * (UCSC binning, 14-bit minimum shift, 5 levels) / flag (| 4 unmapped), the pool's CIGAR words as they are, SEQ two bases a byte, QUAL - 33 (0xff: none), NM / AS / XS
+ * as the smallest integer type that holds the value.  A line htslib's parser rejects makes no record and is counted: a QNAME of 252 bytes or more, a QUAL that is
+ * not '*' and not as long as SEQ.  Read r's record(s) — its extras' behind its own — start at d_rec_off[r] (device, may be NULL; n_reads + 1 entries, the last one
+ * the total); records are not aligned and say nothing of BGZF: mcx_bgzf_deflate_dev frames them.  *n_bytes is always the exact size, *n_dropped (may be NULL) the
+ * lines left out; cap smaller than the size: nothing is written, MCX_ERR_CAPACITY (cap = 0 asks for the size).  On the context's stream, waited for. */
+int mcx_bam_format_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t cap, uint64_t *d_rec_off, uint64_t *n_bytes, uint64_t *n_dropped);
+/* same with host buffers (staged inside) */
+int mcx_bam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *out, uint64_t cap, uint64_t *rec_off, uint64_t *n_bytes, uint64_t *n_dropped);
+/* The uncompressed BAM header: "BAM\1", l_text, mcx_sam_header's text, n_ref, and per contig l_name, the name with its NUL, l_ref.  *n_bytes its size,
+ * MCX_ERR_CAPACITY (nothing written) when cap is smaller; MCX_ERR_UNSUPPORTED for a contig longer than 2^31 - 1, which BAM cannot say. */
+int mcx_bam_header(const mcx_index *, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
+
 /* ---- BGZF input inflated on the device -------------------------------------------------------------
  * bgzip's container is a row of independent gzip members of at most 64 KB of text, each of which says how long it is ('BC' extra
  * field) and carries the CRC-32 and the length of its text.  An inflater takes the raw deflate streams of many members at once — a
@@ -619,6 +634,11 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * block, so a finished file has exactly one, at its end; on a stream (sam_path "-") every library ends with its own, which readers skip.  gzip -d of the file is, byte
  * for byte, the SAM file written without the bit, and the same input gives the same file on every run.  On every input route that device_sam works on, the resident
  * route and -m included; with shard_count > 1 the call returns MCX_ERR_UNSUPPORTED before anything is opened.  (route: MCX_ROUTE_BGZF.)
+ * bit 4 (MCX_SAM_BAM; mapcaller-mi355x -bam) writes BAM instead and implies bits 1 and 2: the header is mcx_bam_header's bytes as BGZF blocks of their own, every part's
+ * records are made by mcx_bam_format_dev's kernels into the buffer the deflater reads, and everything else is the BGZF path above (fresh block per part — a record may
+ * straddle the blocks within a part —, EOF block, append_sam over the previous EOF block with no second header, stdout, MCX_BGZF_BLOCK, the resident route, -m, the
+ * refusal of shard_count > 1).  gzip -d of the file is the uncompressed BAM stream htslib makes of the SAM lines; no index is written, nothing is sorted.  The lines
+ * left out (mcx_bam_format_dev) are counted over the call and the total printed to stderr once, when it is not 0 (MCX_TIMING=1: beside the bgzf line, always).  (route: MCX_ROUTE_BAM.)
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -635,7 +655,8 @@ typedef struct mcx_file_opts {
 } mcx_file_opts;
 enum mcx_sam_bits {
     MCX_SAM_DEVICE = 1, /* the SAM text is made on the device */
-    MCX_SAM_BGZF = 2    /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
+    MCX_SAM_BGZF = 2,   /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
+    MCX_SAM_BAM = 4     /* ... which hold BAM records instead of SAM text (implies both) */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
@@ -646,7 +667,8 @@ enum mcx_route {
     MCX_ROUTE_PARSE = 2,   /* its records were found and packed on the device */
     MCX_ROUTE_ROWS = 4,    /* its batches entered their slots from HBM (mcx_stream_submit_dev): the resident route */
     MCX_ROUTE_SAM = 8,     /* the SAM text was made on the device */
-    MCX_ROUTE_BGZF = 16    /* ... and compressed to BGZF blocks there */
+    MCX_ROUTE_BGZF = 16,   /* ... and compressed to BGZF blocks there */
+    MCX_ROUTE_BAM = 32     /* ... as BAM records, not text */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 

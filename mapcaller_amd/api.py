@@ -74,6 +74,7 @@ SYMBOLS = [
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
+    "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -262,8 +263,9 @@ FASTQ_RULE_PLAIN, FASTQ_RULE_GZ = 0, 1  # mcx_fastq_rule
 READS_FASTQ, READS_FASTA = 0, 1  # mcx_reads_format
 ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 ROUTE_BGZF = 16
+ROUTE_BAM = 32
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
-SAM_DEVICE, SAM_BGZF = 1, 2  # mcx_sam_bits (mcx_file_opts.device_sam)
+SAM_DEVICE, SAM_BGZF, SAM_BAM = 1, 2, 4  # mcx_sam_bits (mcx_file_opts.device_sam)
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
@@ -410,6 +412,13 @@ def lib() -> C.CDLL:
         f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_sam_header.restype = C.c_int
     L.mcx_sam_header.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    for f in (L.mcx_bam_format_dev, L.mcx_bam_format):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mcx_bam_header.restype = C.c_int
+    L.mcx_bam_header.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_bam_last_ms.restype = C.c_int
+    L.mcx_bam_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_inflater_create.restype = C.c_int
     L.mcx_inflater_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
     L.mcx_inflater_free.restype = None
@@ -613,7 +622,7 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -625,13 +634,14 @@ class Mapper:
         interleaved), are parsed and packed to 2-bit rows on the device (the same reads, the same end of the input; other input is read as before).
         ``device_inflate`` and ``device_parse`` together, on BGZF FASTQ or FASTA files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
         parse, pack, map and SAM text all in HBM.  ``bgzf_sam`` = -bgzf: the SAM file is written as BGZF, its blocks deflated on the device (implies ``device_sam``; gzip -d of the
-        file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``last_route()`` says which stages ran on the device."""
+        file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``bam`` = -bam: ``sam`` is written as BAM — the records made on the device, framed by the same BGZF path (implies both;
+        unsorted, no index; not sharded).  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam else 0) | (SAM_BGZF if bgzf_sam else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -648,7 +658,7 @@ class Mapper:
 
     def last_route(self) -> Tuple[int, int]:
         """mcx_files_route: per read file of the last map_files call, the stages that ran on the device as a sum of ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS
-        (the batches entered their slots from HBM), ROUTE_SAM and ROUTE_BGZF (the SAM text left the device as BGZF blocks); the second entry is 0 for one file."""
+        (the batches entered their slots from HBM), ROUTE_SAM, ROUTE_BGZF (the SAM text left the device as BGZF blocks) and ROUTE_BAM (... of BAM records); the second entry is 0 for one file."""
         r = (C.c_uint32 * 2)()
         _check(lib().mcx_files_route(self._h, r), "mcx_files_route")
         return int(r[0]), int(r[1])
@@ -679,29 +689,7 @@ class Mapper:
         QNAMEs, ``quals`` per read the bytes of its quality line that count (at most the read's length; shorter ones are NUL-padded here;
         None: QUAL is '*'), ``aln`` the records and ``pool`` CIGAR words such that read r's are pool[aln[r].cigar_off:][:n_cigar] — map_batch's
         list of per-read arrays is accepted too —, ``extras`` what multi_lines returns."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint32)
-        n = off.size - 1
-        aln, pool = _pool_of(aln, pool)
-        name_off = np.zeros(n + 1, dtype=np.uint32)
-        name_off[1:] = np.cumsum([len(x) for x in names])
-        name_buf = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
-        si = SamIn()
-        si.bases, si.off, si.names, si.name_off = bases.ctypes.data, off.ctypes.data, name_buf.ctypes.data, name_off.ctypes.data
-        si.aln, si.cigar, si.n_reads, si.paired = aln.ctypes.data, pool.ctypes.data, n, int(paired)
-        keep = []
-        if quals is not None:
-            q = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
-            for r, b in enumerate(quals):
-                b = b[:int(off[r + 1]) - int(off[r])]
-                q[int(off[r]):int(off[r]) + len(b)] = np.frombuffer(b, dtype=np.uint8)
-            keep.append(q)
-            si.qual = q.ctypes.data
-        if extras is not None:
-            index = np.ascontiguousarray(extras[0], dtype=np.uint32)
-            x_recs, x_pool = _pool_of(extras[1], extras[2])
-            keep += [index, x_recs, x_pool]
-            si.x_index, si.x_recs, si.x_cigar = index.ctypes.data, x_recs.ctypes.data, x_pool.ctypes.data
+        si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
         nb = C.c_uint64()
         rc = lib().mcx_sam_format(self._h, C.byref(si), None, 0, None, C.byref(nb))
         if rc not in (0, ERR_CAPACITY):
@@ -709,6 +697,26 @@ class Mapper:
         text = np.zeros(max(1, nb.value), dtype=np.uint8)
         _check(lib().mcx_sam_format(self._h, C.byref(si), text.ctypes.data, nb.value, None, C.byref(nb)), "mcx_sam_format")
         return text[:nb.value].tobytes()
+
+    def bam_records(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
+                    pool: np.ndarray, extras=None) -> Tuple[bytes, int]:
+        """The uncompressed BAM records of a mapped batch, made on the device (mcx_bam_format), from what sam_text takes: (the records back to
+        back — the record of every line sam_text would give, in its order —, the lines that made none: a name of 252 bytes or more, a QUAL that
+        is not '*' and not as long as the read)."""
+        si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
+        nb, nd = C.c_uint64(), C.c_uint64()
+        rc = lib().mcx_bam_format(self._h, C.byref(si), None, 0, None, C.byref(nb), C.byref(nd))
+        if rc not in (0, ERR_CAPACITY):
+            _check(rc, "mcx_bam_format")
+        out = np.zeros(max(1, nb.value), dtype=np.uint8)
+        _check(lib().mcx_bam_format(self._h, C.byref(si), out.ctypes.data, nb.value, None, C.byref(nb), C.byref(nd)), "mcx_bam_format")
+        return out[:nb.value].tobytes(), int(nd.value)
+
+    def bam_last_ms(self) -> Tuple[float, float, float]:
+        """the last mcx_bam_format[_dev]'s device times in ms: length kernel, scan, write kernel"""
+        ms = (C.c_float * 3)()
+        _check(lib().mcx_bam_last_ms(self._h, ms), "mcx_bam_last_ms")
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def multi_lines(self, n_reads: int):
         """(multi) the last batch's extra lines: (index uint32 [n_reads + 1], records ALN_DTYPE, their CIGAR words per record) — read r's
@@ -1166,6 +1174,34 @@ def _pool_of(aln: np.ndarray, cigars):
     return aln, pool
 
 
+def _sam_in(bases, off, names, quals, paired, aln, pool, extras):
+    """(SamIn over host arrays, what keeps them alive): the arguments of Mapper.sam_text / bam_records as mcx_sam_in"""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    n = off.size - 1
+    aln, pool = _pool_of(aln, pool)
+    name_off = np.zeros(n + 1, dtype=np.uint32)
+    name_off[1:] = np.cumsum([len(x) for x in names])
+    name_buf = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+    si = SamIn()
+    si.bases, si.off, si.names, si.name_off = bases.ctypes.data, off.ctypes.data, name_buf.ctypes.data, name_off.ctypes.data
+    si.aln, si.cigar, si.n_reads, si.paired = aln.ctypes.data, pool.ctypes.data, n, int(paired)
+    keep = [bases, off, aln, pool, name_off, name_buf]
+    if quals is not None:
+        q = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
+        for r, b in enumerate(quals):
+            b = b[:int(off[r + 1]) - int(off[r])]
+            q[int(off[r]):int(off[r]) + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        keep.append(q)
+        si.qual = q.ctypes.data
+    if extras is not None:
+        index = np.ascontiguousarray(extras[0], dtype=np.uint32)
+        x_recs, x_pool = _pool_of(extras[1], extras[2])
+        keep += [index, x_recs, x_pool]
+        si.x_index, si.x_recs, si.x_cigar = index.ctypes.data, x_recs.ctypes.data, x_pool.ctypes.data
+    return si, keep
+
+
 def sam_header(index: "Index") -> bytes:
     """The @PG / @SQ lines the file front end writes ahead of the first batch (mcx_sam_header)."""
     nb = C.c_uint64()
@@ -1174,6 +1210,17 @@ def sam_header(index: "Index") -> bytes:
         _check(rc, "mcx_sam_header")
     buf = C.create_string_buffer(max(1, nb.value))
     _check(lib().mcx_sam_header(index._h, buf, nb.value, C.byref(nb)), "mcx_sam_header")
+    return buf.raw[:nb.value]
+
+
+def bam_header(index: "Index") -> bytes:
+    """The uncompressed BAM header the file front end writes (as BGZF blocks) ahead of the first batch with ``bam``: magic, sam_header's text, the contigs (mcx_bam_header)."""
+    nb = C.c_uint64()
+    rc = lib().mcx_bam_header(index._h, None, 0, C.byref(nb))
+    if rc not in (0, ERR_CAPACITY):
+        _check(rc, "mcx_bam_header")
+    buf = C.create_string_buffer(max(1, nb.value))
+    _check(lib().mcx_bam_header(index._h, buf, nb.value, C.byref(nb)), "mcx_bam_header")
     return buf.raw[:nb.value]
 
 

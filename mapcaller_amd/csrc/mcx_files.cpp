@@ -173,6 +173,7 @@ struct Run {
     const bool wants_sam;
     const bool dev_sam;         // the text is made on the device (mcx_sam.hip); without a SAM file there is none to make
     const bool bgzf;            // ... and compressed there: the file is BGZF (mcx_deflate.hip)
+    const bool bam;             // ... of BAM records, not text (mcx_bam.hip)
     Timing t;
     Shards sh;
     Pool pool;                  // parse + pack
@@ -237,7 +238,7 @@ struct Run {
           shard_count(o.shard_count > 1 ? (uint64_t)o.shard_count : 1), shard_rank(shard_count > 1 ? (uint64_t)o.shard_rank : 0), sharded(shard_count > 1),
           batch_reads(std::max<uint64_t>(kReadChunkSize, mcx_ctx_max_reads(ctx) / kReadChunkSize * kReadChunkSize)), per_file((uint32_t)(two ? batch_reads / 2 : batch_reads)),
           threads(o.host_threads > 0 ? o.host_threads : (int)std::min<unsigned>(64, std::max<unsigned>(1, mcx_usable_cpus() * 3 / 4 / (unsigned)shard_count))),
-          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), pool(threads), fpool(threads),
+          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), pool(threads), fpool(threads),
           n_objects(sharded ? 16 : 12), parsed(2), mapped(2), formatted(2), spare((size_t)n_objects),
           profile(mcx_ctx_has_profile(ctx)), multi(mcx_ctx_multi(ctx))
     {
@@ -269,7 +270,7 @@ struct Run {
         if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
-        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u);
+        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u);
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
@@ -337,7 +338,7 @@ struct Run {
             mcx_deflater *d = nullptr;
             if (mcx_deflater_create(idx->device, 1u << 20, &d) != 0) return mcx_set_error(MCX_ERR_DEVICE, std::string("-bgzf: ") + mcx_last_error());
             deflater.reset(d);
-            zs.deflater = d; zs.block = 65280;
+            zs.deflater = d; zs.block = 65280; zs.bam = bam ? 1 : 0;
             if (const char *env = getenv("MCX_BGZF_BLOCK")) { // (debug override: the bytes of text per block)
                 const long v = atol(env);
                 if (v >= 1 && v <= 65280) zs.block = (uint32_t)v;
@@ -367,8 +368,13 @@ struct Run {
         }
         if (e == 0 && !opt.append_sam) {
             std::string hdr;
-            sam_header(hix, hdr);
-            if (bgzf) { // the header as BGZF blocks of its own
+            if (bam) { // -bam: the binary header, text and contigs
+                uint64_t n = 0;
+                (void)mcx_bam_header(idx, nullptr, 0, &n);
+                hdr.resize((size_t)n);
+                if (n == 0 || mcx_bam_header(idx, (uint8_t *)&hdr[0], n, &n) != 0) e = mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
+            } else sam_header(hix, hdr);
+            if (bgzf && e == 0) { // the header as BGZF blocks of its own
                 std::string blocks((size_t)mcx_bgzf_bound(hdr.size(), zs.block), '\0');
                 uint64_t made = 0;
                 const auto t0 = now();
@@ -1080,16 +1086,22 @@ struct Run {
         t.w_mapped = t.wall();
     }
 
+    // -bam: the lines htslib's parser would have rejected made no record; said once a call, when there are any
+    void report_dropped() const
+    {
+        if (bam && zs.dropped) fprintf(stderr, "Warning! %llu SAM lines made no BAM record (a read name of 252 bytes or more, or a quality line shorter than its read)\n", (unsigned long long)zs.dropped);
+    }
     void report_timing() const
     {
         if (!getenv("MCX_TIMING")) return;
         std::string e;
         for (size_t k = 0; k < t.each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(t.each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
-        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
+        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks, 32 BAM records): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
         if (dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t.m_sam);
         if (bgzf) fprintf(stderr, "[mcx_map_files] bgzf: %llu bytes of text -> %llu bytes of blocks (%u bytes of text a block), the deflater took %.3f s of them\n",
                           (unsigned long long)zs.text_bytes, (unsigned long long)zs.out_bytes, zs.block, zs.seconds);
+        if (bam) fprintf(stderr, "[mcx_map_files] bam: the text above is BAM records; %llu lines made none\n", (unsigned long long)zs.dropped);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");
         fprintf(stderr, "[mcx_map_files] waits: reader for room behind it %.3f | mapper for a parsed batch %.3f, for copies out %.3f | formatter for the writer %.3f || mapper's calls: submit %.3f, next %.3f, map_batch_dev %.3f, mapped %.3f\n", t.p_push, t.m_take, t.m_collect, t.f_push, t.m_submit, t.m_in, t.m_dev, t.m_out);
@@ -1105,10 +1117,11 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     mcx_file_opts opt;
     mcx_file_opts_default(&opt);
     if (fo) opt = *fo;
+    if (opt.device_sam & MCX_SAM_BAM) opt.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF; // (BAM records are made on the device and framed as BGZF)
     if (opt.shard_count > 1 && (!opt.exchange || !opt.exchange->allgather || opt.exchange->size != opt.shard_count || opt.exchange->rank != opt.shard_rank))
         return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_ex: a sharded run needs mcx_file_opts.exchange with the shard's rank and count");
     if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_BGZF))
-        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF (-bgzf with -gpus N / -devices): map on one GPU, or without -bgzf");
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF or as BAM (-bgzf / -bam with -gpus N / -devices): map on one GPU, or without them");
     Run run(c, fq1, fq2, opt, sam_path, stats);
     if (int e = run.open_input()) return e;
     if (int e = run.open_output()) return e;
@@ -1121,6 +1134,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     writer.join();
     reader.join();
     run.keep_objects();
+    run.report_dropped();
     run.report_timing();
     return run.close_output();
 }

@@ -38,12 +38,16 @@ void **mcx_ctx_files_slot(mcx_ctx *, void (*drop)(void *));
 // the same for mcx_sam.hip's device buffers, and the stream (a hipStream_t) the context's kernels run on
 void **mcx_ctx_sam_slot(mcx_ctx *, void (*drop)(void *));
 void *mcx_ctx_stream(mcx_ctx *);
-// -bgzf: the run's deflater with its block size, and what it has done so far (text in, blocks out, seconds of the calling thread)
-struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; };
+// -bgzf: the run's deflater with its block size, and what it has done so far (text in, blocks out, seconds of the calling thread); bam (-bam): what goes in is
+// not a part's SAM text but its BAM records (mcx_bam.hip), and dropped counts the lines that made none
+struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; int bam; uint64_t dropped; };
 // -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory; bgzf (null: none): the text is
 // compressed in HBM first and its BGZF blocks arrive instead, *n_bytes their size
 int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
                  const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf);
+// -bam (mcx_bam.hip): mcx_bam_format_dev for sam_part's input — the records of a part into d_out[0 .. cap), *n_bytes their exact size (MCX_ERR_CAPACITY, nothing
+// written, when cap is smaller), *n_dropped the lines that made none; the context's device is current
+int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t cap, uint64_t *n_bytes, uint64_t *n_dropped);
 // -gpu_inflate (mcx_inflate.hip): the host form of mcx_inflate in two halves, so that the reader stages a stretch's bytes while the stretch before is on
 // the device — begin packs the members' bytes (src_off into src) into page-locked staging and queues copy in, kernel and copy out; end waits for the oldest
 // begin and hands the text to dst + each member's dst_off (0, or MCX_ERR_IO when a member failed).  At most two begins outstanding; caps: what one holds.

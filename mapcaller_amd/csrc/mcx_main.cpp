@@ -37,7 +37,7 @@ static void usage(const char *prog)
 {
     fprintf(stderr,
             "MapCaller seed-and-extend path on MI355X\n\n"
-            "Usage: %s -i Index_Prefix -f <ReadFile_A1 ...> [-f2 <ReadFile_A2 ...>] [-alg nw|ksw2] [-sam out.sam]\n"
+            "Usage: %s -i Index_Prefix -f <ReadFile_A1 ...> [-f2 <ReadFile_A2 ...>] [-alg nw|ksw2] [-sam out.sam | -bam out.bam]\n"
             "       %s index ref.fa prefix\n\n"
             "Options: -i STR        BWT_Index_Prefix\n"
             "         -r STR        Reference filename (format:fa); an index is built on the GPU first\n"
@@ -54,6 +54,8 @@ static void usage(const char *prog)
             "         -gpu_sam      make the SAM text on the GPU instead of with host threads (same bytes; nothing without -sam)\n"
             "         -bgzf         write the SAM file as BGZF (name it .sam.gz: samtools, bgzip -d, zcat read it), its blocks deflated on the GPU;\n"
             "                       implies -gpu_sam; gzip -d gives the bytes of the plain file; not with -gpus N / -devices\n"
+            "         -bam          BAM output filename ('-' = stdout) instead of -sam (the later of the two counts): the records are made and their BGZF blocks\n"
+            "                       deflated on the GPU; unsorted, no index; not with -gpus N / -devices\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -103,6 +105,7 @@ int main(int argc, char **argv)
     mcx_file_opts_default(&fo);
     bool want_vcf = true; // bVCFoutput, main.cpp:171
     bool multi = false;   // -m: a SAM line for every alignment with the best score
+    bool bam = false;     // -bam: the output file holds BAM records
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -127,7 +130,8 @@ int main(int argc, char **argv)
             if (lf) fclose(lf);
         }
         else if (p == "-alg" && i + 1 < argc) o.alg = strcmp(argv[++i], "ksw2") == 0 ? 1 : 0;
-        else if (p == "-sam" && i + 1 < argc) sam = argv[++i];
+        else if (p == "-sam" && i + 1 < argc) { sam = argv[++i]; bam = false; }
+        else if (p == "-bam" && i + 1 < argc) { sam = argv[++i]; bam = true; } // (main.cpp:274-285: one output name, the switch that comes last says what it holds)
         else if (p == "-indel" && i + 1 < argc) { o.max_pos_diff = atoi(argv[++i]); if (o.max_pos_diff > 100) { o.max_pos_diff = 100; fprintf(stderr, "Warning! The maximal indel size is 100!\n"); } }
         else if (p == "-maxmm" && i + 1 < argc) o.max_mismatch_rate = (float)atof(argv[++i]);
         else if (p == "-t" && i + 1 < argc) { if ((fo.host_threads = atoi(argv[++i])) <= 0) { fprintf(stderr, "Warning! The thread number should be positive!\n"); fo.host_threads = 4; } }
@@ -160,13 +164,14 @@ int main(int argc, char **argv)
         else if (p == "-bgzf") fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
-        else if (p == "-bam") { fprintf(stderr, "Error! %s is not supported by mapcaller-mi355x (DESIGN.md, deliberate deviations)\n", argv[i]); return 1; }
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
     }
     if (f1.empty()) { fprintf(stderr, "Warning! Please specify a valid read input!\n"); usage(argv[0]); return 0; }
     if (!f2.empty() && f1.size() != f2.size()) { fprintf(stderr, "Warning! Paired-end reads input numbers do not match!\n"); return 0; }
     if (devices.empty()) for (int r = 0; r < n_gpus; r++) devices.push_back(n_gpus == 1 ? gpu : r);
     n_gpus = (int)devices.size();
+    if (bam) fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF | MCX_SAM_BAM;
+    if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the
     // early ones (a failed build leaves partial files behind it)

@@ -20,6 +20,7 @@
 #include "../../include/mcx.h"
 #include "mcx_sam.h"
 #include "mcx_internal.h"
+#include "mcx_sam_state.h"
 
 using namespace mcx;
 
@@ -98,81 +99,12 @@ __global__ void __launch_bounds__(64 * kSamWaves) k_sam_write(mcx_sam_in in, Sam
     }
 }
 
-// what a context keeps for the formatter: the contigs' names (once), the lengths and offsets of a batch, and — for the file front end —
-// the names, qualities and text of a batch part in HBM
-struct SamState {
-    char *d_cn_text = nullptr; uint32_t *d_cn_off = nullptr;
-    uint64_t *d_len = nullptr, *d_off = nullptr; uint64_t cap_reads = 0;
-    void *d_tmp = nullptr; size_t tmp_bytes = 0;
-    uint64_t *h_total = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float ms[3] = {0, 0, 0}; // the last call's length kernel, scan, write kernel
-    uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
-    uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
-    ~SamState()
-    {
-        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_names, d_qual, d_text, d_name_off, d_bgzf};
-        for (void *q : p) if (q) (void)hipFree(q);
-        if (h_total) (void)hipHostFree(h_total);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-};
-
-int state_of(mcx_ctx *c, SamState **out)
-{
-    void **slot = mcx_ctx_sam_slot(c, [](void *p) { delete (SamState *)p; });
-    if (!*slot) *slot = new SamState();
-    SamState *st = (SamState *)*slot;
-    if (!st->d_cn_text) { // the contigs' names go to the device once per context
-        const HostIndex &hx = mcx_ctx_index(c)->host;
-        std::string text;
-        std::vector<uint32_t> off(1, 0);
-        for (const std::string &s : hx.chr_name) { text += s; off.push_back((uint32_t)text.size()); }
-        HIP_TRY(hipMalloc((void **)&st->d_cn_text, text.size() + 16));
-        HIP_TRY(hipMalloc((void **)&st->d_cn_off, off.size() * 4));
-        HIP_TRY(hipMemcpy(st->d_cn_text, text.data(), text.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(st->d_cn_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipHostMalloc((void **)&st->h_total, 8, hipHostMallocDefault));
-        for (hipEvent_t &e : st->ev) HIP_TRY(hipEventCreate(&e));
-    }
-    *out = st;
-    return 0;
-}
-
-template <class T> int grow(T **p, uint64_t *cap, uint64_t need, const char *what)
-{
-    if (need <= *cap) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const uint64_t want = need + need / 8 + 4096;
-    if (hipMalloc((void **)p, want * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return mcx_set_error(MCX_ERR_DEVICE, std::string("no room in HBM for ") + what + " (" + std::to_string(want * sizeof(T) >> 20) + " MB): map with a smaller -batch");
-    }
-    *cap = want;
-    return 0;
-}
-
 // in: the struct in host memory, its pointers the device's
 int format_dev(mcx_ctx *c, SamState *st, const mcx_sam_in &in, uint8_t *d_text, uint64_t cap, uint64_t *d_line_off, uint64_t *n_bytes)
 {
     hipStream_t s = (hipStream_t)mcx_ctx_stream(c);
     const uint64_t n = in.n_reads;
-    if (n + 1 > st->cap_reads) {
-        uint64_t cap_b = st->cap_reads;
-        int rc;
-        if ((rc = grow(&st->d_len, &st->cap_reads, n + 1, "the SAM lines' lengths"))) return rc;
-        if ((rc = grow(&st->d_off, &cap_b, n + 1, "the SAM lines' offsets"))) return rc;
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, st->d_len, st->d_off, (int)st->cap_reads, s));
-        if (need > st->tmp_bytes) {
-            if (st->d_tmp) (void)hipFree(st->d_tmp);
-            st->d_tmp = nullptr; st->tmp_bytes = 0;
-            HIP_TRY(hipMalloc(&st->d_tmp, need));
-            st->tmp_bytes = need;
-        }
-    }
+    if (int rc = sam_scan_room(st, n + 1, s)) return rc;
     const SamContigs cn = {st->d_cn_text, st->d_cn_off};
     uint64_t *off = d_line_off ? d_line_off : st->d_off;
     HIP_TRY(hipEventRecord(st->ev[0], s));
@@ -214,7 +146,7 @@ extern "C" int mcx_sam_format_dev(mcx_ctx *c, const mcx_sam_in *d_in, uint8_t *d
     if (!in_ok(d_in)) return mcx_set_error(MCX_ERR_ARG, "mcx_sam_format_dev: null argument");
     HIP_TRY(hipSetDevice(mcx_ctx_index(c)->device));
     SamState *st;
-    if (int rc = state_of(c, &st)) return rc;
+    if (int rc = sam_state_of(c, &st)) return rc;
     return format_dev(c, st, *d_in, d_text, cap, d_line_off, n_bytes);
 }
 
@@ -223,7 +155,7 @@ extern "C" int mcx_sam_last_ms(mcx_ctx *c, float ms[3])
 {
     SamState *st;
     if (!c || !ms) return mcx_set_error(MCX_ERR_ARG, "mcx_sam_last_ms: null argument");
-    if (int rc = state_of(c, &st)) return rc;
+    if (int rc = sam_state_of(c, &st)) return rc;
     memcpy(ms, st->ms, sizeof st->ms);
     return 0;
 }
@@ -237,7 +169,7 @@ extern "C" int mcx_sam_format(mcx_ctx *c, const mcx_sam_in *in, uint8_t *text, u
     if (!in_ok(in)) return mcx_set_error(MCX_ERR_ARG, "mcx_sam_format: null argument");
     HIP_TRY(hipSetDevice(mcx_ctx_index(c)->device));
     SamState *st;
-    if (int rc = state_of(c, &st)) return rc;
+    if (int rc = sam_state_of(c, &st)) return rc;
     // the words of the pools the records point into
     uint64_t words = 0, x_words = 0;
     for (uint64_t r = 0; r < n; r++) words = std::max<uint64_t>(words, (uint64_t)(uint32_t)in->aln[r].cigar_off + (uint64_t)std::max(in->aln[r].n_cigar, 0));
@@ -312,13 +244,13 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
     HIP_TRY(hipSetDevice(mcx_ctx_index(c)->device));
     SamState *st;
     int rc;
-    if ((rc = state_of(c, &st))) return rc;
+    if ((rc = sam_state_of(c, &st))) return rc;
     hipStream_t s = (hipStream_t)mcx_ctx_stream(c);
     if (!on_device) {
         const uint64_t name_bytes = name_off[n_reads];
-        if ((rc = grow(&st->d_names, &st->cap_names, name_bytes + 16, "the reads' names"))) return rc;
-        if ((rc = grow(&st->d_name_off, &st->cap_name_off, (uint64_t)n_reads + 1, "the reads' names"))) return rc;
-        if (qual && (rc = grow(&st->d_qual, &st->cap_qual, qual_bytes + 16, "the reads' qualities"))) return rc;
+        if ((rc = sam_grow(&st->d_names, &st->cap_names, name_bytes + 16, "the reads' names"))) return rc;
+        if ((rc = sam_grow(&st->d_name_off, &st->cap_name_off, (uint64_t)n_reads + 1, "the reads' names"))) return rc;
+        if (qual && (rc = sam_grow(&st->d_qual, &st->cap_qual, qual_bytes + 16, "the reads' qualities"))) return rc;
         HIP_TRY(hipMemcpyAsync(st->d_names, names, name_bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(st->d_name_off, name_off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, s));
         if (qual) HIP_TRY(hipMemcpyAsync(st->d_qual, qual, qual_bytes, hipMemcpyHostToDevice, s));
@@ -332,20 +264,23 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
         uint32_t n_recs = 0, n_words = 0;
         if ((rc = mcx_multi_lines(c, &in.x_index, &in.x_recs, &in.x_cigar, &n_recs, &n_words))) return rc;
     }
-    // the size first (nothing is written into a text buffer that is too small), then room for it on both sides
-    uint64_t total = 0;
-    rc = format_dev(c, st, in, st->d_text, st->cap_text, nullptr, &total);
+    // the size first (nothing is written into a text buffer that is too small), then room for it on both sides; -bam: the part's records instead of its text
+    const bool bam = bgzf && bgzf->bam;
+    uint64_t total = 0, dropped = 0;
+    auto make = [&] { return bam ? mcx_bam_part_dev(c, &in, st->d_text, st->cap_text, &total, &dropped) : format_dev(c, st, in, st->d_text, st->cap_text, nullptr, &total); };
+    rc = make();
     if (rc == MCX_ERR_CAPACITY) {
-        if ((rc = grow(&st->d_text, &st->cap_text, total + 16, "the batch's SAM text"))) return rc;
-        rc = format_dev(c, st, in, st->d_text, st->cap_text, nullptr, &total);
+        if ((rc = sam_grow(&st->d_text, &st->cap_text, total + 16, bam ? "the batch's BAM records" : "the batch's SAM text"))) return rc;
+        rc = make();
     }
     if (rc) return rc;
+    if (bam) bgzf->dropped += dropped;
     // -bgzf: the part's text is compressed where it lies (a fresh block at its start), and only the blocks leave the device
     const uint8_t *d_from = st->d_text;
     if (bgzf && total) {
         const auto t0 = std::chrono::steady_clock::now();
         const uint64_t bound = mcx_bgzf_bound(total, bgzf->block);
-        if ((rc = grow(&st->d_bgzf, &st->cap_bgzf, bound, "the batch's BGZF blocks"))) return rc;
+        if ((rc = sam_grow(&st->d_bgzf, &st->cap_bgzf, bound, "the batch's BGZF blocks"))) return rc;
         uint64_t made = 0;
         if ((rc = mcx_bgzf_deflate_dev(bgzf->deflater, st->d_text, total, st->d_bgzf, st->cap_bgzf, &made))) return rc;
         bgzf->text_bytes += total; bgzf->out_bytes += made;

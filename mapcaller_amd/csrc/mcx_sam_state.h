@@ -1,0 +1,99 @@
+// mapcaller_amd/csrc/mcx_sam_state.h — what a context keeps for its output formatters on the device (mcx_sam.hip: SAM text; mcx_bam.hip: BAM records), which take
+// the same input and share the lengths, the scan's scratch and — in the file front end — the part's buffers.  Not part of the ABI; HIP translation units only.
+#ifndef MCX_SAM_STATE_H
+#define MCX_SAM_STATE_H
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <string>
+#include <vector>
+#include "mcx_internal.h"
+
+namespace mcx {
+
+// the contigs' names (once), the lengths and offsets of a batch, and — for the file front end — the names, qualities and text (or records) of a batch part in HBM
+struct SamState {
+    char *d_cn_text = nullptr; uint32_t *d_cn_off = nullptr;
+    uint64_t *d_len = nullptr, *d_off = nullptr; uint64_t cap_reads = 0;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;
+    uint64_t *h_total = nullptr;            // page-locked: [0] the batch's bytes, [1] (BAM) the lines that made no record
+    unsigned long long *d_dropped = nullptr; // (BAM) counted by the length kernel
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float ms[3] = {0, 0, 0}; // the last call's length kernel, scan, write kernel
+    uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
+    uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
+    ~SamState()
+    {
+        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf};
+        for (void *q : p) if (q) (void)hipFree(q);
+        if (h_total) (void)hipHostFree(h_total);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+static inline int sam_state_of(mcx_ctx *c, SamState **out)
+{
+    void **slot = mcx_ctx_sam_slot(c, [](void *p) { delete (SamState *)p; });
+    if (!*slot) *slot = new SamState();
+    SamState *st = (SamState *)*slot;
+    if (!st->d_cn_text) { // the contigs' names go to the device once per context
+        const HostIndex &hx = mcx_ctx_index(c)->host;
+        std::string text;
+        std::vector<uint32_t> off(1, 0);
+        for (const std::string &s : hx.chr_name) { text += s; off.push_back((uint32_t)text.size()); }
+        hipError_t e = hipMalloc((void **)&st->d_cn_off, off.size() * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&st->d_dropped, 8);
+        if (e == hipSuccess) e = hipMemcpy(st->d_cn_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !st->h_total) e = hipHostMalloc((void **)&st->h_total, 16, hipHostMallocDefault);
+        for (hipEvent_t &ev : st->ev) if (e == hipSuccess && !ev) e = hipEventCreate(&ev);
+        char *d_text = nullptr;
+        if (e == hipSuccess) e = hipMalloc((void **)&d_text, text.size() + 16);
+        if (e == hipSuccess) e = hipMemcpy(d_text, text.data(), text.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (d_text) (void)hipFree(d_text);
+            if (st->d_cn_off) (void)hipFree(st->d_cn_off);
+            if (st->d_dropped) (void)hipFree(st->d_dropped);
+            st->d_cn_off = nullptr; st->d_dropped = nullptr;
+            return mcx_set_error(MCX_ERR_DEVICE, std::string("the formatter's buffers: ") + hipGetErrorString(e));
+        }
+        st->d_cn_text = d_text; // (set last: a half-made state is made again)
+    }
+    *out = st;
+    return 0;
+}
+
+template <class T> int sam_grow(T **p, uint64_t *cap, uint64_t need, const char *what)
+{
+    if (need <= *cap) return 0;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const uint64_t want = need + need / 8 + 4096;
+    if (hipMalloc((void **)p, want * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return mcx_set_error(MCX_ERR_DEVICE, std::string("no room in HBM for ") + what + " (" + std::to_string(want * sizeof(T) >> 20) + " MB): map with a smaller -batch");
+    }
+    *cap = want;
+    return 0;
+}
+
+// room for the lengths, the offsets and the scan's scratch at n_reads + 1 entries
+static inline int sam_scan_room(SamState *st, uint64_t entries, hipStream_t s)
+{
+    if (entries <= st->cap_reads) return 0;
+    uint64_t cap_b = st->cap_reads;
+    int rc;
+    if ((rc = sam_grow(&st->d_len, &st->cap_reads, entries, "the lines' lengths"))) return rc;
+    if ((rc = sam_grow(&st->d_off, &cap_b, entries, "the lines' offsets"))) return rc;
+    size_t need = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, st->d_len, st->d_off, (int)st->cap_reads, s) != hipSuccess) return mcx_set_error(MCX_ERR_DEVICE, "the scan over the lines' lengths cannot be sized");
+    if (need > st->tmp_bytes) {
+        if (st->d_tmp) (void)hipFree(st->d_tmp);
+        st->d_tmp = nullptr; st->tmp_bytes = 0;
+        if (hipMalloc(&st->d_tmp, need) != hipSuccess) { (void)hipGetLastError(); return mcx_set_error(MCX_ERR_DEVICE, "no room in HBM for the scan over the lines' lengths"); }
+        st->tmp_bytes = need;
+    }
+    return 0;
+}
+
+} // namespace mcx
+#endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MapCaller's command line on one or several MI355X of a node.
 
-    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf]] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
+    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 -m mapcaller_amd.run -i idx -f r1.fq -f2 r2.fq -sam out.sam -vcf out.vcf
 
 One process per GPU.  The input stream is cut into batches that are dealt to the ranks in turn
@@ -26,6 +26,13 @@ import torch
 from . import api, dist as mdist
 
 
+class _Output(argparse.Action):
+    """-sam FILE / -bam FILE name the one output file; the switch that comes last says what it holds (reference src/main.cpp:274-285)"""
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.sam = values
+        namespace.bam = option_string == "-bam"
+
+
 def parse(argv):
     ap = argparse.ArgumentParser(prog="mapcaller_amd.run", add_help=True, prefix_chars="-", allow_abbrev=False)
     ap.add_argument("-i", dest="index", required=True, help="BWT index prefix")
@@ -33,7 +40,9 @@ def parse(argv):
     ap.add_argument("-f2", dest="f2", nargs="*", default=[], help="files with #2 mates reads")
     ap.add_argument("-p", "-pair", dest="interleaved", action="store_true", help="paired-end reads are interlaced in the same file")
     ap.add_argument("-alg", default="nw", choices=["nw", "ksw2"])
-    ap.add_argument("-sam", default=None)
+    ap.add_argument("-sam", default=None, action=_Output)
+    ap.add_argument("-bam", dest="sam", action=_Output, metavar="FILE", help="BAM output instead of -sam (the later of the two counts): records made and BGZF blocks deflated on the GPU; unsorted, no index; one process only")
+    ap.set_defaults(bam=False)
     ap.add_argument("-vcf", default="output.vcf")
     ap.add_argument("-no_vcf", action="store_true")
     ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
@@ -93,6 +102,8 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.bam and world > 1:
+        sys.exit("-bam writes one BGZF stream from one GPU: it cannot be combined with several ranks (a sharded BAM writer does not exist yet)")
     if a.bgzf and world > 1:
         sys.exit("-bgzf writes one BGZF stream from one GPU: it cannot be combined with several ranks (a sharded BGZF writer does not exist yet)")
     n_dev = torch.cuda.device_count()
@@ -122,7 +133,7 @@ def main(argv=None):
         f2 = a.f2[k] if a.f2 else None
         # (the ranks write into the one SAM file, every batch's lines at their final place: mcx_map_files_ex)
         st = mapper.map_files(f1, f2, a.sam or None, interleaved=a.interleaved, threads=a.threads,
-                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf)
+                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam)
         for key in totals:
             totals[key] += st[key]
         if td:
