@@ -143,6 +143,7 @@ struct mcx_ctx {
     struct PrePacked { const uint32_t *packed = nullptr; const uint8_t *bases = nullptr; int paired = 0; const uint32_t *any_n = nullptr; } pre;
     int last_paired = 1;                 // what the last batch was mapped as: the guess a batch on its way in is packed under
     const uint32_t *packed_now = nullptr; // the 2-bit form the batch in flight is mapped from (d_packed, or a slot's)
+    int wpad_now = 0;                     // ... and the words from one of its rows to the next: what the batch's longest read needs, wpad at the most (a slot's rows: wpad)
     Knobs kn;
     Params pm;
     mcx_opts opts;
@@ -153,7 +154,7 @@ struct mcx_ctx {
     uint32_t *d_kscratch = nullptr; // k_rescue's scratch for reads with N: a third per set of pass resources
     hipEvent_t ev_pack[2] = {nullptr, nullptr};
     uint32_t *d_read_ext = nullptr, *d_read_blocks = nullptr;
-    uint32_t *d_packed = nullptr; int wpad = 0; // 2-bit form of the batch's reads
+    uint32_t *d_packed = nullptr; int wpad = 0; // 2-bit form of the batch's reads: room for rows of wpad words, what a read of max_read_len takes (a batch's own stride: wpad_now)
     uint32_t *d_order = nullptr; // the pairs of a pass by weight (k_order_*; their class counts: CNT_ORDER)
     uint8_t *d_done = nullptr;                           // per pair of a pass: k_simple wrote its records (the per-pair kernels skip it)
     uint32_t *d_sl_pairs = nullptr, *d_sl_list = nullptr; // the straight-line pairs that wait for a small gapped extension (SimpleLater)

@@ -22,6 +22,7 @@
 // mcx_ctx.h's), -m (mcx_ctx_set_multi, mcx_multi_*), mcx_bwt_search_batch and mcx_cigar_words.  The other units of the library
 // reach this one through the ABI, pack_reads() and reserve_tier0().
 #include "mcx_ctx.h"
+#include "mcx_pack.h"
 #include <hipcub/hipcub.hpp>
 
 // ---------------------------------------------------------------------------------------------
@@ -86,111 +87,45 @@ struct SeedOut {
     const uint8_t *src_state; Layout src_lay; Caps src_caps;
 };
 
-// 16 bytes from any address: two aligned 16-byte fetches and a byte funnel
-static __device__ __forceinline__ U4 load16_unaligned(const uint8_t *p)
-{
-    const uintptr_t a = (uintptr_t)p;
-    const U4 *q = (const U4 *)(a & ~(uintptr_t)15);
-    const U4 lo = q[0];
-    const unsigned sh = (unsigned)(a & 15);
-    if (sh == 0) return lo;
-    const U4 hi = q[1];
-    const unsigned qd = sh >> 2, b = sh & 3;
-    uint32_t s0, s1, s2, s3, s4;
-    switch (qd) {
-    case 0: s0 = lo.x; s1 = lo.y; s2 = lo.z; s3 = lo.w; s4 = hi.x; break;
-    case 1: s0 = lo.y; s1 = lo.z; s2 = lo.w; s3 = hi.x; s4 = hi.y; break;
-    case 2: s0 = lo.z; s1 = lo.w; s2 = hi.x; s3 = hi.y; s4 = hi.z; break;
-    default: s0 = lo.w; s1 = hi.x; s2 = hi.y; s3 = hi.z; s4 = hi.w; break;
-    }
-    U4 r;
-    r.x = __builtin_amdgcn_alignbyte(s1, s0, b); r.y = __builtin_amdgcn_alignbyte(s2, s1, b);
-    r.z = __builtin_amdgcn_alignbyte(s3, s2, b); r.w = __builtin_amdgcn_alignbyte(s4, s3, b);
-    return r;
-}
-
-// four ASCII bytes (first base in the low byte) -> 8 code bits (first base on top) and 4 N flags
-// (first base on top); `comp`: complement the bases (mate 2).  nt4_code (mcx_fm.h) on four lanes of
-// one register: fold case, A/C/G/T membership by zero-byte tests, (c >> 1) & 3 hashes A0 C1 T2 G3.
-// (lower: 4 flags likewise for bytes with bit 5 set — a lower-case letter where the byte is a base at all)
-static __device__ __forceinline__ void pack4(uint32_t w, bool comp, uint32_t &codes, uint32_t &flags, uint32_t &lower)
-{
-    const uint32_t c = w & 0xDFDFDFDFu;
-    auto zero_bytes = [](uint32_t t) { return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu); }; // 0x80 where a byte is 0
-    const uint32_t member = (zero_bytes(c ^ 0x41414141u) | zero_bytes(c ^ 0x43434343u) | zero_bytes(c ^ 0x47474747u) | zero_bytes(c ^ 0x54545454u)) >> 7; // 0x01 per base
-    const uint32_t h = (c >> 1) & 0x03030303u;
-    uint32_t code = h ^ ((h >> 1) & 0x01010101u);
-    if (comp) code ^= 0x03030303u;
-    code &= member * 3u;
-    const uint32_t y = __builtin_bswap32(code), n = __builtin_bswap32(member ^ 0x01010101u);
-    codes = (y | (y >> 6) | (y >> 12) | (y >> 18)) & 0xFFu;
-    flags = (n | (n >> 7) | (n >> 14) | (n >> 21)) & 0xFu;
-    const uint32_t l = __builtin_bswap32((w >> 5) & 0x01010101u);
-    lower = (l | (l >> 7) | (l >> 14) | (l >> 21)) & 0xFu;
-}
-
-// 16 oriented bases i0 .. i0+15 of a read -> (code word, MSB first; 16 N flags, bit 15 = base i0);
-// bases past the read end give code 0 and flag 1; odd: 16 flags likewise for bytes of the read that are not an upper-case A C G T
-// (what the -vcf bookkeeping asks of a read: mcx_profile.h), 0 past the read end
-static __device__ __forceinline__ void pack16(const ReadRef &rd, int i0, uint32_t &codes, uint32_t &flags, uint32_t &odd)
-{
-    const int rlen = rd.rlen;
-    int n = rlen - i0; if (n > 16) n = 16;
-    codes = 0; flags = 0xFFFFu; odd = 0;
-    if (n <= 0) return;
-    // the span of the file's bytes under these bases: forward [i0, i0+n); mate 2 (reverse-complemented) [rlen-i0-n, rlen-i0) backwards
-    const int a0 = rd.flipped ? rlen - i0 - n : i0;
-    U4 v = load16_unaligned(rd.ascii + a0);
-    if (rd.flipped) { // byte order reversed: the span's last byte first
-        const U4 t = v;
-        v.x = __builtin_bswap32(t.w); v.y = __builtin_bswap32(t.z); v.z = __builtin_bswap32(t.y); v.w = __builtin_bswap32(t.x);
-    }
-    uint32_t c0, f0, c1, f1, c2, f2, c3, f3, l0, l1, l2, l3;
-    pack4(v.x, rd.flipped != 0, c0, f0, l0); pack4(v.y, rd.flipped != 0, c1, f1, l1); pack4(v.z, rd.flipped != 0, c2, f2, l2); pack4(v.w, rd.flipped != 0, c3, f3, l3);
-    uint32_t c = (c0 << 24) | (c1 << 16) | (c2 << 8) | c3, f = (f0 << 12) | (f1 << 8) | (f2 << 4) | f3, o = f | (l0 << 12) | (l1 << 8) | (l2 << 4) | l3;
-    if (n < 16) {
-        const int pad = 16 - n;
-        if (rd.flipped) { c <<= 2 * pad; f = (f << pad) & 0xFFFFu; o = (o << pad) & 0xFFFFu; } // the n bytes sat at the end of the reversed vector
-        else { c &= ~0u << (2 * pad); o &= ~0u << pad; }
-        f |= (1u << pad) - 1u;
-        if (!rd.flipped) f &= 0xFFFFu;
-    }
-    codes = c; flags = f; odd = o & 0xFFFFu;
-}
-
 // The packed form of every read of a batch (mcx_fm.h pack_read: 16 bases per code word, one zero
-// word, 32 N flags per mask word, one all-ones word).  One thread per 32 bases: two 16-byte spans
-// of the file's bytes, fetched as aligned 16-byte words by neighbouring threads, so the batch is
-// packed at streaming speed instead of base by base in the seeding lanes.  Mate 2 is packed
-// reverse-complemented (ReadMapping.cpp:451).  tpr threads per read: ceil(max_read_len / 32) + 1.
+// word, 32 N flags per mask word, one all-ones word; the arithmetic is mcx_pack.h's).  Mate 2 is packed
+// reverse-complemented (ReadMapping.cpp:451).
 // (any_n: set when a read of the batch holds a byte that is not one of ACGT — the passes of the large tier, which are queued after the
 //  host has looked at the batch's counters anyway, leave out the kernel for such reads when there is none)
 // (odd_flag, with the -vcf bookkeeping: bit 1 of the read's flag byte is set when the read holds a byte that is not an upper-case A C G T)
+//
+// part m of read r straight from HBM: 32 bases (m < mask words of the read), or the row's two constant words (m = that count)
+static __device__ __forceinline__ void pack_read_part(const ReadBatch &rb, uint32_t r, int m, int paired, int wpad, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag)
+{
+    const uint32_t a = rb.off[r];
+    const int rlen = (int)(rb.off[r + 1] - a), flipped = (paired && (r & 1)) ? 1 : 0, nmw = (rlen + 31) >> 5;
+    if (packed_words(rlen) > wpad) return; // (a read longer than the context was sized for: the batch is refused before this runs, k_max_read_len)
+    uint32_t *o = out + (uint64_t)r * wpad;
+    const uint8_t *p = rb.bases + a;
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 15);
+    if (m < nmw) {
+        uint32_t has_n, odd;
+        pack_unit32((const U4 *)(p - sh), (uint64_t)sh, rlen, flipped, m, o, has_n, odd);
+        if (odd_flag && odd) atomicOr((uint32_t *)(odd_flag + (r & ~3u)), 2u << (8 * (r & 3)));
+        if (has_n) atomicOr(any_n, 1u);
+    } else if (m == nmw) pack_row_ends(rlen, o);
+}
+
+// One thread per part of a read, tpr = ceil(longest read / 32) + 1 parts per read.  Neighbouring threads fetch neighbouring 16-byte words of the batch (a word
+// two threads need comes out of L1 the second time); what bounds the kernel is its arithmetic, some 550 vector instructions per 32 bases, not the shape of
+// its loads: tiles of reads staged in LDS, per workgroup and per wavefront with the next tile's loads in flight, were measured slower.
 __global__ void __launch_bounds__(256) k_pack_reads(ReadBatch rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t r = (uint32_t)(t / (uint32_t)tpr);
-    const int m = (int)(t % (uint32_t)tpr);
-    if (r >= rb.n_reads) return;
-    ReadRef rd;
-    rd.ascii = rb.bases + rb.off[r]; rd.rlen = (int)(rb.off[r + 1] - rb.off[r]); rd.flipped = (paired && (r & 1)) ? 1 : 0;
-    const int rlen = rd.rlen, nc = (rlen + 15) >> 4, nmw = (rlen + 31) >> 5;
-    if (nc + 1 + nmw + 1 > wpad) return; // (a read longer than the context was sized for: the batch is refused before this runs, k_max_read_len)
-    uint32_t *o = out + (uint64_t)r * wpad;
-    if (m < nmw) {
-        uint32_t c0, f0, c1, f1, o0, o1;
-        pack16(rd, 32 * m, c0, f0, o0);
-        pack16(rd, 32 * m + 16, c1, f1, o1);
-        if (odd_flag && (o0 | o1)) atomicOr((uint32_t *)(odd_flag + (r & ~3u)), 2u << (8 * (r & 3)));
-        o[2 * m] = c0;
-        if (2 * m + 1 < nc) o[2 * m + 1] = c1;
-        o[nc + 1 + m] = (f0 << 16) | f1;
-        const int left = rlen - 32 * m; // bases of this mask word inside the read (bit 31 = the first)
-        if (((f0 << 16) | f1) & (left >= 32 ? ~0u : ~(0xFFFFFFFFu >> left))) atomicOr(any_n, 1u);
-    } else if (m == nmw) {
-        o[nc] = 0u;
-        o[nc + 1 + nmw] = 0xFFFFFFFFu;
-    }
+    if (r < rb.n_reads) pack_read_part(rb, r, (int)(t % (uint32_t)tpr), paired, wpad, out, any_n, odd_flag);
+}
+
+// (launched from two units: a batch's own step — mcx_batch_begin — and a batch on its way in — mcx_stream.hip)
+// tpr: ceil(longest read / 32) + 1, the parts of a read; wpad: words from one row to the next
+void pack_reads(const ReadBatch &rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag, hipStream_t s)
+{
+    k_pack_reads<<<(unsigned)(((uint64_t)rb.n_reads * (uint64_t)tpr + 255) / 256), 256, 0, s>>>(rb, paired, wpad, tpr, out, any_n, odd_flag);
 }
 
 // Reads are handed to lanes as the lanes become free: a read is one to six searches (many more steps each inside a
@@ -198,12 +133,6 @@ __global__ void __launch_bounds__(256) k_pack_reads(ReadBatch rb, int paired, in
 // The reads of a pass form one queue; a wavefront takes a chunk of it with one atomic whenever its lanes run dry, and a
 // lane that has finished a read takes the chunk's next one — every search iteration of the wave finds (nearly) all
 // lanes with work, and the launch ends when the queue does, not block by block.
-// (launched from two units: a batch's own step — mcx_batch_begin — and a batch on its way in — mcx_stream.hip)
-void pack_reads(const ReadBatch &rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag, hipStream_t s)
-{
-    k_pack_reads<<<(unsigned)(((uint64_t)rb.n_reads * (uint64_t)tpr + 255) / 256), 256, 0, s>>>(rb, paired, wpad, tpr, out, any_n, odd_flag);
-}
-
 constexpr int kSeedReadsPerLane = 4; // reads per lane and chunk (small selections: one, their launch is as long as its longest chain of reads)
 
 // FM steps a lane takes before the wave looks at its other lanes again (MCX_SEED_FM_BUDGET for experiments)
@@ -556,9 +485,8 @@ static __device__ __forceinline__ uint32_t listed_pairs(const PairSel &sel, cons
     return n;
 }
 
-// (cls_lo .. cls_hi: with the pairs listed by weight, the launch takes the pairs of these classes only — the heavy classes go first, in
-//  a launch of their own, because every pair that can run over this tier's capacities is among them: the large tier starts on
-//  them while the light pairs, nine in ten, are still being clustered)
+// (cls_lo .. cls_hi: with the pairs listed by weight, the launch takes the pairs of these classes only.  The one launch site takes all
+//  classes in one launch, heaviest first inside it: a launch of their own for the heavy classes, ahead of the light ones, is no longer made)
 __global__ void __launch_bounds__(256) k_cluster(Ctx cx, ReadBatch rb, PairSel sel, RescueList rl, const uint32_t *read_blocks, EarlyList el, const uint32_t *order,
                                                  const uint32_t *order_cnt, int cls_lo, int cls_hi)
 {
@@ -1710,7 +1638,7 @@ static Ctx make_ctx(const mcx_ctx *c, int tier, int paired)
     cx.mapq_tab = c->d_mapq; cx.mapq_rows = c->mapq_rows; cx.dp_summary = 1;
     cx.detail = c->prof_planes ? c->d_detail : nullptr; cx.dlay = c->dlay;
     cx.cig_pool = c->run.cig; cx.cig_pool_n = c->d_batch_flags; cx.cig_pool_cap = c->run.cig_cap;
-    cx.packed = c->packed_now ? c->packed_now : c->d_packed; cx.wpad = c->wpad; cx.read_ext = c->d_read_ext; cx.seed_pool = nullptr;
+    cx.packed = c->packed_now ? c->packed_now : c->d_packed; cx.wpad = c->packed_now ? c->wpad_now : c->wpad; cx.read_ext = c->d_read_ext; cx.seed_pool = nullptr;
     return cx;
 }
 
@@ -1822,7 +1750,7 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
     HIP_TRY(hipMemsetAsync(R.d_cnt, 0, CNT_ALL * sizeof(uint32_t), s)); // (the pass's counters, the class counts of its order, the bucket counts of its DP lists)
     SeedOut so; so.tasks = R.d_tasks; so.n_tasks = R.d_cnt + CNT_TASKS; so.task_cap = R.task_cap;
     so.read_ext = c->d_read_ext; so.read_blocks = c->d_read_blocks;
-    so.packed = c->packed_now ? c->packed_now : c->d_packed; so.wpad = c->wpad; so.queue = R.d_cnt + CNT_QUEUE;
+    so.packed = c->packed_now ? c->packed_now : c->d_packed; so.wpad = c->packed_now ? c->wpad_now : c->wpad; so.queue = R.d_cnt + CNT_QUEUE;
     so.src_state = nullptr; so.src_lay = c->tier[0].lay; so.src_caps = c->tier[0].caps;
     if (hits_from_tier0 && tier == 1 && cx.ix.sa_full && !kn.late_reseed) so.src_state = c->tier[0].state;
     RescueList rl; rl.ids = R.d_rescue; rl.n = R.d_cnt + CNT_RESCUE; rl.cap = R.rescue_cap;
@@ -2146,33 +2074,68 @@ __global__ void k_fill_i32(int32_t *p, int32_t v, uint32_t n)
     if (i < n) p[i] = v;
 }
 
-__global__ void k_reduce_stats(const uint32_t *a, const uint32_t *b, uint32_t n, unsigned long long *out)
+// the sum of a 64-bit count over a workgroup of 256: in wave 0's lane 0 (s: four words of LDS per count in use)
+static __device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long *s)
 {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s[0] + s[1] + s[2] + s[3];
+}
+
+// the seeding statistics of a batch: the per-read words 16 bytes at a time (both arrays are 16-byte aligned), three atomics per workgroup
+constexpr unsigned kReduceStatsBlocks = 1024;
+__global__ void __launch_bounds__(256) k_reduce_stats(const uint32_t *a, const uint32_t *b, uint32_t n, unsigned long long *out)
+{
+    __shared__ unsigned long long s_sum[3][4];
     unsigned long long sa = 0, sb = 0, sh = 0; // extension steps, blocks touched, hits (H of SURVEY.md §8d)
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { sa += a[i] & 0x7FFFFFFFu; sb += b[i] & 0xFFFFFu; sh += b[i] >> 20; }
-    for (int o = 32; o > 0; o >>= 1) { sa += __shfl_down(sa, o, 64); sb += __shfl_down(sb, o, 64); sh += __shfl_down(sh, o, 64); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(out, sa); atomicAdd(out + 1, sb); atomicAdd(out + 2, sh); }
+    const uint32_t n4 = n >> 2, T = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t i = t; i < n4; i += T) {
+        const U4 x = ((const U4 *)a)[i], y = ((const U4 *)b)[i];
+        sa += (unsigned long long)(x.x & 0x7FFFFFFFu) + (x.y & 0x7FFFFFFFu) + (x.z & 0x7FFFFFFFu) + (x.w & 0x7FFFFFFFu);
+        sb += (unsigned long long)(y.x & 0xFFFFFu) + (y.y & 0xFFFFFu) + (y.z & 0xFFFFFu) + (y.w & 0xFFFFFu);
+        sh += (unsigned long long)(y.x >> 20) + (y.y >> 20) + (y.z >> 20) + (y.w >> 20);
+    }
+    for (uint32_t i = 4 * n4 + t; i < n; i += T) { sa += a[i] & 0x7FFFFFFFu; sb += b[i] & 0xFFFFFu; sh += b[i] >> 20; }
+    sa = block_sum_256(sa, s_sum[0]); sb = block_sum_256(sb, s_sum[1]); sh = block_sum_256(sh, s_sum[2]);
+    if (threadIdx.x == 0) { if (sa) atomicAdd(out, sa); if (sb) atomicAdd(out + 1, sb); if (sh) atomicAdd(out + 2, sh); }
 }
 
 // ---- avgDist replay on the device (the host only walks the per-chunk sums) ---------------------
 // per chunk of 100 pairs: number of proper pairs and their summed distance (ReadMapping.cpp:527-531)
-__global__ void k_chunk_sums(const PairOut *po, const uint32_t *off, uint32_t n_pairs, uint32_t chunk, uint32_t *ok_cnt, uint32_t *dist_sum,
-                             uint32_t *len_sum, uint32_t *mapped)
+// A wavefront per chunk: neighbouring lanes read neighbouring records (the eight bytes that hold the distance and the two flags) and the pair's two offsets,
+// all fetched before any is looked at; the lanes' sums are folded with shuffles — integer sums, the same in any order.  One atomic per workgroup: the
+// count of mapped reads has one address, and atomics on one address queue behind one another.
+// (lens: the batch is paired, off[2 p + 2] exists for every pair; a single-end batch has no proper pairs and no lengths to sum)
+static inline unsigned chunk_sums_blocks(uint32_t n_chunks) { return std::max(1u, std::min((n_chunks + 3u) / 4u, 1024u)); }
+__global__ void __launch_bounds__(256) k_chunk_sums(const PairOut *po, const uint32_t *off, uint32_t n_pairs, uint32_t chunk, int lens, uint32_t *ok_cnt, uint32_t *dist_sum,
+                                                    uint32_t *len_sum, uint32_t *mapped)
 {
+    static_assert(sizeof(PairOut) == 32 && offsetof(PairOut, pair_dist) == 16 && offsetof(PairOut, pair_ok) == 20 && offsetof(PairOut, mapped) == 22, "k_chunk_sums reads bytes 16..23 of a record");
+    __shared__ uint32_t s_m[4];
     const uint32_t n_chunks = (n_pairs + chunk - 1) / chunk;
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     uint32_t m = 0;
-    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += gridDim.x * blockDim.x) {
+    for (uint32_t c = wave; c < n_chunks; c += n_waves) {
         uint32_t ok = 0, ds = 0, ls = 0;
         const uint32_t p1 = min(n_pairs, (c + 1) * chunk);
-        for (uint32_t p = c * chunk; p < p1; p++) {
-            const PairOut o = po[p];
-            if (o.pair_ok) { ok++; ds += (uint32_t)o.pair_dist; ls += off[2 * p + 2] - off[2 * p]; } // myReadLengthSum, ReadMapping.cpp:529-530
-            m += (uint32_t)o.mapped;
+        for (uint32_t p = c * chunk + lane; p < p1; p += 128) { // (two records a lane and round: a chunk of 100 is one round)
+            const uint32_t q = p + 64;
+            const bool two = q < p1;
+            const uint2 v = *(const uint2 *)((const uint8_t *)(po + p) + 16); // {pair_dist, pair_ok | mapped << 16}
+            const uint2 v2 = two ? *(const uint2 *)((const uint8_t *)(po + q) + 16) : make_uint2(0u, 0u);
+            const uint32_t l = lens ? off[2 * p + 2] - off[2 * p] : 0u, l2 = lens && two ? off[2 * q + 2] - off[2 * q] : 0u; // myReadLengthSum, ReadMapping.cpp:529-530
+            if ((int16_t)(v.y & 0xFFFFu)) { ok++; ds += v.x; ls += l; }
+            if ((int16_t)(v2.y & 0xFFFFu)) { ok++; ds += v2.x; ls += l2; }
+            m += (uint32_t)(int16_t)(v.y >> 16) + (uint32_t)(int16_t)(v2.y >> 16);
         }
-        ok_cnt[c] = ok; dist_sum[c] = ds; len_sum[c] = ls;
+        for (int o = 32; o > 0; o >>= 1) { ok += __shfl_down(ok, o, 64); ds += __shfl_down(ds, o, 64); ls += __shfl_down(ls, o, 64); }
+        if (lane == 0) { ok_cnt[c] = ok; dist_sum[c] = ds; len_sum[c] = ls; }
     }
     for (int o = 32; o > 0; o >>= 1) m += __shfl_down(m, o, 64);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(mapped, m);
+    if (lane == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0 && (m = s_m[0] + s_m[1] + s_m[2] + s_m[3])) atomicAdd(mapped, m);
 }
 
 // pairs whose chunk estimate lies outside their validity interval -> redo list (avg_replay's test)
@@ -2196,30 +2159,35 @@ __global__ void k_check_est(const PairOut *po, uint32_t n_pairs, uint32_t chunk,
 
 // mcx_avg_walk on the device: the estimate every chunk of the batch is checked against.  The walk is no chain: the estimate before chunk k is
 // the run's when the batch began (k = 0, or no more than 1000 proper pairs so far — the count only grows, so nothing moved it yet) or the
-// rounded mean over everything before k (ReadMapping.cpp:538-539) — prefix sums of the chunks' pairs and distances.  One block: a stretch of
-// chunks per thread, the stretches' sums scanned in LDS.
+// rounded mean over everything before k (ReadMapping.cpp:538-539) — prefix sums of the chunks' pairs and distances.  A chunk per thread, 1024
+// chunks per workgroup: a workgroup sums everything before its stretch itself (neighbouring lanes, neighbouring words: tens of thousands of
+// numbers at the most, out of L2) and scans its own chunks with shuffles, so that no workgroup waits for another and none walks a chain.
 // (first: the batch is the first of its round — of a run on one stream, every batch —: its first chunk takes cur0 as it is; a batch behind
 //  others of the round starts from their totals, tp0 / td0 then hold them too)
+static inline unsigned avg_walk_blocks(uint32_t n_chunks) { return std::max(1u, (n_chunks + 1023u) / 1024u); }
 __global__ void __launch_bounds__(1024) k_avg_walk(const uint32_t *ok, const uint32_t *ds, uint32_t nc, long long cur0, long long tp0, long long td0, int first, int32_t *est_chunk)
 {
-    __shared__ long long s_tp[1024], s_td[1024];
-    const uint32_t per = (nc + 1023u) / 1024u, lo = min(nc, threadIdx.x * per), hi = min(nc, lo + per);
-    long long tp = 0, td = 0;
-    for (uint32_t k = lo; k < hi; k++) { tp += ok[k]; td += ds[k]; }
-    s_tp[threadIdx.x] = tp; s_td[threadIdx.x] = td;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) { // inclusive scan over the stretches' sums
-        const long long a = (int)threadIdx.x >= o ? s_tp[threadIdx.x - o] : 0, b = (int)threadIdx.x >= o ? s_td[threadIdx.x - o] : 0;
-        __syncthreads();
-        s_tp[threadIdx.x] += a; s_td[threadIdx.x] += b;
-        __syncthreads();
+    __shared__ long long s_bp[16], s_bd[16], s_wp[16], s_wd[16]; // per wavefront: its share of what lies before the stretch, its own chunks' sums
+    const uint32_t lo = blockIdx.x * 1024u, k = lo + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    long long bp = 0, bd = 0;
+    for (uint32_t i = threadIdx.x; i < lo; i += 1024u) { bp += ok[i]; bd += ds[i]; }
+    for (int o = 32; o > 0; o >>= 1) { bp += __shfl_down(bp, o, 64); bd += __shfl_down(bd, o, 64); }
+    const long long mp = k < nc ? (long long)ok[k] : 0, md = k < nc ? (long long)ds[k] : 0;
+    long long ip = mp, id = md; // inclusive scan over the wavefront
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long a = __shfl_up(ip, o, 64), b = __shfl_up(id, o, 64);
+        if (lane >= o) { ip += a; id += b; }
     }
-    tp = tp0 + s_tp[threadIdx.x] - tp; td = td0 + s_td[threadIdx.x] - td; // what lies before this thread's stretch
-    for (uint32_t k = lo; k < hi; k++) {
+    if (lane == 0) { s_bp[w] = bp; s_bd[w] = bd; }
+    if (lane == 63) { s_wp[w] = ip; s_wd[w] = id; }
+    __syncthreads();
+    long long tp = tp0 + ip - mp, td = td0 + id - md; // what lies before chunk k
+    for (int j = 0; j < 16; j++) { tp += s_bp[j]; td += s_bd[j]; if (j < w) { tp += s_wp[j]; td += s_wd[j]; } }
+    if (k < nc) {
         uint32_t cur = (uint32_t)cur0;
         if ((k > 0 || !first) && tp > 1000) cur = (uint32_t)(int)(1. * (double)td / (double)tp + .5);
         est_chunk[k] = (int32_t)(cur * 1.5);
-        tp += ok[k]; td += ds[k];
     }
 }
 
@@ -2258,10 +2226,10 @@ static int queue_batch_tail(mcx_ctx *c)
     int32_t *d_est = (int32_t *)(t.d + 8);
     uint32_t *d_ok = t.d + 8 + nc, *d_ds = d_ok + nc, *d_ls = d_ds + nc;
     HIP_TRY(hipMemsetAsync(t.d, 0, 8 * sizeof(uint32_t), s));
-    k_reduce_stats<<<256, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
-    k_chunk_sums<<<(nc + 255) / 256, 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, d_ok, d_ds, d_ls, t.d + 1);
+    k_reduce_stats<<<kReduceStatsBlocks, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
+    k_chunk_sums<<<chunk_sums_blocks(nc), 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, br.paired ? 1 : 0, d_ok, d_ds, d_ls, t.d + 1);
     if (br.paired) {
-        k_avg_walk<<<1, 1024, 0, s>>>(d_ok, d_ds, nc, (long long)t.state0[0], (long long)t.state0[1], (long long)t.state0[2], 1, d_est);
+        k_avg_walk<<<avg_walk_blocks(nc), 1024, 0, s>>>(d_ok, d_ds, nc, (long long)t.state0[0], (long long)t.state0[1], (long long)t.state0[2], 1, d_est);
         k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->t0.d_sel_ids, c->t0.d_est, t.d, c->t0.ov_cap);
     }
     HIP_TRY(hipGetLastError());
@@ -2466,11 +2434,13 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
         if (c->prof_planes) HIP_TRY(hipMemsetAsync(c->d_admit, c->kn.prof_by_column ? 2 : 0, ((size_t)n_reads + 3) & ~(size_t)3, s));
         if (vouched && pre.packed && pre.bases == d_bases && pre.paired == (paired ? 1 : 0) && !c->prof_planes) {
             // packed on its way in, under the batch before it (mcx_stream_submit_packed): the step starts with the search; the any-N word comes along
-            c->packed_now = pre.packed;
+            c->packed_now = pre.packed; c->wpad_now = c->wpad; // (rows made on the way in keep the context's stride)
             HIP_TRY(hipMemcpyAsync(c->d_batch_flags + 3, pre.any_n, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         } else {
-            c->packed_now = c->d_packed;
-            pack_reads(br.rb, paired, c->wpad, tpr, c->d_packed, c->d_batch_flags + 3, c->prof_planes ? c->d_admit : nullptr, s);
+            // rows as long as the batch's longest read needs, not the context's: 80 bytes instead of 112 for 150 bases under max_read_len 256 — every pass of the
+            // batch (tiers, late pairs, replays, the -vcf bookkeeping) strides over them by wpad_now
+            c->packed_now = c->d_packed; c->wpad_now = std::min(c->wpad, (packed_words((int)br.longest) + 3) & ~3);
+            pack_reads(br.rb, paired, c->wpad_now, tpr, c->d_packed, c->d_batch_flags + 3, c->prof_planes ? c->d_admit : nullptr, s);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev_pack[1], s));
@@ -2494,7 +2464,7 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     else { // seeding statistics (E, blocks, H of SURVEY.md 8d) before the per-read arrays are reused for the chunk sums
         unsigned long long *d_sum = (unsigned long long *)c->t0.d_cnt;
         HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-        k_reduce_stats<<<256, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
+        k_reduce_stats<<<kReduceStatsBlocks, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
         HIP_TRY(hipMemcpyAsync(c->t0.h_cnt + CNT_N, d_sum, sizeof br.hs, hipMemcpyDeviceToHost, s)); // (read by batch_close, behind the sums' synchronisation: no round trip of its own)
     }
     br.open = true;
@@ -2523,7 +2493,7 @@ extern "C" int mcx_batch_sums(mcx_ctx *c, uint32_t *n_chunks, const uint32_t **p
     uint32_t *d_ls = d_ds + nc;                               // (2 * n_chunks <= n_reads)
     br.ok.resize(nc); br.ds.resize(2 * (size_t)nc);
     HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
-    k_chunk_sums<<<(nc + 255) / 256, 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, d_ok, d_ds, d_ls, c->t0.d_cnt + CNT_LF);
+    k_chunk_sums<<<chunk_sums_blocks(nc), 256, 0, s>>>(c->d_pout, br.rb.off, br.n_pairs, kReadChunkSize / 2, br.paired ? 1 : 0, d_ok, d_ds, d_ls, c->t0.d_cnt + CNT_LF);
     HIP_TRY(hipMemcpyAsync(br.ok.data(), d_ok, nc * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(br.ds.data(), d_ds, 2 * (size_t)nc * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(c->t0.h_cnt, c->t0.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2606,7 +2576,7 @@ extern "C" int mcx_batch_check(mcx_ctx *c, const int64_t state_before[3], int fi
     hipStream_t s = c->t0.stream;
     int32_t *d_est = (int32_t *)(c->tail.d + 8);
     HIP_TRY(hipMemsetAsync(c->tail.d, 0, 8 * sizeof(uint32_t), s));
-    k_avg_walk<<<1, 1024, 0, s>>>(br.d_ok, br.d_ds, br.n_chunks, (long long)state_before[0], (long long)state_before[1], (long long)state_before[2], first_of_round ? 1 : 0, d_est);
+    k_avg_walk<<<avg_walk_blocks(br.n_chunks), 1024, 0, s>>>(br.d_ok, br.d_ds, br.n_chunks, (long long)state_before[0], (long long)state_before[1], (long long)state_before[2], first_of_round ? 1 : 0, d_est);
     k_check_est<<<2048, 256, 0, s>>>(c->d_pout, br.n_pairs, kReadChunkSize / 2, d_est, c->t0.d_sel_ids, c->t0.d_est, c->tail.d, c->t0.ov_cap);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->tail.h, c->tail.d, 8 * 4, hipMemcpyDeviceToHost, s));
