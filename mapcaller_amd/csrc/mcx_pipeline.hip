@@ -94,38 +94,63 @@ struct SeedOut {
 //  host has looked at the batch's counters anyway, leave out the kernel for such reads when there is none)
 // (odd_flag, with the -vcf bookkeeping: bit 1 of the read's flag byte is set when the read holds a byte that is not an upper-case A C G T)
 //
-// part m of read r straight from HBM: 32 bases (m < mask words of the read), or the row's two constant words (m = that count)
+// part m of read r straight from HBM: 32 bases (m < mask words of the read); the thread of a read's last part writes the row's two constant words as well
+// (kOdd: with the odd flags, for -vcf; off[r] and off[r+1] are read once)
+template <bool kOdd>
 static __device__ __forceinline__ void pack_read_part(const ReadBatch &rb, uint32_t r, int m, int paired, int wpad, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag)
 {
-    const uint32_t a = rb.off[r];
-    const int rlen = (int)(rb.off[r + 1] - a), flipped = (paired && (r & 1)) ? 1 : 0, nmw = (rlen + 31) >> 5;
+    const uint32_t a = rb.off[r], e = rb.off[r + 1];
+    const int rlen = (int)(e - a), flipped = (paired && (r & 1)) ? 1 : 0, nmw = (rlen + 31) >> 5;
     if (packed_words(rlen) > wpad) return; // (a read longer than the context was sized for: the batch is refused before this runs, k_max_read_len)
     uint32_t *o = out + (uint64_t)r * wpad;
+    if (m == (nmw > 0 ? nmw - 1 : 0)) pack_row_ends(rlen, o);
+    if (m >= nmw) return;
     const uint8_t *p = rb.bases + a;
     const uint32_t sh = (uint32_t)((uintptr_t)p & 15);
-    if (m < nmw) {
-        uint32_t has_n, odd;
-        pack_unit32((const U4 *)(p - sh), (uint64_t)sh, rlen, flipped, m, o, has_n, odd);
-        if (odd_flag && odd) atomicOr((uint32_t *)(odd_flag + (r & ~3u)), 2u << (8 * (r & 3)));
-        if (has_n) atomicOr(any_n, 1u);
-    } else if (m == nmw) pack_row_ends(rlen, o);
+    uint32_t has_n, odd;
+    pack_unit32<kOdd>((const U4 *)(p - sh), (uint64_t)sh, rlen, flipped, m, o, has_n, odd);
+    if (kOdd && odd) atomicOr((uint32_t *)(odd_flag + (r & ~3u)), 2u << (8 * (r & 3)));
+    if (has_n) atomicOr(any_n, 1u);
 }
 
-// One thread per part of a read, tpr = ceil(longest read / 32) + 1 parts per read.  Neighbouring threads fetch neighbouring 16-byte words of the batch (a word
-// two threads need comes out of L1 the second time); what bounds the kernel is its arithmetic, some 550 vector instructions per 32 bases, not the shape of
-// its loads: tiles of reads staged in LDS, per workgroup and per wavefront with the next tile's loads in flight, were measured slower.
-__global__ void __launch_bounds__(256) k_pack_reads(ReadBatch rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag)
+// One thread per 32 bases of a read, parts = ceil(longest read / 32) threads per read, in workgroups of parts x (256 / parts) threads: threadIdx.x is the part and
+// threadIdx.y the read, so that no thread divides, and neighbouring threads fetch neighbouring bytes of the batch.  A read of 16 bytes or more is fetched 16 bytes
+// at a time from byte addresses of its own, its last bases included, so every span of a wavefront takes one path, and both spans of a part are asked for before either
+// is packed (mcx_pack.h).  With the look-up pack4 that path is 273 vector instructions as compiled where the kernel had 673: 0.49 ms for 8 M reads of 150 bases where
+// it took 0.72, against 0.30 for its 1.9 GB at the copy rate.  What is left is neither the arithmetic alone (some 0.25 ms of vector issue) nor loads in flight (the
+// same part of two reads per thread, four loads in flight: no faster); tiles of reads staged in LDS were measured slower before.
+// (kFlat: one row of threads numbered through 64 bits — more parts than a workgroup has threads, or more workgroups than a grid has in x)
+template <bool kOdd, bool kFlat>
+__global__ void __launch_bounds__(256) k_pack_reads(ReadBatch rb, int paired, int wpad, int parts, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag)
 {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t r = (uint32_t)(t / (uint32_t)tpr);
-    if (r < rb.n_reads) pack_read_part(rb, r, (int)(t % (uint32_t)tpr), paired, wpad, out, any_n, odd_flag);
+    uint32_t r; int m;
+    if (kFlat) {
+        const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, q = t / (uint32_t)parts;
+        if (q >= rb.n_reads) return;
+        r = (uint32_t)q; m = (int)(t - q * (uint32_t)parts);
+    } else {
+        r = blockIdx.x * blockDim.y + threadIdx.y; m = (int)threadIdx.x;
+        if (r >= rb.n_reads) return;
+    }
+    pack_read_part<kOdd>(rb, r, m, paired, wpad, out, any_n, odd_flag);
 }
 
 // (launched from two units: a batch's own step — mcx_batch_begin — and a batch on its way in — mcx_stream.hip)
-// tpr: ceil(longest read / 32) + 1, the parts of a read; wpad: words from one row to the next
+// tpr: ceil(longest read / 32) + 1 (a thread per 32 bases: tpr - 1 of them per read); wpad: words from one row to the next
 void pack_reads(const ReadBatch &rb, int paired, int wpad, int tpr, uint32_t *out, uint32_t *any_n, uint8_t *odd_flag, hipStream_t s)
 {
-    k_pack_reads<<<(unsigned)(((uint64_t)rb.n_reads * (uint64_t)tpr + 255) / 256), 256, 0, s>>>(rb, paired, wpad, tpr, out, any_n, odd_flag);
+    const int parts = std::max(tpr - 1, 1);
+    const uint32_t rpb = parts <= 256 ? 256u / (uint32_t)parts : 0u; // reads per workgroup
+    const uint64_t n_wg = rpb ? ((uint64_t)rb.n_reads + rpb - 1) / rpb : 0;
+    if (rpb && n_wg <= 0x7FFFFFFFull && rb.n_reads <= 0xFFFFFFFFu - 256u) { // (r = blockIdx.x * rpb + threadIdx.y < n_reads + rpb then fits 32 bits)
+        const dim3 wg((unsigned)parts, rpb);
+        if (odd_flag) k_pack_reads<true, false><<<(unsigned)n_wg, wg, 0, s>>>(rb, paired, wpad, parts, out, any_n, odd_flag);
+        else k_pack_reads<false, false><<<(unsigned)n_wg, wg, 0, s>>>(rb, paired, wpad, parts, out, any_n, odd_flag);
+    } else {
+        const unsigned n_flat = (unsigned)(((uint64_t)rb.n_reads * (uint64_t)parts + 255) / 256);
+        if (odd_flag) k_pack_reads<true, true><<<n_flat, 256, 0, s>>>(rb, paired, wpad, parts, out, any_n, odd_flag);
+        else k_pack_reads<false, true><<<n_flat, 256, 0, s>>>(rb, paired, wpad, parts, out, any_n, odd_flag);
+    }
 }
 
 // Reads are handed to lanes as the lanes become free: a read is one to six searches (many more steps each inside a
