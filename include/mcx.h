@@ -464,6 +464,19 @@ int mcx_bam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *out, uint64_t cap, 
 /* The uncompressed BAM header: "BAM\1", l_text, mcx_sam_header's text, n_ref, and per contig l_name, the name with its NUL, l_ref.  *n_bytes its size,
  * MCX_ERR_CAPACITY (nothing written) when cap is smaller; MCX_ERR_UNSUPPORTED for a contig longer than 2^31 - 1, which BAM cannot say. */
 int mcx_bam_header(const mcx_index *, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
+/* Records in HBM put into coordinate order (mapcaller-mi355x -sort).  A record's key is read from its own bytes — (uint32_t)refID << 32 | (uint32_t)(pos + 1) << 1 |
+ * reverse (flag bit 0x10): samtools sort's comparison, refID -1 last, forward before reverse on one position —, the sort is stable: ties keep their order in d_recs.
+ * d_recs[0 .. n_bytes) are whole records in n_groups groups, group g at d_grp_off[g] .. d_grp_off[g + 1] (mcx_bam_format_dev's d_rec_off: a read's records — none,
+ * one, several); d_out receives the same n_bytes in key order, contiguous, d_keys / d_lens (may be NULL; room for n_bytes / 36 entries at most) each output
+ * record's key and length (4 + block_size), *n_records their number.  The block_size chain is walked inside each group: offsets that do not ascend from 0 to
+ * n_bytes, a block_size below 32 or a record that leaves its group return MCX_ERR_ARG, with nothing written to d_out and nothing read outside d_recs[0 .. n_bytes).
+ * cap < n_bytes: MCX_ERR_CAPACITY; n_groups == 0: 0, nothing written.  Scratch (about 50 bytes a record) stays with the context.  On the context's stream, waited for. */
+int mcx_bam_sort_dev(mcx_ctx *, const uint8_t *d_recs, uint64_t n_bytes, const uint64_t *d_grp_off, uint32_t n_groups, uint8_t *d_out, uint64_t cap,
+                     uint64_t *d_keys, uint32_t *d_lens, uint64_t *n_records);
+/* the last call's device times in ms: index (chain walk, scan, keys), sort, place (lengths gathered and summed), gather */
+int mcx_bam_sort_last_ms(mcx_ctx *, float ms[4]);
+/* mcx_bam_header's bytes for a coordinate-sorted file: the text begins with "@HD\tVN:1.6\tSO:coordinate\n" */
+int mcx_bam_header_sorted(const mcx_index *, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
 
 /* ---- BGZF input inflated on the device -------------------------------------------------------------
  * bgzip's container is a row of independent gzip members of at most 64 KB of text, each of which says how long it is ('BC' extra
@@ -639,6 +652,13 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * straddle the blocks within a part —, EOF block, append_sam over the previous EOF block with no second header, stdout, MCX_BGZF_BLOCK, the resident route, -m, the
  * refusal of shard_count > 1).  gzip -d of the file is the uncompressed BAM stream htslib makes of the SAM lines; no index is written, nothing is sorted.  The lines
  * left out (mcx_bam_format_dev) are counted over the call and the total printed to stderr once, when it is not 0 (MCX_TIMING=1: beside the bgzf line, always).  (route: MCX_ROUTE_BAM.)
+ * bit 8 (MCX_SAM_SORT; mapcaller-mi355x -sort; only with bit 4) makes the file a coordinate-sorted BAM (mcx_bam_sort_dev's order, stable from the first read to the
+ * last: a function of the input alone, whatever the batch, block or chunk size).  Every part's records are sorted before they are compressed and go, as a run, to a
+ * temporary file (sam_path + ".sort.tmp"; for "-": ${TMPDIR:-/tmp}/mcx_sort.<pid>.tmp), of the size of the unsorted file, removed when the call returns, however it
+ * returns; the host keeps 12 bytes a record (key, length) and 24 bytes a block.  Behind the last batch the runs are cut by key into chunks of about 256 MB of
+ * records (MCX_SORT_CHUNK=bytes: a debug switch) — equal keys never in two chunks —, and every chunk's slices are read back, inflated, sorted and compressed on the
+ * device and written behind mcx_bam_header_sorted's header; a pile-up on one key makes a chunk that HBM must hold whole (MCX_ERR_CAPACITY when it does not).
+ * MCX_ERR_UNSUPPORTED before anything is opened: the bit without bit 4, append_sam (a sorted file cannot be appended to), shard_count > 1.  (route: MCX_ROUTE_SORT.)
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -656,7 +676,8 @@ typedef struct mcx_file_opts {
 enum mcx_sam_bits {
     MCX_SAM_DEVICE = 1, /* the SAM text is made on the device */
     MCX_SAM_BGZF = 2,   /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
-    MCX_SAM_BAM = 4     /* ... which hold BAM records instead of SAM text (implies both) */
+    MCX_SAM_BAM = 4,    /* ... which hold BAM records instead of SAM text (implies both) */
+    MCX_SAM_SORT = 8    /* ... in coordinate order (only with MCX_SAM_BAM) */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
@@ -668,9 +689,13 @@ enum mcx_route {
     MCX_ROUTE_ROWS = 4,    /* its batches entered their slots from HBM (mcx_stream_submit_dev): the resident route */
     MCX_ROUTE_SAM = 8,     /* the SAM text was made on the device */
     MCX_ROUTE_BGZF = 16,   /* ... and compressed to BGZF blocks there */
-    MCX_ROUTE_BAM = 32     /* ... as BAM records, not text */
+    MCX_ROUTE_BAM = 32,    /* ... as BAM records, not text */
+    MCX_ROUTE_SORT = 64    /* ... sorted by coordinate and merged on the device */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
+/* What the context's last mcx_map_files* call with MCX_SAM_SORT did: runs, chunks of the merge, slices, slices that start inside a BGZF block, bytes read back from
+ * the temporary file, and how many of those were read twice (the blocks at slice borders).  All 0 after a sorted run that failed. */
+int mcx_files_sort_stats(mcx_ctx *, uint64_t stats[6]);
 
 #ifdef __cplusplus
 }

@@ -74,7 +74,7 @@ SYMBOLS = [
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
-    "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header",
+    "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header", "mcx_bam_sort_dev", "mcx_bam_sort_last_ms", "mcx_bam_header_sorted", "mcx_files_sort_stats",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -264,8 +264,9 @@ READS_FASTQ, READS_FASTA = 0, 1  # mcx_reads_format
 ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 ROUTE_BGZF = 16
 ROUTE_BAM = 32
+ROUTE_SORT = 64
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
-SAM_DEVICE, SAM_BGZF, SAM_BAM = 1, 2, 4  # mcx_sam_bits (mcx_file_opts.device_sam)
+SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam)
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
@@ -417,6 +418,14 @@ def lib() -> C.CDLL:
         f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mcx_bam_header.restype = C.c_int
     L.mcx_bam_header.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_bam_sort_dev.restype = C.c_int
+    L.mcx_bam_sort_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_bam_sort_last_ms.restype = C.c_int
+    L.mcx_bam_sort_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_bam_header_sorted.restype = C.c_int
+    L.mcx_bam_header_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_files_sort_stats.restype = C.c_int
+    L.mcx_files_sort_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_bam_last_ms.restype = C.c_int
     L.mcx_bam_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_inflater_create.restype = C.c_int
@@ -622,7 +631,7 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -635,13 +644,15 @@ class Mapper:
         ``device_inflate`` and ``device_parse`` together, on BGZF FASTQ or FASTA files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
         parse, pack, map and SAM text all in HBM.  ``bgzf_sam`` = -bgzf: the SAM file is written as BGZF, its blocks deflated on the device (implies ``device_sam``; gzip -d of the
         file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``bam`` = -bam: ``sam`` is written as BAM — the records made on the device, framed by the same BGZF path (implies both;
-        unsorted, no index; not sharded).  ``last_route()`` says which stages ran on the device."""
+        unsorted, no index; not sharded).  ``sort`` = -sort, only with ``bam``: the file is coordinate-sorted (samtools sort's order, ties in input order) — every part's records sorted
+        on the device into a run of a temporary file beside ``sam`` (removed again), the runs merged chunk by chunk on the device behind the last batch; ERR_UNSUPPORTED without ``bam``,
+        with ``append_sam`` or sharded; ``sort_stats()`` says what the merge did.  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -711,6 +722,37 @@ class Mapper:
         out = np.zeros(max(1, nb.value), dtype=np.uint8)
         _check(lib().mcx_bam_format(self._h, C.byref(si), out.ctypes.data, nb.value, None, C.byref(nb), C.byref(nd)), "mcx_bam_format")
         return out[:nb.value].tobytes(), int(nd.value)
+
+    def sort_stats(self) -> dict:
+        """mcx_files_sort_stats: what the last map_files(sort=True) did — runs, chunks, slices, slices that start inside a BGZF block, bytes read back from the
+        temporary file, and how many of those twice (the blocks at slice borders)"""
+        v = (C.c_uint64 * 6)()
+        _check(lib().mcx_files_sort_stats(self._h, v), "mcx_files_sort_stats")
+        return dict(zip(("runs", "chunks", "slices", "slices_inside_a_block", "bytes_read", "bytes_read_twice"), (int(x) for x in v)))
+
+    def bam_sort(self, recs, grp_off, keys=None, lens=None, out=None):
+        """mcx_bam_sort_dev over torch tensors on the mapper's device: ``recs`` uint8 — whole BAM records back to back —, ``grp_off`` int64 / uint64 [n_groups + 1], the
+        groups' offsets (mcx_bam_format_dev's rec_off).  Returns (the records in coordinate order — ``out`` or a new uint8 tensor of recs' size —, the number of
+        records); ``keys`` (int64, viewed as uint64) and ``lens`` (int32) receive each output record's key and length when given (room for recs.numel() // 36)."""
+        import torch
+        assert recs.dtype == torch.uint8 and recs.is_contiguous() and grp_off.element_size() == 8 and grp_off.is_contiguous()
+        if out is None:
+            out = torch.empty_like(recs)
+        assert out.dtype == torch.uint8 and out.is_contiguous()
+        assert keys is None or (keys.element_size() == 8 and keys.is_contiguous()), "keys: a 64-bit tensor"
+        assert lens is None or (lens.element_size() == 4 and lens.is_contiguous()), "lens: a 32-bit tensor"
+        torch.cuda.synchronize()
+        n = C.c_uint64()
+        _check(lib().mcx_bam_sort_dev(self._h, recs.data_ptr() if recs.numel() else None, recs.numel(), grp_off.data_ptr(), max(0, grp_off.numel() - 1),
+                                      out.data_ptr() if out.numel() else None, out.numel(), keys.data_ptr() if keys is not None else None,
+                                      lens.data_ptr() if lens is not None else None, C.byref(n)), "mcx_bam_sort_dev")
+        return out, int(n.value)
+
+    def bam_sort_last_ms(self) -> Tuple[float, float, float, float]:
+        """the last mcx_bam_sort_dev's device times in ms: index, sort, place, gather"""
+        ms = (C.c_float * 4)()
+        _check(lib().mcx_bam_sort_last_ms(self._h, ms), "mcx_bam_sort_last_ms")
+        return tuple(float(x) for x in ms)
 
     def bam_last_ms(self) -> Tuple[float, float, float]:
         """the last mcx_bam_format[_dev]'s device times in ms: length kernel, scan, write kernel"""
@@ -1213,14 +1255,16 @@ def sam_header(index: "Index") -> bytes:
     return buf.raw[:nb.value]
 
 
-def bam_header(index: "Index") -> bytes:
-    """The uncompressed BAM header the file front end writes (as BGZF blocks) ahead of the first batch with ``bam``: magic, sam_header's text, the contigs (mcx_bam_header)."""
+def bam_header(index: "Index", sorted: bool = False) -> bytes:
+    """The uncompressed BAM header the file front end writes (as BGZF blocks) ahead of the first batch with ``bam``: magic, sam_header's text, the contigs (mcx_bam_header);
+    ``sorted``: the header of a ``sort`` run, whose text begins with @HD VN:1.6 SO:coordinate (mcx_bam_header_sorted)."""
+    call, what = (lib().mcx_bam_header_sorted, "mcx_bam_header_sorted") if sorted else (lib().mcx_bam_header, "mcx_bam_header")
     nb = C.c_uint64()
-    rc = lib().mcx_bam_header(index._h, None, 0, C.byref(nb))
+    rc = call(index._h, None, 0, C.byref(nb))
     if rc not in (0, ERR_CAPACITY):
-        _check(rc, "mcx_bam_header")
+        _check(rc, what)
     buf = C.create_string_buffer(max(1, nb.value))
-    _check(lib().mcx_bam_header(index._h, buf, nb.value, C.byref(nb)), "mcx_bam_header")
+    _check(call(index._h, buf, nb.value, C.byref(nb)), what)
     return buf.raw[:nb.value]
 
 

@@ -20,6 +20,9 @@
 //   * SAM lines are formatted by a second pool into per-slice buffers and written with positioned
 //     writes, every slice at its final place in the file — by every shard into the one output file:
 //     the shards tell each other their batches' sizes with the rounds' other messages.
+//   * with -sort (only -bam) every part's records are sorted on the device before they are compressed and go as a run to a temporary file, of which the
+//     host keeps keys, lengths and block tables; behind the last batch merge() cuts the runs by key into chunks (mcx_sort_plan.h) and reads back, inflates,
+//     sorts, deflates and writes each of them — every step one bulk operation (mcx_bam_sort.hip).
 // Text semantics follow the reference byte for byte: header trimming (GetData.cpp:3-20), the last
 // byte of a FASTQ sequence line dropped (:48-53), multi-line FASTA for plain files (:56-77), the
 // 1024-byte line buffer, the '@'/'>' check and single-line FASTA of the .gz reader (:101-128), an
@@ -31,6 +34,7 @@
 
 #include "mcx_batch.h"
 #include "mcx_shards.h"
+#include "mcx_sort_plan.h"
 
 using namespace mcx;
 using namespace mcx::files;
@@ -41,7 +45,7 @@ extern "C" void mcx_file_opts_default(mcx_file_opts *o) { memset(o, 0, sizeof *o
 // last call ran on the device
 namespace {
 typedef std::unique_ptr<Batch> BatchPtr;
-struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; };
+struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; uint64_t sort_stats[6] = {0, 0, 0, 0, 0, 0}; };
 Kept *kept_of(mcx_ctx *c)
 {
     void **slot = mcx_ctx_files_slot(c, [](void *p) { delete (Kept *)p; });
@@ -55,6 +59,13 @@ extern "C" int mcx_files_route(mcx_ctx *c, uint32_t route[2])
     if (!c || !route) return mcx_set_error(MCX_ERR_ARG, "mcx_files_route: null argument");
     const Kept *k = kept_of(c);
     route[0] = k->route[0]; route[1] = k->route[1];
+    return 0;
+}
+
+extern "C" int mcx_files_sort_stats(mcx_ctx *c, uint64_t stats[6])
+{
+    if (!c || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_files_sort_stats: null argument");
+    memcpy(stats, kept_of(c)->sort_stats, sizeof kept_of(c)->sort_stats);
     return 0;
 }
 
@@ -174,6 +185,7 @@ struct Run {
     const bool dev_sam;         // the text is made on the device (mcx_sam.hip); without a SAM file there is none to make
     const bool bgzf;            // ... and compressed there: the file is BGZF (mcx_deflate.hip)
     const bool bam;             // ... of BAM records, not text (mcx_bam.hip)
+    const bool sort;            // ... in coordinate order: sorted runs to a temporary file, merged behind the last batch (mcx_bam_sort.hip, mcx_sort_plan.h)
     Timing t;
     Shards sh;
     Pool pool;                  // parse + pack
@@ -201,6 +213,16 @@ struct Run {
     struct DefFree { void operator()(mcx_deflater *d) const { mcx_deflater_free(d); } };
     std::unique_ptr<mcx_deflater, DefFree> deflater; // -bgzf: the header's blocks (the opening thread), then every part's (the mapper's thread)
     mcx_sam_bgzf zs = {nullptr, 65280, 0, 0, 0};
+    // -sort: while the batches are mapped sam_fd is the temporary file of the runs; the file asked for waits in out_fd for the merge
+    int out_fd = -1;
+    bool out_stream = false;
+    std::string tmp_path;
+    mcx_sort_sink sink;                // the keys and lengths of the part just made (the mapper's thread)
+    std::vector<sortplan::Run> runs;   // ... kept per run, with its blocks
+    uint64_t tmp_at = 0;               // where the batch in the mapper's hands will lie in the temporary file
+    double sort_secs[5] = {0, 0, 0, 0, 0}; // the merge: read, copy in, inflate, sort, deflate + copy out
+    double merge_seconds = 0;
+    ~Run() { drop_tmp(); }
     uint8_t bgzf_eof[28];
     std::deque<BatchPtr> waiting; // (the writer's; sharded) formatted, their place in the file not known yet
 
@@ -238,7 +260,7 @@ struct Run {
           shard_count(o.shard_count > 1 ? (uint64_t)o.shard_count : 1), shard_rank(shard_count > 1 ? (uint64_t)o.shard_rank : 0), sharded(shard_count > 1),
           batch_reads(std::max<uint64_t>(kReadChunkSize, mcx_ctx_max_reads(ctx) / kReadChunkSize * kReadChunkSize)), per_file((uint32_t)(two ? batch_reads / 2 : batch_reads)),
           threads(o.host_threads > 0 ? o.host_threads : (int)std::min<unsigned>(64, std::max<unsigned>(1, mcx_usable_cpus() * 3 / 4 / (unsigned)shard_count))),
-          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), pool(threads), fpool(threads),
+          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), sort((o.device_sam & MCX_SAM_SORT) != 0 && bam), pool(threads), fpool(threads),
           n_objects(sharded ? 16 : 12), parsed(2), mapped(2), formatted(2), spare((size_t)n_objects),
           profile(mcx_ctx_has_profile(ctx)), multi(mcx_ctx_multi(ctx))
     {
@@ -270,7 +292,7 @@ struct Run {
         if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
-        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u);
+        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u);
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
@@ -366,7 +388,20 @@ struct Run {
             uint8_t tail[28];
             if (e == 0 && bgzf && opt.append_sam && sam_base >= 28 && pread(sam_fd, tail, 28, (off_t)(sam_base - 28)) == 28 && memcmp(tail, bgzf_eof, 28) == 0) sam_base -= 28;
         }
-        if (e == 0 && !opt.append_sam) {
+        if (e == 0 && sort) { // the runs go to a temporary file, without a header; the file asked for is written by the merge
+            out_fd = sam_fd; out_stream = sam_stream;
+            if (out_stream) { const char *dir = getenv("TMPDIR"); tmp_path = std::string(dir && dir[0] ? dir : "/tmp") + "/mcx_sort." + std::to_string((long long)getpid()) + ".tmp"; }
+            else tmp_path = std::string(sam_path) + ".sort.tmp";
+            sam_fd = ::open(tmp_path.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0600);
+            sam_stream = false; sam_base = 0;
+            zs.sort = &sink;
+            if (sam_fd < 0) {
+                e = mcx_set_error(MCX_ERR_IO, "-sort: cannot write the temporary file " + tmp_path);
+                tmp_path.clear();
+                sam_fd = out_fd; sam_stream = out_stream; out_fd = -1;
+            }
+        }
+        if (e == 0 && !opt.append_sam && !sort) {
             std::string hdr;
             if (bam) { // -bam: the binary header, text and contigs
                 uint64_t n = 0;
@@ -834,7 +869,7 @@ struct Run {
             }
         }
         flush_waiting(true); // the places of the last rounds' text arrive with the closing exchanges
-        if (bgzf && sam_fd >= 0 && write_rc == 0 && !write_all(sam_fd, (const char *)bgzf_eof, 28, next_place, sam_stream)) write_rc = MCX_ERR_IO; // (-bgzf is never sharded)
+        if (bgzf && !sort && sam_fd >= 0 && write_rc == 0 && !write_all(sam_fd, (const char *)bgzf_eof, 28, next_place, sam_stream)) write_rc = MCX_ERR_IO; // (-bgzf is never sharded; -sort: the merge ends the file)
     }
     void flush_waiting(bool block) // batches whose place has arrived go out, oldest first
     {
@@ -987,7 +1022,11 @@ struct Run {
                       mcx_sam_part(c, d_bases, d_off, cnt, second ? 0 : 1, p->sam_names + (second ? p->sam_part_names[0] : 0), p->sam_name_off + (second ? npr + 1 : 0),
                                    p->fastq ? p->sam_qual + (second ? p->sam_part_qual[0] : 0) : nullptr, p->sam_part_qual[second ? 1 : 0], d_aln, d_cig,
                                    &p->dev_text, &p->dev_text_cap, p->dev_bytes, &got, bgzf ? &zs : nullptr);
-        if (e) rc = e; else p->dev_bytes += got;
+        if (e) rc = e;
+        else {
+            if (sort && !note_run(p->dev_text + p->dev_bytes, got, tmp_at + p->dev_bytes)) rc = mcx_set_error(MCX_ERR_DEVICE, "-sort: the part's blocks do not walk as BGZF");
+            p->dev_bytes += got;
+        }
         t.m_sam += secs(tq, now());
     }
     // one shard: the batch's parts are mapped as they are
@@ -1069,6 +1108,7 @@ struct Run {
             if (p->n) t.map += secs(t1, now());
             if (t.w_first_mapped == 0) t.w_first_mapped = t.wall();
             if (rc) { p->n = 0; abort.store(true); places.fail(); }
+            if (sort) tmp_at += p->n ? p->dev_bytes : 0; // (the writer puts the batches one behind the other, those that count)
             if (parts_out == 0) { // nothing on its way out: the batch goes on as it is, behind the ones that are
                 collect_until(0);
                 mapped.push(std::move(cur));
@@ -1084,6 +1124,137 @@ struct Run {
         }
         if (rc) places.fail();
         t.w_mapped = t.wall();
+    }
+
+
+    // ---- -sort: the runs, and the merge behind the last batch ---------------------------------------------------------------
+    // a part has come back as `bytes` of BGZF blocks that will lie at byte `at` of the temporary file: its keys and lengths (the sink) and its block table
+    bool note_run(const uint8_t *blocks, uint64_t bytes, uint64_t at)
+    {
+        if (sink.keys.empty()) return true;
+        runs.emplace_back();
+        sortplan::Run &r = runs.back();
+        r.keys.swap(sink.keys); r.lens.swap(sink.lens);
+        uint64_t u = 0;
+        for (uint64_t o = 0; o < bytes;) { // BSIZE at byte 16 of a block of ours, ISIZE in its last four
+            if (bytes - o < 26 || blocks[o] != 0x1f || blocks[o + 1] != 0x8b || blocks[o + 12] != 'B' || blocks[o + 13] != 'C') return false;
+            const uint32_t size = ((uint32_t)blocks[o + 16] | (uint32_t)blocks[o + 17] << 8) + 1;
+            if (size < 26 || size > bytes - o) return false;
+            const uint8_t *q = blocks + o + size - 4;
+            const uint32_t isize = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+            sortplan::Block b; b.c_off = at + o; b.c_size = size; b.u_size = isize; b.u_off = u;
+            r.blocks.push_back(b);
+            u += isize; o += size;
+        }
+        r.finish();
+        return r.bytes == u;
+    }
+    void drop_tmp() // the temporary file goes, however the run ends; the file asked for is sam_fd again
+    {
+        if (tmp_path.empty()) return;
+        if (sam_fd >= 0) close(sam_fd);
+        unlink(tmp_path.c_str());
+        tmp_path.clear();
+        sam_fd = out_fd; sam_stream = out_stream; out_fd = -1;
+    }
+    // every step of a chunk is one bulk operation: pread of the covering blocks, one inflate over all of them, the sort core, the deflater, one write
+    int merge()
+    {
+        const Tick t_begin = now();
+        uint64_t chunk_bytes = 256ull << 20;
+        if (const char *env = getenv("MCX_SORT_CHUNK")) { const long long v = atoll(env); if (v >= 1) chunk_bytes = (uint64_t)v; } // (debug override)
+        sortplan::Plan plan;
+        sortplan::make_plan(runs, chunk_bytes, &plan);
+        for (sortplan::Run &r : runs) std::vector<uint64_t>().swap(r.keys); // (the plan is made: 8 of the 12 bytes a record go)
+        uint64_t *ss = kept->sort_stats;
+        ss[0] = runs.size(); ss[1] = plan.chunks.size();
+        const int tmp_fd = sam_fd;
+        const int fd = out_fd; const bool stream = out_stream;
+        uint64_t place = 0;
+        int e = 0;
+        // the header, blocks of its own
+        {
+            uint64_t n = 0;
+            (void)mcx_bam_header_sorted(idx, nullptr, 0, &n);
+            std::string hdr((size_t)n, '\0');
+            if (n == 0 || mcx_bam_header_sorted(idx, (uint8_t *)&hdr[0], n, &n) != 0) return mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
+            std::string blocks((size_t)mcx_bgzf_bound(hdr.size(), zs.block), '\0');
+            uint64_t made = 0;
+            if ((e = mcx_bgzf_deflate(zs.deflater, (const uint8_t *)hdr.data(), hdr.size(), (uint8_t *)&blocks[0], blocks.size(), &made))) return e;
+            if (!write_all(fd, blocks.data(), (size_t)made, place, stream)) return mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
+            place += made;
+        }
+        mcx_inflater *inf = nullptr;
+        if (mcx_inflater_create_dev(idx->device, 0, 1u << 16, &inf) != 0) return mcx_set_error(MCX_ERR_DEVICE, std::string("-sort: ") + mcx_last_error());
+        uint8_t *h_src = nullptr, *h_out = nullptr;
+        uint64_t h_src_cap = 0, h_out_cap = 0;
+        std::vector<mcx_deflate_member> members;
+        std::vector<uint32_t> lens;
+        std::vector<uint64_t> first, base;
+        for (size_t k = 0; k < plan.chunks.size() && e == 0; k++) {
+            const sortplan::Chunk &ch = plan.chunks[k];
+            if (ch.records == 0) continue;
+            uint64_t src_bytes = 0;
+            for (const sortplan::Slice &sl : ch.slices) { const sortplan::Run &r = runs[sl.run]; src_bytes += r.blocks[sl.k1 - 1].c_off + r.blocks[sl.k1 - 1].c_size - r.blocks[sl.k0].c_off; }
+            if (src_bytes + 8 > h_src_cap) {
+                mcx_pinned_free(h_src);
+                h_src_cap = src_bytes + src_bytes / 8 + 4096;
+                if (!(h_src = (uint8_t *)mcx_pinned_alloc(h_src_cap))) { h_src_cap = 0; e = mcx_set_error(MCX_ERR_DEVICE, "-sort: cannot allocate pinned host memory for a chunk's blocks"); break; }
+            }
+            members.clear(); lens.clear(); first.clear(); base.clear();
+            uint64_t so = 0, to = 0;
+            const Tick t0 = now();
+            for (const sortplan::Slice &sl : ch.slices) {
+                const sortplan::Run &r = runs[sl.run];
+                const uint64_t c0 = r.blocks[sl.k0].c_off, cn = r.blocks[sl.k1 - 1].c_off + r.blocks[sl.k1 - 1].c_size - c0;
+                for (uint64_t done = 0; done < cn && e == 0;) {
+                    const ssize_t got = pread(tmp_fd, h_src + so + done, (size_t)(cn - done), (off_t)(c0 + done));
+                    if (got <= 0) e = mcx_set_error(MCX_ERR_IO, "-sort: cannot read the temporary file " + tmp_path); else done += (uint64_t)got;
+                }
+                if (e) break;
+                first.push_back(lens.size());
+                base.push_back(to + (sl.b0 - r.blocks[sl.k0].u_off));
+                lens.insert(lens.end(), r.lens.begin() + (ptrdiff_t)sl.r0, r.lens.begin() + (ptrdiff_t)sl.r1);
+                for (uint64_t j = sl.k0; j < sl.k1; j++) {
+                    const sortplan::Block &b = r.blocks[j];
+                    if (b.u_size) {
+                        const uint8_t *q = h_src + so + (b.c_off - c0) + b.c_size - 8;
+                        mcx_deflate_member m; memset(&m, 0, sizeof m);
+                        m.src_off = so + (b.c_off - c0) + 18; m.src_len = b.c_size - 26; m.dst_off = to; m.isize = b.u_size;
+                        m.crc32 = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+                        members.push_back(m);
+                    }
+                    to += b.u_size;
+                }
+                ss[2]++; ss[4] += cn;
+                if (sl.b0 != r.blocks[sl.k0].u_off) { ss[3]++; ss[5] += r.blocks[sl.k0].c_size; } // (the slice before it in the run has read this block too)
+                so += cn;
+            }
+            if (e) break;
+            sort_secs[0] += secs(t0, now());
+            memset(h_src + so, 0, 8);
+            uint64_t made = 0;
+            e = mcx_bam_sort_chunk(c, inf, zs.deflater, zs.block, h_src, so + 8, members.data(), (uint32_t)members.size(), to, lens.data(), lens.size(), first.data(), base.data(), (uint32_t)first.size(),
+                                   ch.bytes, &h_out, &h_out_cap, &made, sort_secs + 1);
+            if (e) break;
+            const Tick t1 = now();
+            if (!write_all(fd, (const char *)h_out, (size_t)made, place, stream)) e = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
+            t.write += secs(t1, now());
+            place += made;
+        }
+        if (e == 0 && !write_all(fd, (const char *)bgzf_eof, 28, place, stream)) e = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
+        mcx_pinned_free(h_src); mcx_pinned_free(h_out);
+        mcx_inflater_free(inf);
+        merge_seconds = secs(t_begin, now());
+        return e;
+    }
+    // behind the threads: the merge when all went well, and the end of the temporary file whatever happened
+    void finish_sort()
+    {
+        if (!sort) return;
+        memset(kept->sort_stats, 0, sizeof kept->sort_stats);
+        if (rc == 0 && write_rc.load() == 0 && out_fd >= 0) rc = merge();
+        drop_tmp();
     }
 
     // -bam: the lines htslib's parser would have rejected made no record; said once a call, when there are any
@@ -1102,6 +1273,9 @@ struct Run {
         if (bgzf) fprintf(stderr, "[mcx_map_files] bgzf: %llu bytes of text -> %llu bytes of blocks (%u bytes of text a block), the deflater took %.3f s of them\n",
                           (unsigned long long)zs.text_bytes, (unsigned long long)zs.out_bytes, zs.block, zs.seconds);
         if (bam) fprintf(stderr, "[mcx_map_files] bam: the text above is BAM records; %llu lines made none\n", (unsigned long long)zs.dropped);
+        if (sort) fprintf(stderr, "[mcx_map_files] sort: %llu runs (%.3f s of the mapper's time), %llu chunks of %llu slices (%llu start inside a block); the merge %.3f s: read %.3f, copy in %.3f, inflate %.3f, sort %.3f, deflate + copy out %.3f; %llu bytes read back, %llu of them twice\n",
+                          (unsigned long long)kept->sort_stats[0], sink.run_seconds, (unsigned long long)kept->sort_stats[1], (unsigned long long)kept->sort_stats[2], (unsigned long long)kept->sort_stats[3], merge_seconds,
+                          sort_secs[0], sort_secs[1], sort_secs[2], sort_secs[3], sort_secs[4], (unsigned long long)kept->sort_stats[4], (unsigned long long)kept->sort_stats[5]);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");
         fprintf(stderr, "[mcx_map_files] waits: reader for room behind it %.3f | mapper for a parsed batch %.3f, for copies out %.3f | formatter for the writer %.3f || mapper's calls: submit %.3f, next %.3f, map_batch_dev %.3f, mapped %.3f\n", t.p_push, t.m_take, t.m_collect, t.f_push, t.m_submit, t.m_in, t.m_dev, t.m_out);
@@ -1120,6 +1294,12 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     if (opt.device_sam & MCX_SAM_BAM) opt.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF; // (BAM records are made on the device and framed as BGZF)
     if (opt.shard_count > 1 && (!opt.exchange || !opt.exchange->allgather || opt.exchange->size != opt.shard_count || opt.exchange->rank != opt.shard_rank))
         return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_ex: a sharded run needs mcx_file_opts.exchange with the shard's rank and count");
+    if ((opt.device_sam & MCX_SAM_SORT) && !(opt.device_sam & MCX_SAM_BAM))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -sort puts BAM records into coordinate order and needs -bam (MCX_SAM_SORT without MCX_SAM_BAM); SAM text is not sorted");
+    if ((opt.device_sam & MCX_SAM_SORT) && opt.append_sam)
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sorted file cannot be appended to (-sort with append_sam): map the libraries in one run, or merge the sorted files");
+    if ((opt.device_sam & MCX_SAM_SORT) && opt.shard_count > 1)
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write a sorted BAM file (-sort with -gpus N / -devices): map on one GPU");
     if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_BGZF))
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF or as BAM (-bgzf / -bam with -gpus N / -devices): map on one GPU, or without them");
     Run run(c, fq1, fq2, opt, sam_path, stats);
@@ -1133,6 +1313,7 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
     formatter.join();
     writer.join();
     reader.join();
+    run.finish_sort();
     run.keep_objects();
     run.report_dropped();
     run.report_timing();

@@ -6,6 +6,7 @@
 #include "mcx_build.h"
 #include "../../include/mcx.h"
 #include <atomic>
+#include <vector>
 
 struct mcx_index {
     mcx::IndexView view;
@@ -40,7 +41,10 @@ void **mcx_ctx_sam_slot(mcx_ctx *, void (*drop)(void *));
 void *mcx_ctx_stream(mcx_ctx *);
 // -bgzf: the run's deflater with its block size, and what it has done so far (text in, blocks out, seconds of the calling thread); bam (-bam): what goes in is
 // not a part's SAM text but its BAM records (mcx_bam.hip), and dropped counts the lines that made none
-struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; int bam; uint64_t dropped; };
+// sort (-sort; null: none): the part's records are put into coordinate order before they are compressed (mcx_bam_sort.hip), and the sorted keys and lengths of
+// the part — a run of the merge — arrive in the sink
+struct mcx_sort_sink { std::vector<uint64_t> keys; std::vector<uint32_t> lens; double run_seconds = 0; };
+struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; int bam; uint64_t dropped; mcx_sort_sink *sort; };
 // -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory; bgzf (null: none): the text is
 // compressed in HBM first and its BGZF blocks arrive instead, *n_bytes their size
 int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const uint8_t *names, const uint32_t *name_off,
@@ -48,6 +52,12 @@ int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint3
 // -bam (mcx_bam.hip): mcx_bam_format_dev for sam_part's input — the records of a part into d_out[0 .. cap), *n_bytes their exact size (MCX_ERR_CAPACITY, nothing
 // written, when cap is smaller), *n_dropped the lines that made none; the context's device is current
 int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t cap, uint64_t *n_bytes, uint64_t *n_dropped);
+// -sort (mcx_bam_sort.hip).  part: what mcx_bam_part_dev just made (n_reads groups, n_bytes) in key order in a buffer of the state's own, *d_sorted; keys and
+// lengths into the sink.  chunk: one chunk of the merge, from the blocks read back from the temporary file to the blocks of the sorted file (see there).
+int mcx_bam_sort_part(mcx_ctx *, uint32_t n_reads, uint64_t n_bytes, mcx_sort_sink *sink, const uint8_t **d_sorted);
+int mcx_bam_sort_chunk(mcx_ctx *, mcx_inflater *, mcx_deflater *, uint32_t block, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n_members,
+                       uint64_t text_bytes, const uint32_t *lens, uint64_t n_records, const uint64_t *slice_first, const uint64_t *slice_base, uint32_t n_slices, uint64_t rec_bytes,
+                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4]);
 // -gpu_inflate (mcx_inflate.hip): the host form of mcx_inflate in two halves, so that the reader stages a stretch's bytes while the stretch before is on
 // the device — begin packs the members' bytes (src_off into src) into page-locked staging and queues copy in, kernel and copy out; end waits for the oldest
 // begin and hands the text to dst + each member's dst_off (0, or MCX_ERR_IO when a member failed).  At most two begins outstanding; caps: what one holds.

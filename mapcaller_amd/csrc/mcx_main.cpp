@@ -56,6 +56,9 @@ static void usage(const char *prog)
             "                       implies -gpu_sam; gzip -d gives the bytes of the plain file; not with -gpus N / -devices\n"
             "         -bam          BAM output filename ('-' = stdout) instead of -sam (the later of the two counts): the records are made and their BGZF blocks\n"
             "                       deflated on the GPU; unsorted, no index; not with -gpus N / -devices\n"
+            "         -sort         with -bam: a coordinate-sorted BAM file (samtools sort's order, ties in input order), sorted and merged on the GPU; needs temporary\n"
+            "                       disk of the file's size beside it (out.bam.sort.tmp; for stdout in $TMPDIR) and 12 bytes of host memory a record;\n"
+            "                       one library (one -f / -f2 pair); not with -gpus N / -devices; no index is written (samtools index takes the file)\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -106,6 +109,7 @@ int main(int argc, char **argv)
     bool want_vcf = true; // bVCFoutput, main.cpp:171
     bool multi = false;   // -m: a SAM line for every alignment with the best score
     bool bam = false;     // -bam: the output file holds BAM records
+    bool want_sort = false; // -sort: ... in coordinate order
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -162,6 +166,7 @@ int main(int argc, char **argv)
         else if (p == "-m") multi = true; // bUnique = false, main.cpp:308
         else if (p == "-gpu_sam") fo.device_sam |= MCX_SAM_DEVICE;
         else if (p == "-bgzf") fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF;
+        else if (p == "-sort") want_sort = true;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
@@ -171,6 +176,10 @@ int main(int argc, char **argv)
     if (devices.empty()) for (int r = 0; r < n_gpus; r++) devices.push_back(n_gpus == 1 ? gpu : r);
     n_gpus = (int)devices.size();
     if (bam) fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF | MCX_SAM_BAM;
+    if (want_sort && !bam) { fprintf(stderr, "Error! -sort puts BAM records into coordinate order: it needs -bam (SAM text is not sorted)\n"); return 1; }
+    if (want_sort && f1.size() > 1) { fprintf(stderr, "Error! -sort writes one sorted file from one library: a sorted file cannot be appended to (give one -f / -f2 pair)\n"); return 1; }
+    if (want_sort && n_gpus > 1) { fprintf(stderr, "Error! -sort sorts and merges on one GPU: it cannot be combined with -gpus N / -devices\n"); return 1; }
+    if (want_sort) fo.device_sam |= MCX_SAM_SORT;
     if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the

@@ -275,14 +275,20 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
     }
     if (rc) return rc;
     if (bam) bgzf->dropped += dropped;
+    // -sort: the part's records in coordinate order — a run of the merge — in a second buffer
+    const uint8_t *d_plain = st->d_text;
+    if (bam && bgzf->sort) {
+        bgzf->sort->keys.clear(); bgzf->sort->lens.clear();
+        if (total && (rc = mcx_bam_sort_part(c, n_reads, total, bgzf->sort, &d_plain))) return rc;
+    }
     // -bgzf: the part's text is compressed where it lies (a fresh block at its start), and only the blocks leave the device
-    const uint8_t *d_from = st->d_text;
+    const uint8_t *d_from = d_plain;
     if (bgzf && total) {
         const auto t0 = std::chrono::steady_clock::now();
         const uint64_t bound = mcx_bgzf_bound(total, bgzf->block);
         if ((rc = sam_grow(&st->d_bgzf, &st->cap_bgzf, bound, "the batch's BGZF blocks"))) return rc;
         uint64_t made = 0;
-        if ((rc = mcx_bgzf_deflate_dev(bgzf->deflater, st->d_text, total, st->d_bgzf, st->cap_bgzf, &made))) return rc;
+        if ((rc = mcx_bgzf_deflate_dev(bgzf->deflater, d_plain, total, st->d_bgzf, st->cap_bgzf, &made))) return rc;
         bgzf->text_bytes += total; bgzf->out_bytes += made;
         bgzf->seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         d_from = st->d_bgzf; total = made;

@@ -10,6 +10,25 @@
 
 namespace mcx {
 
+// -sort (mcx_bam_sort.hip): the arrays of a call's records — source and destination offsets, keys, lengths and indexes, as found and in sorted order —, the
+// groups' counts, hipcub's scratch, the sorted records, and for the merge's chunks the blocks read back, their members and their text
+struct SortBufs {
+    uint64_t *d_src_off = nullptr, *d_dst_off = nullptr, *d_key = nullptr, *d_key_s = nullptr; uint32_t *d_len = nullptr, *d_len_s = nullptr, *d_idx = nullptr, *d_idx_s = nullptr; uint64_t cap = 0;
+    uint32_t *d_count = nullptr, *d_first = nullptr; uint64_t cap_groups = 0;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;
+    uint32_t *d_error = nullptr;
+    uint8_t *d_sorted = nullptr, *d_src = nullptr, *d_inflated = nullptr; uint64_t cap_sorted = 0, cap_src = 0, cap_inflated = 0;
+    mcx_deflate_member *d_members = nullptr; uint32_t *d_status = nullptr; uint64_t *d_slices = nullptr; uint64_t cap_members = 0, cap_status = 0, cap_slices = 0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float ms[4] = {0, 0, 0, 0}; // the last call's index, sort, place, gather
+    ~SortBufs()
+    {
+        void *p[] = {d_src_off, d_dst_off, d_key, d_key_s, d_len, d_len_s, d_idx, d_idx_s, d_count, d_first, d_tmp, d_error, d_sorted, d_src, d_inflated, d_members, d_status, d_slices};
+        for (void *q : p) if (q) (void)hipFree(q);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 // the contigs' names (once), the lengths and offsets of a batch, and — for the file front end — the names, qualities and text (or records) of a batch part in HBM
 struct SamState {
     char *d_cn_text = nullptr; uint32_t *d_cn_off = nullptr;
@@ -21,6 +40,7 @@ struct SamState {
     float ms[3] = {0, 0, 0}; // the last call's length kernel, scan, write kernel
     uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
     uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
+    SortBufs sort;
     ~SamState()
     {
         void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf};
