@@ -179,7 +179,7 @@ typedef struct mcx_stats {
     int64_t replayed_pairs; /* pairs re-run because the avgDist trajectory moved past their validity interval */
     int64_t halved_selections; /* times a selection of pairs was mapped in two halves because a work list ran over */
     int64_t simple_pairs;   /* pairs (reads, single-end) that went from their seeds to their records on the straight-line path (k_simple) */
-    double ms_encode /* k_pack_reads */, ms_seed, ms_sa, ms_cluster /* k_cluster alone */, ms_rescue, ms_build, ms_dp, ms_finish, ms_total;
+    double ms_encode /* k_pack_reads */, ms_seed, ms_sa, ms_cluster /* the pass's stream from the order's end to the rescue fork: k_cluster (with the heavy pairs aside: the light pairs' launch and whatever wait for the heavy side is left) */, ms_rescue, ms_build, ms_dp, ms_finish, ms_total;
     double ms_simple;       /* the straight-line path: k_simple (collect), k_simple_dp, k_simple (replay) */
     double ms_order;        /* k_order_count + k_order_place */
 } mcx_stats;
@@ -475,6 +475,10 @@ int mcx_bam_sort_dev(mcx_ctx *, const uint8_t *d_recs, uint64_t n_bytes, const u
                      uint64_t *d_keys, uint32_t *d_lens, uint64_t *n_records);
 /* the last call's device times in ms: index (chain walk, scan, keys), sort, place (lengths gathered and summed), gather */
 int mcx_bam_sort_last_ms(mcx_ctx *, float ms[4]);
+/* (tests, measurements) the last tier-0 pass of the context: out[0..5] the pairs the order listed per weight class, heaviest first (all zero: the pass
+   made no order); out[6] the pairs of the heavy classes' clustering launch, out[7] of the light classes'; out[8] 1 when the heavy pairs were listed and
+   clustered on a side stream beside the straight-line path, 0 when one launch in line took all classes; out[9] the pairs that launch listed for the large tier */
+int mcx_pass_last_shape(mcx_ctx *, uint32_t out[10]);
 /* mcx_bam_header's bytes for a coordinate-sorted file: the text begins with "@HD\tVN:1.6\tSO:coordinate\n" */
 int mcx_bam_header_sorted(const mcx_index *, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
 

@@ -75,6 +75,7 @@ SYMBOLS = [
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
     "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header", "mcx_bam_sort_dev", "mcx_bam_sort_last_ms", "mcx_bam_header_sorted", "mcx_files_sort_stats",
+    "mcx_pass_last_shape",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -422,6 +423,8 @@ def lib() -> C.CDLL:
     L.mcx_bam_sort_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_bam_sort_last_ms.restype = C.c_int
     L.mcx_bam_sort_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_pass_last_shape.restype = C.c_int
+    L.mcx_pass_last_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.mcx_bam_header_sorted.restype = C.c_int
     L.mcx_bam_header_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mcx_files_sort_stats.restype = C.c_int
@@ -753,6 +756,13 @@ class Mapper:
         ms = (C.c_float * 4)()
         _check(lib().mcx_bam_sort_last_ms(self._h, ms), "mcx_bam_sort_last_ms")
         return tuple(float(x) for x in ms)
+
+    def pass_last_shape(self) -> dict:
+        """mcx_pass_last_shape: the last tier-0 pass — the pairs the order listed per weight class (heaviest first; all zero without the order), the pairs of
+        the heavy and of the light clustering launch, whether the heavy ones went aside (a side stream beside the straight-line path), the early list's length"""
+        v = (C.c_uint32 * 10)()
+        _check(lib().mcx_pass_last_shape(self._h, v), "mcx_pass_last_shape")
+        return {"classes": [int(x) for x in v[:6]], "heavy": int(v[6]), "light": int(v[7]), "aside": int(v[8]), "early": int(v[9])}
 
     def bam_last_ms(self) -> Tuple[float, float, float]:
         """the last mcx_bam_format[_dev]'s device times in ms: length kernel, scan, write kernel"""

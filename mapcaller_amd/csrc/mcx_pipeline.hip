@@ -304,8 +304,13 @@ struct EarlyList { uint32_t *ids; int32_t *est; uint32_t *n; uint32_t cap; uint3
 // (dozens of hits to sort and cluster, a dozen candidates to build and score) sixty-three ordinary pairs wait.  So the pairs
 // of a pass are dealt to the lanes by weight — total seed hits, known once k_seed is done — heaviest class first: like sits
 // with like, and the long wavefronts start early.  Two small passes (count, place) make the permutation `order`.
-constexpr int kWorkClasses = 6;
-static __device__ __forceinline__ int work_class(uint32_t hits) { return hits > 64 ? 0 : hits > 32 ? 1 : hits > 16 ? 2 : hits > 8 ? 3 : hits > 4 ? 4 : 5; }
+// Classes 0 .. kHeavyClasses - 1 are the heavy pairs: more than kLightHits hits (mcx_types.h — the bound light_pairs_fit() holds against the
+// tier's capacities), so more than kSimpleHits in one read at least: k_simple never takes such a pair, and its class, its place in the order and its
+// clustering depend on k_seed alone.  run_pairs lists and clusters them on a side stream beside the straight-line path (passes H and L below).
+constexpr int kWorkClasses = 6, kHeavyClasses = 4;
+constexpr uint32_t kAsideGatePairs = 1u << 16; // passes of at least this many pairs tell the next pass whether the aside path pays (mcx_ctx::aside_pays)
+static __device__ __forceinline__ int work_class(uint32_t hits) { return hits > 64 ? 0 : hits > 32 ? 1 : hits > 16 ? 2 : hits > (uint32_t)kLightHits ? 3 : hits > 4 ? 4 : 5; }
+static_assert(kLightHits >= 2 * kSimpleHits, "a heavy pair must hold a read with more than kSimpleHits hits: k_simple leaves its hits alone while k_cluster sorts them");
 
 static __device__ __forceinline__ int pair_work_class(const PairSel &sel, uint32_t local, const uint32_t *read_blocks, int nr, const uint8_t *done = nullptr)
 {
@@ -316,7 +321,10 @@ static __device__ __forceinline__ int pair_work_class(const PairSel &sel, uint32
 
 constexpr int kOrderTile = 16; // pairs per thread of the two passes: a block of 256 settles 4096 pairs with one global atomic per class
 
-__global__ void __launch_bounds__(256) k_order_count(PairSel sel, const uint32_t *read_blocks, int nr, uint32_t *counts, const uint8_t *done)
+// (cls_lo .. cls_hi: the classes this pass lists; a pair of another class is left out like one that k_simple took.  The order is made in one pass over
+//  all classes, or in two into the one array and the one set of counts: pass H, the heavy classes, without `done` — behind k_seed, beside k_simple —
+//  and pass L, the light ones, behind both: its stretches begin where H's final counts end.)
+__global__ void __launch_bounds__(256) k_order_count(PairSel sel, const uint32_t *read_blocks, int nr, uint32_t *counts, const uint8_t *done, int cls_lo, int cls_hi)
 {
     __shared__ uint32_t n_cls[kWorkClasses];
     if (threadIdx.x < kWorkClasses) n_cls[threadIdx.x] = 0u;
@@ -324,7 +332,8 @@ __global__ void __launch_bounds__(256) k_order_count(PairSel sel, const uint32_t
     const uint32_t base = blockIdx.x * (256u * kOrderTile);
     for (int t = 0; t < kOrderTile; t++) {
         const uint32_t local = base + t * 256u + threadIdx.x;
-        const int cls = local < sel.n ? pair_work_class(sel, local, read_blocks, nr, done) : -1;
+        int cls = local < sel.n ? pair_work_class(sel, local, read_blocks, nr, done) : -1;
+        if (cls < cls_lo || cls > cls_hi) cls = -1;
 #pragma unroll
         for (int k = 0; k < kWorkClasses; k++) {
             const uint64_t m = __ballot(cls == k);
@@ -336,7 +345,7 @@ __global__ void __launch_bounds__(256) k_order_count(PairSel sel, const uint32_t
 }
 
 // counts[k * kCntPad]: pairs of class k; counts[(8 + k) * kCntPad]: how many of them were placed so far
-__global__ void __launch_bounds__(256) k_order_place(PairSel sel, const uint32_t *read_blocks, int nr, uint32_t *counts, uint32_t *order, const uint8_t *done)
+__global__ void __launch_bounds__(256) k_order_place(PairSel sel, const uint32_t *read_blocks, int nr, uint32_t *counts, uint32_t *order, const uint8_t *done, int cls_lo, int cls_hi)
 {
     __shared__ uint32_t n_cls[kWorkClasses], at_cls[kWorkClasses];
     if (threadIdx.x < kWorkClasses) n_cls[threadIdx.x] = 0u;
@@ -348,6 +357,7 @@ __global__ void __launch_bounds__(256) k_order_place(PairSel sel, const uint32_t
     for (int t = 0; t < kOrderTile; t++) {
         const uint32_t local = base + t * 256u + threadIdx.x;
         cls[t] = local < sel.n ? pair_work_class(sel, local, read_blocks, nr, done) : -1;
+        if (cls[t] < cls_lo || cls[t] > cls_hi) cls[t] = -1;
 #pragma unroll
         for (int k = 0; k < kWorkClasses; k++) {
             const uint64_t m = __ballot(cls[t] == k);
@@ -419,20 +429,27 @@ __global__ void __launch_bounds__(256) k_simple(Ctx cx, ReadBatch rb, uint32_t n
     bool later = false;
     if (ok) {
         const PairState st = pair_state(cx.state, cx.lay, cx.caps, pair);
+        // both reads' counts before the first fetch of a hit: a pair with a read of more than kSimpleHits hits is not this kernel's, and its hits are
+        // not looked at — the clustering kernel may be sorting a heavy pair's in place at this moment (run_pairs: the heavy pairs aside)
+        int nhs[2] = {0, 0};
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            if (s < nr) {
+                const uint32_t r = pair * nr + s;
+                nhs[s] = (int)(read_blocks[r] >> 20);
+                ok = ok && nhs[s] >= 1 && nhs[s] <= kSimpleHits && !(cx.read_ext[r] >> 31);
+            }
+        }
 #pragma unroll
         for (int s = 0; s < 2; s++) {
             if (s < nr && ok) {
                 const uint32_t r = pair * nr + s;
-                const int nh = (int)(read_blocks[r] >> 20);
                 rl[s] = (int)(rb.off[r + 1] - rb.off[r]);
                 io.read = r;
-                ok = nh >= 1 && nh <= kSimpleHits && !(cx.read_ext[r] >> 31);
-                if (ok) {
-                    if constexpr (DETAIL) { uint8_t *rec = cx.detail + (uint64_t)r * cx.dlay.stride; det.frags = (Frag *)(rec + sizeof(DetailHdr)); det.ops = rec + cx.dlay.off_ops; }
-                    const int how = simple_read<NW, uint16_t>(cx.ix, cx.pm, rl[s], cx.packed + (uint64_t)r * cx.wpad, st.hits[s], nh, sr[s], stage + s * kSimpleRuns * 256, 256, io, det);
-                    ok = how != kSimpleNo;
-                    later = later || how == kSimpleLater;
-                }
+                if constexpr (DETAIL) { uint8_t *rec = cx.detail + (uint64_t)r * cx.dlay.stride; det.frags = (Frag *)(rec + sizeof(DetailHdr)); det.ops = rec + cx.dlay.off_ops; }
+                const int how = simple_read<NW, uint16_t>(cx.ix, cx.pm, rl[s], cx.packed + (uint64_t)r * cx.wpad, st.hits[s], nhs[s], sr[s], stage + s * kSimpleRuns * 256, 256, io, det);
+                ok = how != kSimpleNo;
+                later = later || how == kSimpleLater;
             }
         }
         if (ok && nr == 2) ok = simple_pair_ok(sr[0], sr[1], est[pair]);
@@ -510,8 +527,8 @@ static __device__ __forceinline__ uint32_t listed_pairs(const PairSel &sel, cons
     return n;
 }
 
-// (cls_lo .. cls_hi: with the pairs listed by weight, the launch takes the pairs of these classes only.  The one launch site takes all
-//  classes in one launch, heaviest first inside it: a launch of their own for the heavy classes, ahead of the light ones, is no longer made)
+// (cls_lo .. cls_hi: with the pairs listed by weight, the launch takes the pairs of these classes only: all classes in one launch, heaviest
+//  first inside it, or — run_pairs, the heavy pairs aside — the heavy classes on a side stream beside k_simple and the light ones behind it)
 __global__ void __launch_bounds__(256) k_cluster(Ctx cx, ReadBatch rb, PairSel sel, RescueList rl, const uint32_t *read_blocks, EarlyList el, const uint32_t *order,
                                                  const uint32_t *order_cnt, int cls_lo, int cls_hi)
 {
@@ -1338,6 +1355,7 @@ static Knobs knobs_read()
     k.cluster_by_lane = on("MCX_CLUSTER_BY_LANE"); k.rescue_in_line = on("MCX_RESCUE_IN_LINE"); k.build_by_lane = on("MCX_BUILD_BY_LANE");
     k.no_sums_cache = on("MCX_NO_SUMS_CACHE"); k.prof_by_column = on("MCX_PROF_BY_COLUMN"); k.tier1_hist = on("MCX_TIER1_HIST"); k.dp_hist = on("MCX_DP_HIST");
     k.no_tier_overlap = on("MCX_NO_TIER_OVERLAP"); k.no_late_overlap = on("MCX_NO_LATE_OVERLAP"); k.no_prof_overlap = on("MCX_NO_PROF_OVERLAP"); k.no_tier1_grow = on("MCX_NO_TIER1_GROW");
+    k.cluster_in_line = on("MCX_CLUSTER_IN_LINE"); k.cluster_split = on("MCX_CLUSTER_SPLIT");
     // A batch packed on its way in (mcx_stream_submit_packed; MCX_PREPACK=1) pays on runtimes whose copies in and out overlap: 16.2-16.3 against 16.7-16.8 ms per
     // step on ROCm 7.2's; on one that puts both directions on one SDMA engine (HIP 7.0, what torch's wheel carries) the copy in ends late and the longer chain
     // behind it reaches into the next step: 17.5 against 17.1.  Off unless asked for: one fuzz round in 480 of the CLI with it on did not come out
@@ -1433,7 +1451,7 @@ struct PassSizes {
     uint32_t task_cap = 0;           // SA tasks (0: no list — a side set runs only with every suffix-array entry resident)
     uint32_t job_cap[kDpClasses] = {0, 0, 0, 0, 0, 0};
     uint64_t dp_stride[3] = {0, 0, 0}; uint32_t dp_blocks[3] = {0, 0, 0}, dp_lane_blocks = 0;
-    uint32_t h_cnt_words = CNT_N;
+    uint32_t h_cnt_words = CNT_COPY;
 };
 
 static PassSizes tier0_sizes(const mcx_ctx *c)
@@ -1454,7 +1472,7 @@ static PassSizes tier0_sizes(const mcx_ctx *c)
     if (const char *e = getenv("MCX_DP_BLOCKS1")) blocks[1] = (uint32_t)std::max(256, atoi(e)); // (experiments; a size that was asked for stays: dp_scratch_grow)
     for (int k = 0; k < 3; k++) { z.dp_stride[k] = spill[k]; z.dp_blocks[k] = blocks[k]; }
     z.dp_lane_blocks = 4096;
-    z.h_cnt_words = CNT_N + 8; // (+8: the seeding statistics of a batch, on their way to batch_close)
+    z.h_cnt_words = CNT_COPY + 8; // (+8: the seeding statistics of a batch, on their way to batch_close)
     return z;
 }
 
@@ -1486,6 +1504,7 @@ static int passres_alloc(PassRes &t, const PassSizes &z)
         HIP_TRY(hipEventCreateWithFlags(&t.dp_join[k], hipEventDisableTiming));
     }
     HIP_TRY(hipEventCreateWithFlags(&t.dp_fork, hipEventDisableTiming));
+    if (z.tier0 && z.n_side) for (hipEvent_t *e : {&t.ev_seeded, &t.ev_order_h, &t.ev_heavy}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (auto &e : t.ev) HIP_TRY(hipEventCreate(&e));
     t.task_cap = z.task_cap;
     if (t.task_cap && (rc = dmalloc(&t.d_tasks, t.task_cap))) return rc;
@@ -1522,6 +1541,7 @@ static void passres_free(PassRes &t)
     for (auto &e : t.ev) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 5; k++) { if (t.dp_stream[k]) (void)hipStreamDestroy(t.dp_stream[k]); if (t.dp_join[k]) (void)hipEventDestroy(t.dp_join[k]); }
     if (t.dp_fork) (void)hipEventDestroy(t.dp_fork);
+    for (hipEvent_t e : {t.ev_seeded, t.ev_order_h, t.ev_heavy}) if (e) (void)hipEventDestroy(e);
     if (t.stream) (void)hipStreamDestroy(t.stream);
 }
 
@@ -1535,7 +1555,7 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
     HIP_TRY(hipSetDevice(idx->device));
     for (auto &e : c->ev_pack) HIP_TRY(hipEventCreate(&e));
     int rc = 0;
-    c->tier[0].caps = tier0_caps(); c->tier[0].lay = make_layout(c->tier[0].caps); c->tier[0].max_pairs = (uint32_t)c->max_reads;
+    c->tier[0].caps = tier0_caps(); c->light_fit = light_pairs_fit(c->tier[0].caps); c->tier[0].lay = make_layout(c->tier[0].caps); c->tier[0].max_pairs = (uint32_t)c->max_reads;
     c->tier[1].caps = tier1_caps(c->rlen_max); c->tier[1].lay = make_layout(c->tier[1].caps);
     // (the heavy pairs of a batch in as few passes as possible — a pass is bound by its slowest pair, not by its size, and passes follow
     //  one another: BASELINE config 5 sends 4.5 % of its pairs here, five passes of 36 k pairs with 8 GB of records — with room in
@@ -1818,7 +1838,30 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
     // the pairs in the order of their weight (k_order_*): worth two small passes when the pass is a large one
     const uint32_t *order = nullptr, *order_cnt = nullptr;
     bool split = false; // (time stamps 10 and 11 were taken: the straight-line path's and the order's share of the stage before clustering)
-    if (tier == 0 && sel.n >= kn.order_min && c->d_order && !kn.no_work_order) {
+    const bool ordered = tier == 0 && sel.n >= kn.order_min && c->d_order && !kn.no_work_order;
+    // The heavy pairs aside: their order (pass H) and their clustering need k_seed's output alone — k_simple never takes a pair with more than kLightHits
+    // hits and does not look at its hits —, so they go onto a side stream right behind the seeding, beside the straight-line path; the main stream lists
+    // and clusters the light pairs behind k_simple and joins.  Every pair that can run over while clustering is a heavy one (light_pairs_fit, asked where
+    // the capacities were made), so the early list, its length and ev_clustered come from the side stream: the large tier starts from there.
+    // MCX_CLUSTER_IN_LINE: one launch over all classes on the pass's stream, as it is for the other tiers, without the order, and without side streams.
+    // Not where there is nothing to hide behind: with hardly a straight-line pair in the batch (250-base reads at 5 % indels: nearly every pair is heavy)
+    // k_simple ends in 0.2 ms, the two clustering launches only share the chip, and the step was measured 1 % longer.  What the last large pass saw decides.
+    const bool aside = ordered && R.dp_stream[0] && R.ev_seeded && c->light_fit && c->aside_pays && !kn.cluster_in_line && !kn.cluster_split;
+    hipStream_t hs = aside ? R.dp_stream[0] : s;
+    if (aside) {
+        const unsigned ob = (sel.n + 256 * kOrderTile - 1) / (256 * kOrderTile);
+        HIP_TRY(hipEventRecord(R.ev_seeded, s)); // (behind k_sa, which rewrites the hits where the suffix array is sampled)
+        HIP_TRY(hipStreamWaitEvent(hs, R.ev_seeded, 0));
+        k_order_count<<<ob, 256, 0, hs>>>(sel, so.read_blocks, nr, R.d_cnt + CNT_ORDER, nullptr, 0, kHeavyClasses - 1);
+        k_order_place<<<ob, 256, 0, hs>>>(sel, so.read_blocks, nr, R.d_cnt + CNT_ORDER, c->d_order, nullptr, 0, kHeavyClasses - 1);
+        HIP_TRY(hipEventRecord(R.ev_order_h, hs));
+        // (a grid for every pair of the pass: how many are heavy stays on the device, and a block past the launch's classes ends at once)
+        k_cluster<<<pb, 256, 0, hs>>>(cx, rb, sel, rl, so.read_blocks, el, c->d_order, R.d_cnt + CNT_ORDER, 0, kHeavyClasses - 1);
+        if (early && c->h_early) k_publish_early<<<1, 64, 0, hs>>>(R.d_cnt + CNT_EARLY, c->d_batch_flags + 3, c->d_early);
+        if (early) HIP_TRY(hipEventRecord(c->ev_clustered, hs));
+        HIP_TRY(hipEventRecord(R.ev_heavy, hs));
+    }
+    if (ordered) {
         // ahead of them, on a whole batch: the straight-line pairs from their seeds to their records (k_simple); what is left is listed
         // by weight for the per-pair kernels.  (Not without the suffix array in HBM — the seeds must be text positions —, not on a
         // selection: k_simple takes pair = record.  With the -vcf bookkeeping on it writes the pairs' detail records as well.)
@@ -1846,8 +1889,10 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
         uint32_t *cls_cnt = R.d_cnt + CNT_ORDER; // (cleared with the pass's counters)
         order_cnt = cls_cnt; // (the class counts: how many pairs the order lists — all of them without k_simple — and where a class begins)
         const unsigned ob = (sel.n + 256 * kOrderTile - 1) / (256 * kOrderTile);
-        k_order_count<<<ob, 256, 0, s>>>(sel, so.read_blocks, nr, cls_cnt, done);
-        k_order_place<<<ob, 256, 0, s>>>(sel, so.read_blocks, nr, cls_cnt, c->d_order, done);
+        // (aside: pass L — its stretches of the order begin where pass H's final counts end; that event is long past by now)
+        if (aside) HIP_TRY(hipStreamWaitEvent(s, R.ev_order_h, 0));
+        k_order_count<<<ob, 256, 0, s>>>(sel, so.read_blocks, nr, cls_cnt, done, aside ? kHeavyClasses : 0, kWorkClasses - 1);
+        k_order_place<<<ob, 256, 0, s>>>(sel, so.read_blocks, nr, cls_cnt, c->d_order, done, aside ? kHeavyClasses : 0, kWorkClasses - 1);
         order = c->d_order;
         if (timing) { HIP_TRY(hipEventRecord(R.ev[11], s)); split = true; }
     }
@@ -1857,9 +1902,18 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
         k_cluster_wave<<<std::min<unsigned>(sel.n, 16384u), 64, cluster_lds_bytes(small, small), s>>>(cx, rb, sel, rl, so.read_blocks, -1, small, small, small);
         if (small < cx.caps.hit_cap)
             k_cluster_wave<<<std::min<unsigned>(sel.n, 8192u), 64, cl_bytes, s>>>(cx, rb, sel, rl, so.read_blocks, small, 1 << 30, cx.caps.hit_cap, cx.caps.cand_cap);
+    } else if (aside) { // the light pairs; none of them can run over: no early list.  Then the heavy side joins (the time stamp below: behind the join)
+        EarlyList none = el; none.ids = nullptr; none.est = nullptr; none.cap = 0;
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, none, order, order_cnt, kHeavyClasses, kWorkClasses - 1);
+        HIP_TRY(hipStreamWaitEvent(s, R.ev_heavy, 0));
+    } else if (ordered && kn.cluster_split) { // (MCX_CLUSTER_SPLIT, measurements: the two launches of the aside path one after the other on the pass's stream)
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kHeavyClasses - 1);
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, kHeavyClasses, kWorkClasses - 1);
     } else k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kWorkClasses - 1);
-    if (early && c->h_early) k_publish_early<<<1, 64, 0, s>>>(R.d_cnt + CNT_EARLY, c->d_batch_flags + 3, c->d_early);
-    if (early) HIP_TRY(hipEventRecord(c->ev_clustered, s));
+    if (!aside) {
+        if (early && c->h_early) k_publish_early<<<1, 64, 0, s>>>(R.d_cnt + CNT_EARLY, c->d_batch_flags + 3, c->d_early);
+        if (early) HIP_TRY(hipEventRecord(c->ev_clustered, s));
+    }
     if (timing) HIP_TRY(hipEventRecord(R.ev[e++], s));
     // mate rescue beside the build of the pairs that do not await it (k_build's modes), when the set has a side stream for it
     const bool rescue_aside = paired && R.dp_stream[0] && !kn.rescue_in_line;
@@ -1910,8 +1964,9 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
     else k_finish<false><<<pb, 256, 0, s>>>(cx, rb, sel, d_recs, c->d_pout, R.d_ov, R.d_cnt + CNT_OV, R.ov_cap, c->d_batch_flags + 2, order, order_cnt, MultiOut());
     if (timing) HIP_TRY(hipEventRecord(R.ev[e++], s));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(R.h_cnt, R.d_cnt, CNT_N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    const int e_flag = e | (rescue_aside ? 0x100 : 0) | (split ? 0x200 : 0); // (for pass_finish: which stage a time stamp closes)
+    static_assert(CNT_COPY == CNT_ORDER + kWorkClasses * kCntPad, "the order's class counts come back with the pass's counters");
+    HIP_TRY(hipMemcpyAsync(R.h_cnt, R.d_cnt, CNT_COPY * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    const int e_flag = e | (rescue_aside ? 0x100 : 0) | (split ? 0x200 : 0) | (aside ? 0x400 : 0); // (for pass_finish: which stage a time stamp closes; the heavy pairs went aside)
     if (queued) { *queued = e_flag; return 0; }
     hipEvent_t ev_dbg[2] = {nullptr, nullptr}; // (MCX_TIMING: when tier 0 and the large tier beside it were done)
     if (early && kn.timing) {
@@ -2031,6 +2086,14 @@ static int pass_finish(mcx_ctx *c, int tier, const PassRes &R, uint32_t n_sel, m
             }
         }
     }
+    if (tier == 0) { // mcx_pass_last_shape: the class counts (all zero without the order), the two launches' pairs, whether the heavy ones went aside, the early list
+        uint32_t *sh = c->last_shape;
+        sh[6] = sh[7] = 0;
+        for (int k = 0; k < kWorkClasses; k++) { sh[k] = n[CNT_ORDER + k * kCntPad]; sh[k < kHeavyClasses ? 6 : 7] += sh[k]; }
+        sh[8] = (e & 0x400) ? 1u : 0u; sh[9] = n[CNT_EARLY];
+        // (run_pairs: the heavy pairs aside) a large ordered pass says whether the next one has a straight-line path worth hiding behind: an eighth of its pairs
+        if ((e & 0x200) && n_sel >= kAsideGatePairs) c->aside_pays = (uint64_t)n[CNT_SIMPLE] * 8 >= n_sel;
+    }
     if (tier == 0 && !c->dp_grown) c->job2_seen = std::max(c->job2_seen, n[CNT_JOB2]); // (batch_close: dp_scratch_grow)
     // a work list that ran over: nothing of this pass is kept, the caller maps the selection in two halves
     if ((R.d_tasks && n[CNT_TASKS] > R.task_cap) || n[CNT_RESCUE] > R.rescue_cap || n[CNT_RTASK] > R.rtask_cap || n[CNT_RSEED] > R.rseed_cap) return kListOverflow;
@@ -2061,6 +2124,13 @@ static int pass_finish(mcx_ctx *c, int tier, const PassRes &R, uint32_t n_sel, m
             stats->ms_dp += ms[6]; stats->ms_finish += ms[7];
         }
     }
+    return 0;
+}
+
+extern "C" int mcx_pass_last_shape(mcx_ctx *c, uint32_t out[10])
+{
+    if (!c || !out) return mcx_set_error(MCX_ERR_ARG, "mcx_pass_last_shape: null argument");
+    memcpy(out, c->last_shape, sizeof c->last_shape);
     return 0;
 }
 
@@ -2485,12 +2555,12 @@ extern "C" int mcx_batch_begin(mcx_ctx *c, const uint8_t *d_bases, const uint32_
     rc = run_selection(c, br.rb, paired, nullptr, nullptr, est0, br.n_pairs, br.recs, d_cigar, stats, true);
     br.t_begun = std::chrono::steady_clock::now();
     if (rc) return rc;
-    if (c->tail.queued) memcpy(c->t0.h_cnt + CNT_N, c->tail.h + 2, sizeof br.hs); // (the pass queued the batch's tail and it stands: the statistics came with it)
+    if (c->tail.queued) memcpy(c->t0.h_cnt + CNT_COPY, c->tail.h + 2, sizeof br.hs); // (the pass queued the batch's tail and it stands: the statistics came with it)
     else { // seeding statistics (E, blocks, H of SURVEY.md 8d) before the per-read arrays are reused for the chunk sums
         unsigned long long *d_sum = (unsigned long long *)c->t0.d_cnt;
         HIP_TRY(hipMemsetAsync(c->t0.d_cnt, 0, CNT_N * sizeof(uint32_t), s));
         k_reduce_stats<<<kReduceStatsBlocks, 256, 0, s>>>(c->d_read_ext, c->d_read_blocks, n_reads, d_sum);
-        HIP_TRY(hipMemcpyAsync(c->t0.h_cnt + CNT_N, d_sum, sizeof br.hs, hipMemcpyDeviceToHost, s)); // (read by batch_close, behind the sums' synchronisation: no round trip of its own)
+        HIP_TRY(hipMemcpyAsync(c->t0.h_cnt + CNT_COPY, d_sum, sizeof br.hs, hipMemcpyDeviceToHost, s)); // (read by batch_close, behind the sums' synchronisation: no round trip of its own)
     }
     br.open = true;
     return 0;
@@ -2803,7 +2873,7 @@ static int batch_close(mcx_ctx *c, mcx_stats *stats)
         int64_t pairs = 0, dist_sum = 0, len_sum = 0;
         if (br.paired) for (uint32_t k = 0; k < br.n_chunks; k++) { pairs += br.ok[k]; dist_sum += br.ds[k]; len_sum += br.ds[br.n_chunks + k]; }
         stats->reads += br.rb.n_reads; stats->mapped += br.mapped; stats->pairs += pairs; stats->pair_dist_sum += dist_sum; stats->pair_len_sum += len_sum;
-        memcpy(br.hs, c->t0.h_cnt + CNT_N, sizeof br.hs);
+        memcpy(br.hs, c->t0.h_cnt + CNT_COPY, sizeof br.hs);
         stats->fm_ext_steps += (int64_t)br.hs[0]; stats->fm_blocks += (int64_t)br.hs[1]; stats->sa_hits += (int64_t)br.hs[2];
         float ms_pack = 0;
         if (hipEventElapsedTime(&ms_pack, c->ev_pack[0], c->ev_pack[1]) == hipSuccess) stats->ms_encode += ms_pack; // k_pack_reads

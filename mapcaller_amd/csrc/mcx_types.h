@@ -79,6 +79,13 @@ struct Caps {
     int32_t kmer_cap;  // rescue window length
 };
 
+// The order of a pass (mcx_pipeline.hip work_class) calls a pair light when its two reads hold at most kLightHits seed hits together.
+// A light pair cannot run over while clustering — a read of it has at most kLightHits hits, and no more clusters than hits —
+// as long as the tier's seeding capacities are no smaller: then every pair the clustering kernel lists for the large tier is a heavy
+// one, and the heavy pairs may be clustered in a launch of their own beside the straight-line path (run_pairs asks this once per context).
+constexpr int kLightHits = 8;
+static inline MCX_HD bool light_pairs_fit(const Caps &c) { return kLightHits <= (c.hit_seed < c.cand_seed ? c.hit_seed : c.cand_seed); }
+
 struct alignas(16) Hit { // one seed occurrence: FragPair_t with bSimple (structure.h:113-123)
     int64_t gPos;     // K1 stores the BWT row here, K2 overwrites it with the text position
     int32_t rPos;

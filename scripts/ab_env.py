@@ -79,7 +79,7 @@ def main():
             print(json.dumps({"variant": v, "ms_per_step": round(1000 * dt / a.steps, 3), "M_reads_per_s": round(n * a.steps / dt / 1e6, 1),
                               "stage_ms": {k[3:]: round(d[k] / a.steps, 3) for k in d if k.startswith("ms_")}, "tier1_pairs": d["tier1_pairs"],
                               "mapped": d["mapped"], "fm_blocks": d["fm_blocks"], "dp_jobs": d["dp_jobs"], "dp_cells": d["dp_cells"], "simple_pairs": d.get("simple_pairs"),
-                              "checksum_records": chk_rec, "checksum_cigars": chk_cig}), flush=True)
+                              "pass_shape": mp.pass_last_shape(), "checksum_records": chk_rec, "checksum_cigars": chk_cig}), flush=True)
             mp.close()
             for k, _ in kv:
                 os.environ.pop(k, None)
