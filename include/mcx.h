@@ -421,6 +421,26 @@ void mcx_vcf_defaults(mcx_vcf_opts *);
 int mcx_call_variants(const mcx_index *, const uint32_t *d_planes, const mcx_sparse_rec *recs, uint64_t n_recs,
                       int64_t paired_pairs, int64_t pair_dist_sum, int64_t pair_len_sum,
                       const mcx_vcf_opts *, const char *vcf_path, mcx_vcf_stats *stats);
+/* Test entry: the dense half of mcx_call_variants by itself, so that its kernels can be held against a plain restatement on
+ * planes made for the purpose.  No index: d_pac is the forward genome in device memory, four bases a byte as in the .pac file
+ * ((genome_size + 3) / 4 bytes); d_planes as for mcx_call_variants.  Runs, in this order on one object, the scan (block depth,
+ * per-position records, their (position, type) order), the column gather of pos[0 .. n_pos) and the coverage sums (mode 0) /
+ * minima over covered positions (mode 1; ~0 if there is none) of ranges[0 .. n_ranges), each [beg, end] inclusive and clipped
+ * to the genome.  *sites / *n_sites: the ordered records, in storage of the library's that the next call on any thread
+ * replaces; columns, range_vals: the caller's, n_pos and n_ranges entries.  A position outside the genome gives a zero column.
+ * Of opts, -ploidy -ad -somatic -monomorphic -gvcf and freq_thr are read (-gvcf is dropped beside -monomorphic as in
+ * mcx_call_variants). */
+typedef struct mcx_vc_site {  /* a call (type 0 SNV, 11 monomorphic) or a run boundary (100 .. 105: gap start / end, dup start / end, */
+    int64_t pos;              /* normal start / end) at pos; alt: codes of the one or two ALT alleles, low nibble first, 0xF = none  */
+    uint8_t type, geno, qscore, alt;
+    uint16_t DP, AD_ref, AD_alt, pad;
+    uint32_t pad2;
+} mcx_vc_site;
+typedef struct mcx_vc_column { uint32_t v[10]; int32_t depth; uint32_t ref; } mcx_vc_column; /* the ten counters, block depth, reference code */
+typedef struct mcx_vc_range { int64_t beg, end; int32_t mode, pad; } mcx_vc_range;
+int mcx_vc_dense_dev(int device, const uint8_t *d_pac, int64_t genome_size, const uint32_t *d_planes, const mcx_vcf_opts *,
+                     const int64_t *pos, uint64_t n_pos, const mcx_vc_range *ranges, uint64_t n_ranges,
+                     const mcx_vc_site **sites, uint64_t *n_sites, mcx_vc_column *columns, uint64_t *range_vals);
 
 /* ---- SAM text ----------------------------------------------------------------------------------
  * Replaces GenerateSingleSamStream / GeneratePairedSamStream (reference src/SamReport.cpp:324-488) and the -m lines

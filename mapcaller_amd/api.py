@@ -63,7 +63,7 @@ SYMBOLS = [
     "mcx_opts_default", "mcx_ctx_create", "mcx_ctx_create_fit", "mcx_ctx_free", "mcx_bwt_search_batch", "mcx_extend_batch", "mcx_extend_lanes",
     "mcx_avg_init", "mcx_map_batch_dev", "mcx_map_batch", "mcx_cigar_words", "mcx_map_files", "mcx_map_files_ex", "mcx_file_opts_default",
     "mcx_profile_attach", "mcx_profile_settle", "mcx_profile_finalize", "mcx_profile_sparse", "mcx_planes_alloc", "mcx_planes_free", "mcx_planes_bytes",
-    "mcx_vcf_defaults", "mcx_call_variants",
+    "mcx_vcf_defaults", "mcx_call_variants", "mcx_vc_dense_dev",
     "mcx_batch_begin", "mcx_batch_sums", "mcx_batch_replay", "mcx_batch_end", "mcx_avg_walk", "mcx_batch_totals", "mcx_batch_check", "mcx_avg_advance", "mcx_exchange_local", "mcx_exchange_local_free",
     "mcx_profile_sparse_shard", "mcx_batch_end_keys", "mcx_batch_accumulate",
     "mcx_stream_submit", "mcx_stream_submit_packed", "mcx_stream_map", "mcx_stream_collect", "mcx_stream_next", "mcx_stream_mapped",
@@ -311,6 +311,49 @@ class VcfStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# the records of mcx_vc_dense_dev (csrc/mcx_variants_host.h SiteRec, Column, RangeQ)
+VC_SITE_DTYPE = np.dtype([("pos", "<i8"), ("type", "u1"), ("geno", "u1"), ("qscore", "u1"), ("alt", "u1"), ("DP", "<u2"), ("AD_ref", "<u2"),
+                          ("AD_alt", "<u2"), ("pad", "<u2"), ("pad2", "<u4")])
+VC_COLUMN_DTYPE = np.dtype([("v", "<u4", (10,)), ("depth", "<i4"), ("ref", "<u4")])
+VC_RANGE_DTYPE = np.dtype([("beg", "<i8"), ("end", "<i8"), ("mode", "<i4"), ("pad", "<i4")])
+assert (VC_SITE_DTYPE.itemsize, VC_COLUMN_DTYPE.itemsize, VC_RANGE_DTYPE.itemsize) == (24, 48, 24)
+
+
+def vcf_opts(**switches):
+    """mcx_vcf_opts at the reference's defaults with ``switches`` (its fields) set; strings are kept alive by the second value."""
+    o = VcfOpts()
+    lib().mcx_vcf_defaults(C.byref(o))
+    keep = []
+    for k, v in switches.items():
+        if isinstance(v, str):
+            v = v.encode()
+            keep.append(v)
+        setattr(o, k, v)
+    return o, keep
+
+
+def vc_dense(d_pac_ptr: int, G: int, d_planes_ptr: int, positions=(), ranges=(), device: int = 0, **switches):
+    """mcx_vc_dense_dev (tests): the variant caller's dense half over planes and a packed genome in HBM.  ``positions``: genome
+    positions; ``ranges``: (beg, end, mode) rows, mode 0 coverage sum, 1 minimum over covered positions.  Returns (the ordered
+    records as VC_SITE_DTYPE, the columns as VC_COLUMN_DTYPE, the range values as uint64), each a numpy array of its own."""
+    o, _keep = vcf_opts(**switches)
+    pos = np.ascontiguousarray(positions, dtype=np.int64).reshape(-1)
+    rq = np.zeros(len(ranges), dtype=VC_RANGE_DTYPE)
+    if len(ranges):
+        r = np.asarray(ranges, dtype=np.int64).reshape(-1, 3)
+        rq["beg"], rq["end"], rq["mode"] = r[:, 0], r[:, 1], r[:, 2]
+    cols = np.zeros(len(pos), dtype=VC_COLUMN_DTYPE)
+    vals = np.zeros(len(rq), dtype=np.uint64)
+    p_sites, n_sites = C.c_void_p(), C.c_uint64()
+    _check(lib().mcx_vc_dense_dev(device, d_pac_ptr, G, d_planes_ptr, C.byref(o), pos.ctypes.data, len(pos), rq.ctypes.data, len(rq),
+                                  C.byref(p_sites), C.byref(n_sites), cols.ctypes.data, vals.ctypes.data), "mcx_vc_dense_dev")
+    n = int(n_sites.value)
+    sites = np.empty(n, dtype=VC_SITE_DTYPE)
+    if n:
+        C.memmove(sites.ctypes.data, p_sites.value, n * VC_SITE_DTYPE.itemsize)
+    return sites, cols, vals
+
+
 _lib = None
 
 
@@ -407,6 +450,8 @@ def lib() -> C.CDLL:
     L.mcx_vcf_defaults.restype = None
     L.mcx_call_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64,
                                     C.POINTER(VcfOpts), C.c_char_p, C.POINTER(VcfStats)]
+    L.mcx_vc_dense_dev.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(VcfOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
     L.mcx_gz_inflate.restype = C.c_int64
     L.mcx_gz_inflate.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     for f in (L.mcx_sam_format_dev, L.mcx_sam_format):
@@ -539,14 +584,7 @@ class Index:
         ``pair_dist_sum`` / ``pair_len_sum``: totals of Mapper.stats.  ``switches``: fields of
         mcx_vcf_opts (ploidy, min_allele_depth, min_cnv, min_gap, fragment_size, filter, gvcf,
         monomorphic, somatic, sample_id, ref_name, cmdline)."""
-        o = VcfOpts()
-        lib().mcx_vcf_defaults(C.byref(o))
-        keep = []
-        for k, v in switches.items():
-            if isinstance(v, str):
-                v = v.encode()
-                keep.append(v)
-            setattr(o, k, v)
+        o, _keep = vcf_opts(**switches)
         if isinstance(sparse, np.ndarray):  # raw mcx_sparse_rec bytes
             raw = np.ascontiguousarray(sparse, dtype=np.uint8).reshape(-1, 64)
             st = VcfStats()

@@ -242,7 +242,9 @@ template <typename T> struct DevBuf {
 // the dense half on the GPU: the ten planes in HBM behind the caller's interface
 class GpuProfile : public DenseProfile {
 public:
-    GpuProfile(const mcx_index *ix, const uint32_t *planes) : ix_(ix), pl_(planes_view((void *)planes, ix->view.G)), G_(ix->view.G) {}
+    GpuProfile(const mcx_index *ix, const uint32_t *planes) : GpuProfile(ix->view, planes) {}
+    // (of the view, the dense half reads the packed genome alone: pac, G, G2, seq_len)
+    GpuProfile(const IndexView &view, const uint32_t *planes) : view_(view), pl_(planes_view((void *)planes, view.G)), G_(view.G) {}
     int64_t genome_size() const override { return G_; }
     int gather(const std::vector<int64_t> &pos, ColVec &out) override
     {
@@ -252,7 +254,7 @@ public:
         int rc;
         if ((rc = d_pos.alloc(pos.size())) || (rc = d_col.alloc(pos.size()))) return rc;
         if ((rc = copy_in(d_pos.p, pos.data(), pos.size() * sizeof(int64_t)))) return rc;
-        k_vc_gather<<<(unsigned)((pos.size() + 255) / 256), 256>>>(pl_, d_depth_.p, ix_->view, G_, d_pos.p, pos.size(), d_col.p);
+        k_vc_gather<<<(unsigned)((pos.size() + 255) / 256), 256>>>(pl_, d_depth_.p, view_, G_, d_pos.p, pos.size(), d_col.p);
         VC_TRY(hipGetLastError());
         return copy_out(out.data(), d_col.p, pos.size() * sizeof(Column));
     }
@@ -299,7 +301,7 @@ public:
             VC_TRY(hipEventRecord(ev[2], 0));
             const int64_t n_tiles = (G_ + kScanTile - 1) / kScanTile, groups = std::min<int64_t>(n_tiles, 256 * 32);
             const int64_t per_group = (n_tiles + groups - 1) / groups;
-            k_vc_scan<<<(unsigned)((n_tiles + per_group - 1) / per_group), kScanTile>>>(pl_, d_depth_.p, ix_->view, sp, d_out.p, d_n.p, cap, per_group);
+            k_vc_scan<<<(unsigned)((n_tiles + per_group - 1) / per_group), kScanTile>>>(pl_, d_depth_.p, view_, sp, d_out.p, d_n.p, cap, per_group);
             VC_TRY(hipGetLastError());
             VC_TRY(hipEventRecord(ev[3], 0));
             VC_TRY(hipMemcpy(&n, d_n.p, sizeof n, hipMemcpyDeviceToHost));
@@ -347,7 +349,7 @@ public:
     }
 
 private:
-    const mcx_index *ix_;
+    IndexView view_;
     PlanesView pl_;
     int64_t G_;
     DevBuf<int32_t> d_depth_;
@@ -390,4 +392,38 @@ extern "C" int mcx_call_variants(const mcx_index *ix, const uint32_t *d_planes, 
     const int rc = c.run(recs, n_recs, paired_pairs, pair_dist_sum, pair_len_sum, vcf_path, stats);
     if (rc == 0 && stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+// Test entry (include/mcx.h): scan, gather and ranges of one GpuProfile over the caller's planes and packed genome
+static_assert(sizeof(mcx_vc_site) == sizeof(SiteRec) && sizeof(mcx_vc_column) == sizeof(Column) && sizeof(mcx_vc_range) == sizeof(RangeQ),
+              "the records of mcx_vc_dense_dev are the dense half's own");
+extern "C" int mcx_vc_dense_dev(int device, const uint8_t *d_pac, int64_t genome_size, const uint32_t *d_planes, const mcx_vcf_opts *opts,
+                                const int64_t *pos, uint64_t n_pos, const mcx_vc_range *ranges, uint64_t n_ranges,
+                                const mcx_vc_site **sites, uint64_t *n_sites, mcx_vc_column *columns, uint64_t *range_vals)
+{
+    if (!d_pac || !d_planes || !opts || !sites || !n_sites || (n_pos && (!pos || !columns)) || (n_ranges && (!ranges || !range_vals)))
+        return mcx_set_error(MCX_ERR_ARG, "mcx_vc_dense_dev: null argument");
+    if (genome_size < 1) return mcx_set_error(MCX_ERR_ARG, "mcx_vc_dense_dev: empty genome");
+    if (opts->min_allele_depth < 1) return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_vc_dense_dev: -ad must be at least 1");
+    VC_TRY(hipSetDevice(device));
+    IndexView view;
+    memset(&view, 0, sizeof view);
+    view.pac = d_pac; view.G = genome_size; view.G2 = 2 * genome_size; view.seq_len = (uint64_t)view.G2;
+    GpuProfile prof(view, d_planes);
+    static std::mutex mu;
+    static SiteVec kept; // (what *sites points into until the next call)
+    std::lock_guard<std::mutex> lock(mu);
+    double ms_depth = 0, ms_scan = 0;
+    int rc;
+    if ((rc = prof.scan(scan_params(*opts, genome_size), kept, ms_depth, ms_scan))) return rc;
+    *sites = (const mcx_vc_site *)kept.data(); *n_sites = kept.size();
+    ColVec col;
+    if ((rc = prof.gather(std::vector<int64_t>(pos, pos + n_pos), col))) return rc;
+    if (n_pos) memcpy(columns, col.data(), n_pos * sizeof(Column));
+    std::vector<RangeQ> q(n_ranges);
+    if (n_ranges) memcpy(q.data(), ranges, n_ranges * sizeof(RangeQ));
+    std::vector<unsigned long long> val;
+    if ((rc = prof.ranges(q, val))) return rc;
+    if (n_ranges) memcpy(range_vals, val.data(), n_ranges * sizeof(unsigned long long));
+    return 0;
 }

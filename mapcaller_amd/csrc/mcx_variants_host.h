@@ -371,12 +371,18 @@ inline void Caller::fold(const mcx_sparse_rec *recs, uint64_t n)
     std::sort(tnl_.begin(), tnl_.end(), lt);
 }
 
-inline int Caller::scan(SiteVec &sites)
+// what the scan reads of the switches (-gvcf gives way to -monomorphic, main.cpp:322)
+static inline ScanParams scan_params(const mcx_vcf_opts &o, int64_t G)
 {
     ScanParams sp;
-    sp.G = G_; sp.min_ad = o_.min_allele_depth; sp.somatic = o_.somatic; sp.ploidy = o_.ploidy; sp.mono = o_.monomorphic; sp.gvcf = o_.gvcf;
-    sp.freq_thr = (double)o_.freq_thr;
-    return prof_.scan(sp, sites, ms_depth_, ms_scan_);
+    sp.G = G; sp.min_ad = o.min_allele_depth; sp.somatic = o.somatic; sp.ploidy = o.ploidy; sp.mono = o.monomorphic; sp.gvcf = o.gvcf && !o.monomorphic;
+    sp.freq_thr = (double)o.freq_thr;
+    return sp;
+}
+
+inline int Caller::scan(SiteVec &sites)
+{
+    return prof_.scan(scan_params(o_, G_), sites, ms_depth_, ms_scan_);
 }
 
 // GetAreaIndFrequency :63-94: the tallies within 5 bp; the most frequent string (the longer one on

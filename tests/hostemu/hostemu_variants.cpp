@@ -155,4 +155,35 @@ int hostemu_call_variants(const char *prefix, const char *prof_path, const char 
     return c.run(recs.data(), recs.size(), pairs, dist_sum, len_sum, vcf_path, nullptr);
 }
 
+// The dense half by itself, as mcx_vc_dense_dev (include/mcx.h) runs it on the GPU: scan, then gather, then ranges on one
+// HostProfile.  pac: the forward genome, four bases a byte; rows: int32 [10][G] in plane order — no index files.
+// *sites points into storage that the next call replaces.
+int hostemu_vc_dense(const uint8_t *pac, int64_t G, const int32_t *rows, const mcx_vcf_opts *opts, const int64_t *pos, uint64_t n_pos,
+                     const mcx_vc_range *ranges, uint64_t n_ranges, const mcx_vc_site **sites, uint64_t *n_sites, mcx_vc_column *columns,
+                     uint64_t *range_vals)
+{
+    static_assert(sizeof(mcx_vc_site) == sizeof(SiteRec) && sizeof(mcx_vc_column) == sizeof(Column) && sizeof(mcx_vc_range) == sizeof(RangeQ), "record layouts");
+    if (!pac || G < 1 || !rows || !opts || !sites || !n_sites) return mcx_set_error(MCX_ERR_ARG, "hostemu_vc_dense: bad argument");
+    HostIndex hix;
+    hix.G = G; hix.seq_len = (uint64_t)(2 * G);
+    hix.pac.assign(pac, pac + (G + 3) / 4);
+    std::vector<uint32_t> planes((size_t)G * 10);
+    for (size_t i = 0; i < planes.size(); i++) planes[i] = (uint32_t)rows[i];
+    HostProfile prof(hix, std::move(planes));
+    static SiteVec kept;
+    double ms_depth, ms_scan;
+    int rc;
+    if ((rc = prof.scan(scan_params(*opts, G), kept, ms_depth, ms_scan))) return rc;
+    *sites = (const mcx_vc_site *)kept.data(); *n_sites = kept.size();
+    ColVec col;
+    if ((rc = prof.gather(std::vector<int64_t>(pos, pos + n_pos), col))) return rc;
+    if (n_pos) memcpy(columns, col.data(), n_pos * sizeof(Column));
+    std::vector<RangeQ> q(n_ranges);
+    if (n_ranges) memcpy(q.data(), ranges, n_ranges * sizeof(RangeQ));
+    std::vector<unsigned long long> val;
+    if ((rc = prof.ranges(q, val))) return rc;
+    if (n_ranges) memcpy(range_vals, val.data(), n_ranges * sizeof(unsigned long long));
+    return 0;
+}
+
 }
