@@ -501,6 +501,26 @@ int mcx_bam_sort_last_ms(mcx_ctx *, float ms[4]);
 int mcx_pass_last_shape(mcx_ctx *, uint32_t out[10]);
 /* mcx_bam_header's bytes for a coordinate-sorted file: the text begins with "@HD\tVN:1.6\tSO:coordinate\n" */
 int mcx_bam_header_sorted(const mcx_index *, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
+/* What a .bai is made of (mapcaller-mi355x -index), from one run of coordinate-sorted records in HBM that has just been deflated.  d_recs[0 .. n_bytes) are
+ * n_records whole records, record i at d_rec_off[i] .. d_rec_off[i + 1] (device; n_records + 1 entries from 0 to n_bytes); they were cut into BGZF blocks of
+ * block_text_bytes of text, block k of the n_blocks = ceil(n_bytes / block_text_bytes) written at byte d_block_coff[k] of the file (device; n_blocks + 1 entries,
+ * the last one the byte behind them).  A record's virtual offset u is d_block_coff[offset / block] << 16 | offset % block; its interval is [pos, bam_endpos): pos +
+ * the reference length of its CIGAR (M, D, N, = and X), pos + 1 when flag bit 4 is set or that length is 0; its bin is reg2bin of the interval (htslib's
+ * hts_idx_push: min_shift 14, 5 levels; 4680 for a record without a contig).
+ * d_runs[0 .. runs_cap) receives one entry per maximal stretch of records with one (ref_id, bin) — the first record's u, the records without and with flag bit 4 —,
+ * all records with refID < 0 as one stretch (ref_id -1, bin 4680); *n_runs their number.  d_lin is the table of the 16 kb windows of all n_ref contigs, contig t's at
+ * d_lin[d_lin_base[t] .. d_lin_base[t + 1]) (device; d_lin_base has n_ref + 1 entries), which the caller sets to all-ones once: every window that a record without
+ * flag bit 4 on a contig touches (pos >> 14 .. (end - 1) >> 14) holds the smallest u seen so far, over consecutive calls on one table.
+ * MCX_ERR_ARG, with nothing written to d_runs or d_lin and nothing read outside the inputs: offsets that do not ascend from 0 to n_bytes, a record that is not
+ * 4 + its block_size long or shorter than its name and CIGAR, n_blocks that is not the number of blocks, a refID of n_ref or more, a position or end beyond 2^29 or
+ * beyond the contig's windows, records whose (refID, pos) descend, a record on a contig behind one without.  runs_cap too small: MCX_ERR_CAPACITY, *n_runs says what
+ * is needed, nothing written.  n_records == 0: 0, no stretches.  Scratch (52 bytes a record) stays with the context.  On the context's stream, waited for. */
+typedef struct mcx_bai_run { int32_t ref_id; uint32_t bin; uint64_t u; uint32_t n_mapped, n_unmapped; } mcx_bai_run;
+int mcx_bam_index_dev(mcx_ctx *, const uint8_t *d_recs, uint64_t n_bytes, const uint64_t *d_rec_off, uint32_t n_records, uint32_t block_text_bytes,
+                      const uint64_t *d_block_coff, uint32_t n_blocks, uint64_t *d_lin, const uint64_t *d_lin_base, uint32_t n_ref,
+                      mcx_bai_run *d_runs, uint64_t runs_cap, uint64_t *n_runs);
+/* the last call's device times in ms: records (fields, CIGAR walk, offsets, order), stretches (flags, scans, the list), windows (running maximum, the table) */
+int mcx_bam_index_last_ms(mcx_ctx *, float ms[3]);
 
 /* ---- BGZF input inflated on the device -------------------------------------------------------------
  * bgzip's container is a row of independent gzip members of at most 64 KB of text, each of which says how long it is ('BC' extra
@@ -551,6 +571,10 @@ void     mcx_deflater_free(mcx_deflater *);
 int      mcx_deflater_set_block(mcx_deflater *, uint32_t text_bytes);    /* 1..65280 per BGZF block, sticky; default 65280; else MCX_ERR_ARG */
 uint64_t mcx_bgzf_bound(uint64_t text_bytes, uint32_t block_text_bytes); /* bytes the blocks of that much text can take at most (every block stored: text + 31 per block) */
 int      mcx_bgzf_deflate_dev(mcx_deflater *, const uint8_t *d_text, uint64_t text_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t *n_out);
+/* where the blocks of the last mcx_bgzf_deflate_dev lie: *d_block_at a device array of the object's own, valid until its next call, with *n_blocks + 1 entries —
+ * block k begins at byte (*d_block_at)[k] of d_out, the last entry is *n_out — over all launches of that call (mcx_bam_index_dev makes virtual offsets of them);
+ * *n_blocks 0 and a null array after a call without text or before the first */
+int      mcx_bgzf_deflate_blocks(mcx_deflater *, const uint64_t **d_block_at, uint64_t *n_blocks);
 /* host buffers, staged through the object's page-locked buffers in as many launches as max_text_bytes requires: the same bytes */
 int      mcx_bgzf_deflate(mcx_deflater *, const uint8_t *text, uint64_t text_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n_out);
 int      mcx_bgzf_eof(uint8_t out[28]);                                  /* the empty block that ends a BGZF file */
@@ -683,6 +707,12 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * records (MCX_SORT_CHUNK=bytes: a debug switch) — equal keys never in two chunks —, and every chunk's slices are read back, inflated, sorted and compressed on the
  * device and written behind mcx_bam_header_sorted's header; a pile-up on one key makes a chunk that HBM must hold whole (MCX_ERR_CAPACITY when it does not).
  * MCX_ERR_UNSUPPORTED before anything is opened: the bit without bit 4, append_sam (a sorted file cannot be appended to), shard_count > 1.  (route: MCX_ROUTE_SORT.)
+ * bit 16 (MCX_SAM_INDEX; mapcaller-mi355x -index; only with bit 8) writes sam_path + ".bai" as well, the index samtools index would make of the file (format BAI; the
+ * same chunks, meta pairs and linear entries as htslib's hts_idx_push / hts_idx_finish, a contig's bins listed ascending — a function of the BAM file alone): after
+ * each chunk of the merge is compressed, mcx_bam_index_dev reads its records, which still lie in HBM, against the places of the chunk's blocks in the file, and
+ * the host keeps 24 bytes a stretch of records with one (contig, bin).  The index is written — under another name, then renamed — once the BAM file is complete
+ * and closed, and removed when the call fails; the BAM file's bytes are those of a run without the bit.  MCX_ERR_UNSUPPORTED before anything is opened: the bit
+ * without bit 8, sam_path "-" (no name to put the index beside), a contig longer than 2^29 (BAI cannot address it; CSI is not offered).  (route: MCX_ROUTE_INDEX.)
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -701,7 +731,8 @@ enum mcx_sam_bits {
     MCX_SAM_DEVICE = 1, /* the SAM text is made on the device */
     MCX_SAM_BGZF = 2,   /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
     MCX_SAM_BAM = 4,    /* ... which hold BAM records instead of SAM text (implies both) */
-    MCX_SAM_SORT = 8    /* ... in coordinate order (only with MCX_SAM_BAM) */
+    MCX_SAM_SORT = 8,   /* ... in coordinate order (only with MCX_SAM_BAM) */
+    MCX_SAM_INDEX = 16  /* ... with its .bai written beside it (only with MCX_SAM_SORT) */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
@@ -714,12 +745,16 @@ enum mcx_route {
     MCX_ROUTE_SAM = 8,     /* the SAM text was made on the device */
     MCX_ROUTE_BGZF = 16,   /* ... and compressed to BGZF blocks there */
     MCX_ROUTE_BAM = 32,    /* ... as BAM records, not text */
-    MCX_ROUTE_SORT = 64    /* ... sorted by coordinate and merged on the device */
+    MCX_ROUTE_SORT = 64,   /* ... sorted by coordinate and merged on the device */
+    MCX_ROUTE_INDEX = 128  /* ... and indexed there: the .bai is made of what the merge's chunks say of their records */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 /* What the context's last mcx_map_files* call with MCX_SAM_SORT did: runs, chunks of the merge, slices, slices that start inside a BGZF block, bytes read back from
  * the temporary file, and how many of those were read twice (the blocks at slice borders).  All 0 after a sorted run that failed. */
 int mcx_files_sort_stats(mcx_ctx *, uint64_t stats[6]);
+/* What the context's last mcx_map_files* call with MCX_SAM_INDEX wrote: stretches (maximal runs of records with one contig and bin, after joining across the
+ * merge's chunks), bins written (the pseudo-bins included), linear-index entries, and the .bai file's bytes.  All 0 after an indexed run that failed. */
+int mcx_files_index_stats(mcx_ctx *, uint64_t stats[4]);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,7 @@ SYMBOLS = [
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
     "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header", "mcx_bam_sort_dev", "mcx_bam_sort_last_ms", "mcx_bam_header_sorted", "mcx_files_sort_stats",
+    "mcx_bam_index_dev", "mcx_bam_index_last_ms", "mcx_bgzf_deflate_blocks", "mcx_files_index_stats",
     "mcx_pass_last_shape",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
@@ -266,11 +267,21 @@ ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 ROUTE_BGZF = 16
 ROUTE_BAM = 32
 ROUTE_SORT = 64
+ROUTE_INDEX = 128
+SAM_INDEX = 16  # (mcx_sam_bits, below)
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
-SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam)
+SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam); SAM_INDEX = 16 above
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
+
+
+class BaiRun(C.Structure):
+    """mcx_bai_run: a stretch of records with one (contig, bin) — the virtual offset of its first record and its records without / with flag bit 4"""
+    _fields_ = [("ref_id", C.c_int32), ("bin", C.c_uint32), ("u", C.c_uint64), ("n_mapped", C.c_uint32), ("n_unmapped", C.c_uint32)]
+
+
+BAI_RUN_DTYPE = np.dtype([("ref_id", "<i4"), ("bin", "<u4"), ("u", "<u8"), ("n_mapped", "<u4"), ("n_unmapped", "<u4")])
 
 
 class FastqIn(C.Structure):
@@ -474,6 +485,15 @@ def lib() -> C.CDLL:
     L.mcx_bam_header_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mcx_files_sort_stats.restype = C.c_int
     L.mcx_files_sort_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_bam_index_dev.restype = C.c_int
+    L.mcx_bam_index_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                    C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_bam_index_last_ms.restype = C.c_int
+    L.mcx_bam_index_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_files_index_stats.restype = C.c_int
+    L.mcx_files_index_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_bgzf_deflate_blocks.restype = C.c_int
+    L.mcx_bgzf_deflate_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.mcx_bam_last_ms.restype = C.c_int
     L.mcx_bam_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_inflater_create.restype = C.c_int
@@ -672,7 +692,8 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False) -> dict:
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
+                  index: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -687,13 +708,15 @@ class Mapper:
         file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``bam`` = -bam: ``sam`` is written as BAM — the records made on the device, framed by the same BGZF path (implies both;
         unsorted, no index; not sharded).  ``sort`` = -sort, only with ``bam``: the file is coordinate-sorted (samtools sort's order, ties in input order) — every part's records sorted
         on the device into a run of a temporary file beside ``sam`` (removed again), the runs merged chunk by chunk on the device behind the last batch; ERR_UNSUPPORTED without ``bam``,
-        with ``append_sam`` or sharded; ``sort_stats()`` says what the merge did.  ``last_route()`` says which stages ran on the device."""
+        with ``append_sam`` or sharded; ``sort_stats()`` says what the merge did.  ``index`` = -index, only with ``sort``: ``sam`` + ".bai" is written as well (what samtools index makes of the file), built on the
+        device from the merge's chunks and written once the BAM file is complete; ERR_UNSUPPORTED without ``sort``, for ``sam`` "-" and for a contig longer than 2^29; ``index_stats()``
+        says what was written.  ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -770,6 +793,38 @@ class Mapper:
         v = (C.c_uint64 * 6)()
         _check(lib().mcx_files_sort_stats(self._h, v), "mcx_files_sort_stats")
         return dict(zip(("runs", "chunks", "slices", "slices_inside_a_block", "bytes_read", "bytes_read_twice"), (int(x) for x in v)))
+
+    def index_stats(self) -> dict:
+        """mcx_files_index_stats: what the last map_files(index=True) wrote — stretches, bins, linear-index entries, the .bai file's bytes (all 0 after a run that failed)"""
+        v = (C.c_uint64 * 4)()
+        _check(lib().mcx_files_index_stats(self._h, v), "mcx_files_index_stats")
+        return dict(zip(("stretches", "bins", "intervals", "bytes"), (int(x) for x in v)))
+
+    def bam_index(self, recs, rec_off, block: int, block_coff, lin, lin_base, runs=None):
+        """mcx_bam_index_dev over torch tensors on the mapper's device: ``recs`` uint8 — coordinate-sorted BAM records back to back —, ``rec_off`` 64-bit [n + 1], their
+        offsets from 0 to recs.numel(); ``block`` the bytes of text a BGZF block took and ``block_coff`` 64-bit [n_blocks + 1] where each block lies in the file;
+        ``lin`` 64-bit, the windows' table (all-ones before the first call; updated in place), and ``lin_base`` 64-bit [n_ref + 1], where each contig's windows begin
+        in it.  Returns the stretches as a numpy array of BAI_RUN_DTYPE; ``runs``: a uint8 tensor of 24 bytes a stretch to take them (ERR_CAPACITY when it is short;
+        default: as many as there are records)."""
+        import torch
+        for t in (rec_off, block_coff, lin, lin_base):
+            assert t.element_size() == 8 and t.is_contiguous(), "offsets and tables: 64-bit tensors"
+        assert recs.dtype == torch.uint8 and recs.is_contiguous()
+        n = max(0, rec_off.numel() - 1)
+        if runs is None:
+            runs = torch.zeros(24 * max(n, 1), dtype=torch.uint8, device=recs.device)
+        assert runs.dtype == torch.uint8 and runs.is_contiguous()
+        torch.cuda.synchronize()
+        n_runs = C.c_uint64()
+        _check(lib().mcx_bam_index_dev(self._h, recs.data_ptr() if recs.numel() else None, recs.numel(), rec_off.data_ptr(), n, block, block_coff.data_ptr(), max(0, block_coff.numel() - 1),
+                                       lin.data_ptr(), lin_base.data_ptr(), max(0, lin_base.numel() - 1), runs.data_ptr(), runs.numel() // 24, C.byref(n_runs)), "mcx_bam_index_dev")
+        return runs[:24 * n_runs.value].cpu().numpy().view(BAI_RUN_DTYPE).copy()
+
+    def bam_index_last_ms(self) -> Tuple[float, float, float]:
+        """the last mcx_bam_index_dev's device times in ms: records, stretches, windows"""
+        ms = (C.c_float * 3)()
+        _check(lib().mcx_bam_index_last_ms(self._h, ms), "mcx_bam_index_last_ms")
+        return tuple(float(x) for x in ms)
 
     def bam_sort(self, recs, grp_off, keys=None, lens=None, out=None):
         """mcx_bam_sort_dev over torch tensors on the mapper's device: ``recs`` uint8 — whole BAM records back to back —, ``grp_off`` int64 / uint64 [n_groups + 1], the
@@ -1220,6 +1275,13 @@ class Deflater:
         n = C.c_uint64()
         _check(lib().mcx_bgzf_deflate(self._h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, out.size, C.byref(n)), "mcx_bgzf_deflate")
         return out[:n.value].tobytes()
+
+    def blocks(self) -> Tuple[int, int]:
+        """mcx_bgzf_deflate_blocks: (a device pointer to n_blocks + 1 uint64 — where each block of the last deflate_dev begins in its output, the last entry its size —,
+        n_blocks); the array is the deflater's and holds until its next call"""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mcx_bgzf_deflate_blocks(self._h, C.byref(p), C.byref(n)), "mcx_bgzf_deflate_blocks")
+        return int(p.value or 0), int(n.value)
 
     def last_ms(self) -> float:
         """the last deflate_dev's kernels, in ms by events on the deflater's stream"""

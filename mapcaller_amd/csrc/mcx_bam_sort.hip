@@ -331,9 +331,10 @@ int mcx_bam_sort_part(mcx_ctx *c, uint32_t n_reads, uint64_t n_bytes, mcx_sort_s
 // The merge's chunk: the covering blocks of its slices (src: page-locked, src_bytes with 8 bytes of slack behind the last member) are inflated into HBM in one
 // row (members: dst_off in that row, text_bytes of it), the records — lens[n_records] in (run, index) order; slice k's start at record slice_first[k], byte
 // slice_base[k] of the row — are sorted by the core, deflated, and their blocks brought to (*h_out)[0 .. *n_out), a page-locked buffer that grows as needed.
+// bai (-index; null: none): the chunk's blocks will lie at byte file_at of the file, and its records are indexed before they leave HBM (mcx_bai.hip).
 int mcx_bam_sort_chunk(mcx_ctx *c, mcx_inflater *inf, mcx_deflater *def, uint32_t block, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n_members,
                        uint64_t text_bytes, const uint32_t *lens, uint64_t n_records, const uint64_t *slice_first, const uint64_t *slice_base, uint32_t n_slices, uint64_t rec_bytes,
-                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4])
+                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], mcx_bai_sink *bai, uint64_t file_at)
 {
     *n_out = 0;
     if (n_records == 0) return 0;
@@ -394,6 +395,12 @@ int mcx_bam_sort_chunk(mcx_ctx *c, mcx_inflater *inf, mcx_deflater *def, uint32_
     t0 = now();
     uint64_t made = 0;
     if ((rc = mcx_bgzf_deflate_dev(def, b.d_sorted, rec_bytes, st->d_bgzf, st->cap_bgzf, &made))) return rc;
+    // -index: the sorted records are still there, their destination offsets are the scan's, and the deflater knows where every block went
+    if (bai) {
+        const auto ti = now();
+        if ((rc = mcx_bai_chunk(c, bai, b.d_sorted, rec_bytes, b.d_dst_off, n, block, def, file_at))) return rc;
+        t0 += now() - ti; // (the sink keeps its own time)
+    }
     if (made > *h_out_cap) {
         mcx_pinned_free(*h_out);
         *h_out_cap = 0;

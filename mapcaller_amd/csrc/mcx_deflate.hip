@@ -53,8 +53,9 @@ __global__ void __launch_bounds__(64 * kDefWaves) k_deflate(const uint8_t *__res
     if (lane == 0) { meta[i].payload = payload; meta[i].crc = crc; }
 }
 
-// meta[i].at = *total + the sizes of the members before i; *total += all of them
-__global__ void __launch_bounds__(1024) k_places(Meta *__restrict__ meta, uint32_t n_blocks, uint64_t *__restrict__ total)
+// meta[i].at = *total + the sizes of the members before i; *total += all of them.  block_at (may be null): the same places, kept for the whole call —
+// entry i of this launch's part, and behind the launch's last block the new total (the next launch begins there and writes the same value)
+__global__ void __launch_bounds__(1024) k_places(Meta *__restrict__ meta, uint32_t n_blocks, uint64_t *__restrict__ total, uint64_t *__restrict__ block_at)
 {
     __shared__ uint64_t part[1024];
     const uint32_t t = threadIdx.x, per = (n_blocks + 1023) / 1024;
@@ -70,9 +71,9 @@ __global__ void __launch_bounds__(1024) k_places(Meta *__restrict__ meta, uint32
         __syncthreads();
     }
     uint64_t at = *total + part[t] - sum;
-    for (uint32_t i = lo; i < hi; i++) { meta[i].at = at; at += meta[i].payload + mcx::def::kMemberExtra; }
+    for (uint32_t i = lo; i < hi; i++) { meta[i].at = at; if (block_at) block_at[i] = at; at += meta[i].payload + mcx::def::kMemberExtra; }
     __syncthreads(); // (every thread has read *total)
-    if (t == 1023) *total += part[1023];
+    if (t == 1023) { if (block_at) block_at[n_blocks] = at; *total += part[1023]; }
 }
 
 __global__ void __launch_bounds__(256) k_gather(const uint8_t *__restrict__ slots, uint32_t slot_bytes, const Meta *__restrict__ meta, uint32_t n_blocks, uint32_t block, uint64_t text_bytes,
@@ -99,6 +100,7 @@ struct mcx_deflater {
     uint64_t max_text = 0;                                 // per launch of the host form
     uint8_t *d_slots = nullptr; uint64_t cap_slots = 0;    // the scratch: a slot per block of a launch
     Meta *d_meta = nullptr; uint64_t cap_meta = 0;
+    uint64_t *d_block_at = nullptr; uint64_t cap_block_at = 0, n_block_at = 0; // where the blocks of the last mcx_bgzf_deflate_dev begin, over all its launches
     uint64_t *d_total = nullptr, *h_total = nullptr;
     uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr; uint64_t cap_in = 0, cap_out = 0; // the host form's staging
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -118,8 +120,9 @@ int grow_dev(mcx_deflater *f, void **p, uint64_t *cap, uint64_t want, const char
     return 0;
 }
 
-// the launches of one call: text in HBM to blocks in HBM, *f->d_total the bytes made; nothing is waited for
-int queue(mcx_deflater *f, const uint8_t *d_text, uint64_t text_bytes, uint8_t *d_out, uint64_t out_cap)
+// the launches of one call: text in HBM to blocks in HBM, *f->d_total the bytes made; nothing is waited for.  keep_places: the blocks' places stay in
+// f->d_block_at for mcx_bgzf_deflate_blocks (d_meta is a launch's and overwritten by the next)
+int queue(mcx_deflater *f, const uint8_t *d_text, uint64_t text_bytes, uint8_t *d_out, uint64_t out_cap, bool keep_places)
 {
     const uint32_t block = f->block, slot_bytes = mcx::def::slot_bytes_of(block);
     const uint64_t per_launch = std::max<uint64_t>(1, std::min<uint64_t>(kLaunchText / block, kLaunchBlocks));
@@ -128,12 +131,19 @@ int queue(mcx_deflater *f, const uint8_t *d_text, uint64_t text_bytes, uint8_t *
     uint64_t meta_bytes = f->cap_meta * sizeof(Meta);
     if (int rc = grow_dev(f, (void **)&f->d_meta, &meta_bytes, most * sizeof(Meta), "the blocks' sizes")) return rc;
     f->cap_meta = meta_bytes / sizeof(Meta);
+    if (keep_places) {
+        f->n_block_at = 0;
+        uint64_t at_bytes = f->cap_block_at * 8;
+        if (int rc = grow_dev(f, (void **)&f->d_block_at, &at_bytes, (blocks_of(text_bytes, block) + 1) * 8, "the blocks' places")) { f->cap_block_at = 0; return rc; }
+        f->cap_block_at = at_bytes / 8;
+        f->n_block_at = blocks_of(text_bytes, block);
+    }
     HIP_TRY(hipMemsetAsync(f->d_total, 0, 8, f->stream));
     for (uint64_t at = 0; at < text_bytes; at += per_launch * block) {
         const uint64_t bytes = std::min<uint64_t>(text_bytes - at, per_launch * block);
         const uint32_t n = (uint32_t)blocks_of(bytes, block);
         k_deflate<<<(n + kDefWaves - 1) / kDefWaves, 64 * kDefWaves, 0, f->stream>>>(d_text + at, bytes, block, n, f->d_slots, slot_bytes, f->d_meta);
-        k_places<<<1, 1024, 0, f->stream>>>(f->d_meta, n, f->d_total);
+        k_places<<<1, 1024, 0, f->stream>>>(f->d_meta, n, f->d_total, keep_places ? f->d_block_at + at / block : nullptr);
         k_gather<<<n, 256, 0, f->stream>>>(f->d_slots, slot_bytes, f->d_meta, n, block, bytes, d_out, out_cap);
         HIP_TRY(hipGetLastError());
     }
@@ -147,7 +157,7 @@ extern "C" void mcx_deflater_free(mcx_deflater *f)
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    void *d[] = {f->d_slots, f->d_meta, f->d_total, f->d_in, f->d_out};
+    void *d[] = {f->d_slots, f->d_meta, f->d_block_at, f->d_total, f->d_in, f->d_out};
     for (void *p : d) if (p) (void)hipFree(p);
     mcx_pinned_free(f->h_total); mcx_pinned_free(f->h_in); mcx_pinned_free(f->h_out);
     for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
@@ -201,18 +211,27 @@ extern "C" int mcx_bgzf_deflate_dev(mcx_deflater *f, const uint8_t *d_text, uint
 {
     if (n_out) *n_out = 0;
     if (!f || !n_out) return mcx_set_error(MCX_ERR_ARG, "mcx_bgzf_deflate_dev: null argument");
+    f->n_block_at = 0;
     if (text_bytes == 0) return 0;
     if (!d_text || !d_out) return mcx_set_error(MCX_ERR_ARG, "mcx_bgzf_deflate_dev: null argument");
     if (out_cap < mcx_bgzf_bound(text_bytes, f->block))
         return mcx_set_error(MCX_ERR_CAPACITY, "mcx_bgzf_deflate_dev: the blocks of " + std::to_string(text_bytes) + " bytes of text can take " + std::to_string(mcx_bgzf_bound(text_bytes, f->block)) + " bytes");
     HIP_TRY(hipSetDevice(f->device));
     HIP_TRY(hipEventRecord(f->ev[0], f->stream));
-    if (int rc = queue(f, d_text, text_bytes, d_out, out_cap)) return rc;
+    if (int rc = queue(f, d_text, text_bytes, d_out, out_cap, true)) return rc;
     HIP_TRY(hipEventRecord(f->ev[1], f->stream));
     HIP_TRY(hipMemcpyAsync(f->h_total, f->d_total, 8, hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));
     HIP_TRY(hipEventElapsedTime(&f->last_ms, f->ev[0], f->ev[1]));
     *n_out = *f->h_total;
+    return 0;
+}
+
+extern "C" int mcx_bgzf_deflate_blocks(mcx_deflater *f, const uint64_t **d_block_at, uint64_t *n_blocks)
+{
+    if (!f || !d_block_at || !n_blocks) return mcx_set_error(MCX_ERR_ARG, "mcx_bgzf_deflate_blocks: null argument");
+    *n_blocks = f->n_block_at;
+    *d_block_at = f->n_block_at ? f->d_block_at : nullptr;
     return 0;
 }
 
@@ -253,7 +272,7 @@ extern "C" int mcx_bgzf_deflate(mcx_deflater *f, const uint8_t *text, uint64_t t
         const uint64_t bytes = std::min(step, text_bytes - at);
         memcpy(f->h_in, text + at, bytes);
         HIP_TRY(hipMemcpyAsync(f->d_in, f->h_in, bytes, hipMemcpyHostToDevice, f->stream));
-        if (int rc = queue(f, f->d_in, bytes, f->d_out, f->cap_out)) return rc;
+        if (int rc = queue(f, f->d_in, bytes, f->d_out, f->cap_out, false)) return rc;
         HIP_TRY(hipMemcpyAsync(f->h_total, f->d_total, 8, hipMemcpyDeviceToHost, f->stream));
         HIP_TRY(hipStreamSynchronize(f->stream));
         const uint64_t got = *f->h_total;

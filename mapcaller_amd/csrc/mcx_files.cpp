@@ -45,7 +45,7 @@ extern "C" void mcx_file_opts_default(mcx_file_opts *o) { memset(o, 0, sizeof *o
 // last call ran on the device
 namespace {
 typedef std::unique_ptr<Batch> BatchPtr;
-struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; uint64_t sort_stats[6] = {0, 0, 0, 0, 0, 0}; };
+struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; uint64_t sort_stats[6] = {0, 0, 0, 0, 0, 0}; uint64_t index_stats[4] = {0, 0, 0, 0}; };
 Kept *kept_of(mcx_ctx *c)
 {
     void **slot = mcx_ctx_files_slot(c, [](void *p) { delete (Kept *)p; });
@@ -66,6 +66,13 @@ extern "C" int mcx_files_sort_stats(mcx_ctx *c, uint64_t stats[6])
 {
     if (!c || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_files_sort_stats: null argument");
     memcpy(stats, kept_of(c)->sort_stats, sizeof kept_of(c)->sort_stats);
+    return 0;
+}
+
+extern "C" int mcx_files_index_stats(mcx_ctx *c, uint64_t stats[4])
+{
+    if (!c || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_files_index_stats: null argument");
+    memcpy(stats, kept_of(c)->index_stats, sizeof kept_of(c)->index_stats);
     return 0;
 }
 
@@ -186,6 +193,7 @@ struct Run {
     const bool bgzf;            // ... and compressed there: the file is BGZF (mcx_deflate.hip)
     const bool bam;             // ... of BAM records, not text (mcx_bam.hip)
     const bool sort;            // ... in coordinate order: sorted runs to a temporary file, merged behind the last batch (mcx_bam_sort.hip, mcx_sort_plan.h)
+    const bool index;           // ... with its .bai beside it, made of what the merge's chunks say of their records (mcx_bai.hip, mcx_bai.h)
     Timing t;
     Shards sh;
     Pool pool;                  // parse + pack
@@ -222,6 +230,10 @@ struct Run {
     uint64_t tmp_at = 0;               // where the batch in the mapper's hands will lie in the temporary file
     double sort_secs[5] = {0, 0, 0, 0, 0}; // the merge: read, copy in, inflate, sort, deflate + copy out
     double merge_seconds = 0;
+    // -index: the stretches and windows of the merge's chunks, and — once the EOF block is written — the bytes of <sam_path>.bai, which close_output writes
+    mcx_bai_sink bai;
+    std::vector<uint8_t> bai_bytes;
+    uint64_t indexed_records = 0;
     ~Run() { drop_tmp(); }
     uint8_t bgzf_eof[28];
     std::deque<BatchPtr> waiting; // (the writer's; sharded) formatted, their place in the file not known yet
@@ -260,7 +272,7 @@ struct Run {
           shard_count(o.shard_count > 1 ? (uint64_t)o.shard_count : 1), shard_rank(shard_count > 1 ? (uint64_t)o.shard_rank : 0), sharded(shard_count > 1),
           batch_reads(std::max<uint64_t>(kReadChunkSize, mcx_ctx_max_reads(ctx) / kReadChunkSize * kReadChunkSize)), per_file((uint32_t)(two ? batch_reads / 2 : batch_reads)),
           threads(o.host_threads > 0 ? o.host_threads : (int)std::min<unsigned>(64, std::max<unsigned>(1, mcx_usable_cpus() * 3 / 4 / (unsigned)shard_count))),
-          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), sort((o.device_sam & MCX_SAM_SORT) != 0 && bam), pool(threads), fpool(threads),
+          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), sort((o.device_sam & MCX_SAM_SORT) != 0 && bam), index((o.device_sam & MCX_SAM_INDEX) != 0 && sort), pool(threads), fpool(threads),
           n_objects(sharded ? 16 : 12), parsed(2), mapped(2), formatted(2), spare((size_t)n_objects),
           profile(mcx_ctx_has_profile(ctx)), multi(mcx_ctx_multi(ctx))
     {
@@ -292,7 +304,7 @@ struct Run {
         if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
-        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u);
+        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u) | (index ? (uint32_t)MCX_ROUTE_INDEX : 0u);
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
@@ -455,7 +467,24 @@ struct Run {
     {
         if (sam_fd >= 0 && !sam_stream) { if (close(sam_fd) != 0 && write_rc.load() == 0) write_rc.store(MCX_ERR_IO); }
         if (rc == 0 && write_rc.load()) rc = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + (sam_path ? sam_path : ""));
+        if (index) write_index();
         return rc;
+    }
+    // -index: the BAM file is complete and closed — its index goes beside it, whole (written under another name and renamed) or not at all; after a run that
+    // failed, an index an earlier run left there would describe another file: it goes
+    void write_index()
+    {
+        const std::string path = std::string(sam_path) + ".bai", part = path + ".tmp";
+        memset(kept->index_stats, 0, sizeof kept->index_stats);
+        if (rc == 0) {
+            const int fd = ::open(part.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            bool ok = fd >= 0 && write_all(fd, (const char *)bai_bytes.data(), bai_bytes.size(), 0, false);
+            if (fd >= 0 && close(fd) != 0) ok = false;
+            if (ok && rename(part.c_str(), path.c_str()) != 0) ok = false;
+            if (!ok) { unlink(part.c_str()); rc = mcx_set_error(MCX_ERR_IO, "-index: cannot write " + path); }
+        }
+        if (rc) { unlink(path.c_str()); return; }
+        kept->index_stats[0] = bai.stats.stretches; kept->index_stats[1] = bai.stats.bins; kept->index_stats[2] = bai.stats.intervals; kept->index_stats[3] = bai.stats.bytes;
     }
 
     // ---- stage 1: parse + pack ---------------------------------------------------------------------------------------
@@ -1184,8 +1213,9 @@ struct Run {
             if (!write_all(fd, blocks.data(), (size_t)made, place, stream)) return mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
             place += made;
         }
+        if (index && (e = mcx_bai_begin(c, &bai))) { mcx_bai_free(c, &bai); return e; }
         mcx_inflater *inf = nullptr;
-        if (mcx_inflater_create_dev(idx->device, 0, 1u << 16, &inf) != 0) return mcx_set_error(MCX_ERR_DEVICE, std::string("-sort: ") + mcx_last_error());
+        if (mcx_inflater_create_dev(idx->device, 0, 1u << 16, &inf) != 0) { if (index) mcx_bai_free(c, &bai); return mcx_set_error(MCX_ERR_DEVICE, std::string("-sort: ") + mcx_last_error()); }
         uint8_t *h_src = nullptr, *h_out = nullptr;
         uint64_t h_src_cap = 0, h_out_cap = 0;
         std::vector<mcx_deflate_member> members;
@@ -1235,14 +1265,19 @@ struct Run {
             memset(h_src + so, 0, 8);
             uint64_t made = 0;
             e = mcx_bam_sort_chunk(c, inf, zs.deflater, zs.block, h_src, so + 8, members.data(), (uint32_t)members.size(), to, lens.data(), lens.size(), first.data(), base.data(), (uint32_t)first.size(),
-                                   ch.bytes, &h_out, &h_out_cap, &made, sort_secs + 1);
+                                   ch.bytes, &h_out, &h_out_cap, &made, sort_secs + 1, index ? &bai : nullptr, place);
             if (e) break;
+            indexed_records += lens.size();
             const Tick t1 = now();
             if (!write_all(fd, (const char *)h_out, (size_t)made, place, stream)) e = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
             t.write += secs(t1, now());
             place += made;
         }
         if (e == 0 && !write_all(fd, (const char *)bgzf_eof, 28, place, stream)) e = mcx_set_error(MCX_ERR_IO, std::string("cannot write ") + sam_path);
+        if (index) { // the EOF block's place ends the last chunk of the index
+            if (e == 0) e = mcx_bai_end(c, &bai, place, &bai_bytes);
+            mcx_bai_free(c, &bai);
+        }
         mcx_pinned_free(h_src); mcx_pinned_free(h_out);
         mcx_inflater_free(inf);
         merge_seconds = secs(t_begin, now());
@@ -1276,6 +1311,9 @@ struct Run {
         if (sort) fprintf(stderr, "[mcx_map_files] sort: %llu runs (%.3f s of the mapper's time), %llu chunks of %llu slices (%llu start inside a block); the merge %.3f s: read %.3f, copy in %.3f, inflate %.3f, sort %.3f, deflate + copy out %.3f; %llu bytes read back, %llu of them twice\n",
                           (unsigned long long)kept->sort_stats[0], sink.run_seconds, (unsigned long long)kept->sort_stats[1], (unsigned long long)kept->sort_stats[2], (unsigned long long)kept->sort_stats[3], merge_seconds,
                           sort_secs[0], sort_secs[1], sort_secs[2], sort_secs[3], sort_secs[4], (unsigned long long)kept->sort_stats[4], (unsigned long long)kept->sort_stats[5]);
+        if (index) fprintf(stderr, "[mcx_map_files] index: %llu records in %llu stretches, %llu bins and %llu linear entries written, %llu bytes; %.3f s of the merge (on the device: records %.3f, stretches %.3f, windows %.3f ms)\n",
+                           (unsigned long long)indexed_records, (unsigned long long)bai.stats.stretches, (unsigned long long)bai.stats.bins, (unsigned long long)bai.stats.intervals, (unsigned long long)bai.stats.bytes,
+                           bai.seconds, bai.ms[0], bai.ms[1], bai.ms[2]);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");
         fprintf(stderr, "[mcx_map_files] waits: reader for room behind it %.3f | mapper for a parsed batch %.3f, for copies out %.3f | formatter for the writer %.3f || mapper's calls: submit %.3f, next %.3f, map_batch_dev %.3f, mapped %.3f\n", t.p_push, t.m_take, t.m_collect, t.f_push, t.m_submit, t.m_in, t.m_dev, t.m_out);
@@ -1300,6 +1338,14 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sorted file cannot be appended to (-sort with append_sam): map the libraries in one run, or merge the sorted files");
     if ((opt.device_sam & MCX_SAM_SORT) && opt.shard_count > 1)
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write a sorted BAM file (-sort with -gpus N / -devices): map on one GPU");
+    if ((opt.device_sam & MCX_SAM_INDEX) && !(opt.device_sam & MCX_SAM_SORT))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index writes the .bai of a coordinate-sorted BAM file and needs -sort (MCX_SAM_INDEX without MCX_SAM_SORT); an unsorted file has no index");
+    if ((opt.device_sam & MCX_SAM_INDEX) && sam_path && strcmp(sam_path, "-") == 0)
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index writes <file>.bai beside the BAM file: a file that goes to stdout has no name to put it beside");
+    if (opt.device_sam & MCX_SAM_INDEX)
+        for (int32_t len : mcx_ctx_index(c)->host.chr_len)
+            if ((int64_t)len > (1ll << 29))
+                return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index: a contig is longer than 2^29 bases, which a .bai cannot address (a .csi could: not offered)");
     if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_BGZF))
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF or as BAM (-bgzf / -bam with -gpus N / -devices): map on one GPU, or without them");
     Run run(c, fq1, fq2, opt, sam_path, stats);

@@ -5,6 +5,7 @@
 #include "mcx_host.h"
 #include "mcx_build.h"
 #include "../../include/mcx.h"
+#include "mcx_bai.h"
 #include <atomic>
 #include <vector>
 
@@ -57,7 +58,25 @@ int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t
 int mcx_bam_sort_part(mcx_ctx *, uint32_t n_reads, uint64_t n_bytes, mcx_sort_sink *sink, const uint8_t **d_sorted);
 int mcx_bam_sort_chunk(mcx_ctx *, mcx_inflater *, mcx_deflater *, uint32_t block, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n_members,
                        uint64_t text_bytes, const uint32_t *lens, uint64_t n_records, const uint64_t *slice_first, const uint64_t *slice_base, uint32_t n_slices, uint64_t rec_bytes,
-                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4]);
+                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], struct mcx_bai_sink *bai, uint64_t file_at);
+// -index (mcx_bai.hip): the index of the file the merge writes.  begin: the windows' table of the context's contigs in HBM, all-ones.  chunk: the records just
+// deflated (d_rec_off: n + 1 entries; the deflater still knows where their blocks lie) whose blocks will go to byte file_at of the file: their stretches join the
+// accumulator, their windows the table.  end: the table comes back and the file's bytes are made, eof_at the byte the EOF block is written at.  The sink's
+// device arrays go with mcx_bai_free.
+struct mcx_bai_sink {
+    mcx::bai::Index acc;
+    std::vector<uint64_t> lin_base;                       // n_ref + 1: where each contig's windows begin in the table
+    uint64_t *d_lin = nullptr, *d_lin_base = nullptr;
+    mcx_bai_run *d_runs = nullptr; uint64_t cap_runs = 0;
+    std::vector<mcx_bai_run> h_runs;
+    mcx::bai::Stats stats;
+    double seconds = 0;                                   // of the calling thread, all three
+    float ms[3] = {0, 0, 0};                              // the device's, summed over the chunks: records, stretches, windows
+};
+int mcx_bai_begin(mcx_ctx *, mcx_bai_sink *);
+int mcx_bai_chunk(mcx_ctx *, mcx_bai_sink *, const uint8_t *d_recs, uint64_t n_bytes, const uint64_t *d_rec_off, uint32_t n_records, uint32_t block, mcx_deflater *, uint64_t file_at);
+int mcx_bai_end(mcx_ctx *, mcx_bai_sink *, uint64_t eof_at, std::vector<uint8_t> *bytes);
+void mcx_bai_free(mcx_ctx *, mcx_bai_sink *);
 // -gpu_inflate (mcx_inflate.hip): the host form of mcx_inflate in two halves, so that the reader stages a stretch's bytes while the stretch before is on
 // the device — begin packs the members' bytes (src_off into src) into page-locked staging and queues copy in, kernel and copy out; end waits for the oldest
 // begin and hands the text to dst + each member's dst_off (0, or MCX_ERR_IO when a member failed).  At most two begins outstanding; caps: what one holds.

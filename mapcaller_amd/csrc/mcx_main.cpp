@@ -58,7 +58,9 @@ static void usage(const char *prog)
             "                       deflated on the GPU; unsorted, no index; not with -gpus N / -devices\n"
             "         -sort         with -bam: a coordinate-sorted BAM file (samtools sort's order, ties in input order), sorted and merged on the GPU; needs temporary\n"
             "                       disk of the file's size beside it (out.bam.sort.tmp; for stdout in $TMPDIR) and 12 bytes of host memory a record;\n"
-            "                       one library (one -f / -f2 pair); not with -gpus N / -devices; no index is written (samtools index takes the file)\n"
+            "                       one library (one -f / -f2 pair); not with -gpus N / -devices; -index writes its .bai\n"
+            "         -index        with -bam -sort: write the file's index beside it (out.bam.bai, what samtools index makes: format BAI), built on the GPU while the\n"
+            "                       merge writes the file; not to stdout; contigs up to 2^29 bases (no .csi)\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -110,6 +112,7 @@ int main(int argc, char **argv)
     bool multi = false;   // -m: a SAM line for every alignment with the best score
     bool bam = false;     // -bam: the output file holds BAM records
     bool want_sort = false; // -sort: ... in coordinate order
+    bool want_index = false; // -index: ... with its .bai beside it
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -167,6 +170,7 @@ int main(int argc, char **argv)
         else if (p == "-gpu_sam") fo.device_sam |= MCX_SAM_DEVICE;
         else if (p == "-bgzf") fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF;
         else if (p == "-sort") want_sort = true;
+        else if (p == "-index") want_index = true;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
@@ -180,6 +184,9 @@ int main(int argc, char **argv)
     if (want_sort && f1.size() > 1) { fprintf(stderr, "Error! -sort writes one sorted file from one library: a sorted file cannot be appended to (give one -f / -f2 pair)\n"); return 1; }
     if (want_sort && n_gpus > 1) { fprintf(stderr, "Error! -sort sorts and merges on one GPU: it cannot be combined with -gpus N / -devices\n"); return 1; }
     if (want_sort) fo.device_sam |= MCX_SAM_SORT;
+    if (want_index && !want_sort) { fprintf(stderr, "Error! -index writes the .bai of a coordinate-sorted BAM file: it needs -bam -sort (an unsorted file has no index)\n"); return 1; }
+    if (want_index && sam == "-") { fprintf(stderr, "Error! -index writes <file>.bai beside the BAM file: a file that goes to stdout has no name to put it beside\n"); return 1; }
+    if (want_index) fo.device_sam |= MCX_SAM_INDEX;
     if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the

@@ -29,6 +29,22 @@ struct SortBufs {
     }
 };
 
+// -index (mcx_bai.hip): per record of a call its (refID, bin), virtual offset, end window (packed with the contig, and its running maximum), first window, head
+// and mapped flags (and their running sums); per stretch its first record; hipcub's scratch
+struct BaiBufs {
+    uint64_t *d_tb = nullptr, *d_u = nullptr, *d_wpack = nullptr, *d_wmax = nullptr, *d_hm = nullptr, *d_hs = nullptr; uint32_t *d_w0 = nullptr, *d_start = nullptr; uint64_t cap = 0;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;
+    uint32_t *d_error = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float ms[3] = {0, 0, 0}; // the last call's records, stretches, windows
+    ~BaiBufs()
+    {
+        void *p[] = {d_tb, d_u, d_wpack, d_wmax, d_hm, d_hs, d_w0, d_start, d_tmp, d_error};
+        for (void *q : p) if (q) (void)hipFree(q);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 // the contigs' names (once), the lengths and offsets of a batch, and — for the file front end — the names, qualities and text (or records) of a batch part in HBM
 struct SamState {
     char *d_cn_text = nullptr; uint32_t *d_cn_off = nullptr;
@@ -41,6 +57,7 @@ struct SamState {
     uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
     uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
     SortBufs sort;
+    BaiBufs bai;
     ~SamState()
     {
         void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf};

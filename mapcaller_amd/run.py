@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MapCaller's command line on one or several MI355X of a node.
 
-    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort]] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
+    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort [-index]]] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 -m mapcaller_amd.run -i idx -f r1.fq -f2 r2.fq -sam out.sam -vcf out.vcf
 
 One process per GPU.  The input stream is cut into batches that are dealt to the ranks in turn
@@ -43,7 +43,8 @@ def parse(argv):
     ap.add_argument("-sam", default=None, action=_Output)
     ap.add_argument("-bam", dest="sam", action=_Output, metavar="FILE", help="BAM output instead of -sam (the later of the two counts): records made and BGZF blocks deflated on the GPU; unsorted, no index; one process only")
     ap.set_defaults(bam=False)
-    ap.add_argument("-sort", dest="sort", action="store_true", help="with -bam: a coordinate-sorted BAM file, sorted and merged on the GPU (temporary disk of the file's size beside it, 12 bytes of host memory a record; one library, one process; no index)")
+    ap.add_argument("-sort", dest="sort", action="store_true", help="with -bam: a coordinate-sorted BAM file, sorted and merged on the GPU (temporary disk of the file's size beside it, 12 bytes of host memory a record; one library, one process; -index writes its .bai)")
+    ap.add_argument("-index", dest="bai", action="store_true", help="with -bam -sort: write the file's index beside it (FILE.bai, what samtools index makes), built on the GPU while the merge writes the file")
     ap.add_argument("-vcf", default="output.vcf")
     ap.add_argument("-no_vcf", action="store_true")
     ap.add_argument("-m", dest="multi", action="store_true", help="a SAM line for every alignment with the best score")
@@ -105,6 +106,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.sort and not a.bam:
         sys.exit("-sort puts BAM records into coordinate order: it needs -bam (SAM text is not sorted)")
+    if a.bai and not a.sort:
+        sys.exit("-index writes the .bai of a coordinate-sorted BAM file: it needs -bam -sort")
     if a.sort and world > 1:
         sys.exit("-sort sorts and merges on one GPU: it cannot be combined with several ranks")
     if a.bam and world > 1:
@@ -138,7 +141,7 @@ def main(argv=None):
         f2 = a.f2[k] if a.f2 else None
         # (the ranks write into the one SAM file, every batch's lines at their final place: mcx_map_files_ex)
         st = mapper.map_files(f1, f2, a.sam or None, interleaved=a.interleaved, threads=a.threads,
-                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort)
+                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort, index=a.bai)
         for key in totals:
             totals[key] += st[key]
         if td:
