@@ -521,6 +521,31 @@ int mcx_bam_index_dev(mcx_ctx *, const uint8_t *d_recs, uint64_t n_bytes, const 
                       mcx_bai_run *d_runs, uint64_t runs_cap, uint64_t *n_runs);
 /* the last call's device times in ms: records (fields, CIGAR walk, offsets, order), stretches (flags, scans, the list), windows (running maximum, the table) */
 int mcx_bam_index_last_ms(mcx_ctx *, float ms[3]);
+/* Duplicate marking (mapcaller-mi355x -markdup), in three operations.  The rule (mcx_markdup.h holds its arithmetic for the device and the host):
+ *   a read is a group of mcx_bam_format_dev's rec_off and its record the group's first; it is placed when it has a record and flag bit 4 is clear.
+ *   end(record) = (refID, u5, reverse), u5 the unclipped 5' position: forward pos - leading S and H, reverse pos + reflen - 1 + trailing S and H (reflen over M, D, N,
+ *   = and X); score(record) = the sum of the QUAL bytes that are 15 or more (0xff counts as 0).  A packed end is refID << 40 | (u5 + 2^38) << 1 | reverse, for
+ *   0 <= refID < 2^24 - 1, |u5| < 2^38 and fewer than 2^23 bases; all-ones is no end.
+ *   Units, numbered in input order.  Paired: reads 2i and 2i + 1 are unit i — both placed: a pair unit, its key the two ends in ascending order, its score the sum of
+ *   both; one placed: a fragment unit, key its end, score its own; none placed: no unit (kind 0).  Single-end: read i is unit i, a fragment unit when placed.
+ *   Among pair units with equal keys the one with the highest score stays, a tie going to the lowest number; the others are duplicates.  A fragment unit is a
+ *   duplicate when a pair unit has one of its two ends equal to the fragment's end; otherwise, among fragments with equal ends, all but the best (as above) are.
+ * mcx_bam_dup_units_dev: d_recs / n_bytes / d_grp_off / n_groups as for mcx_bam_sort_dev (paired: n_groups must be even); d_units receives *n_units = n_groups / 2
+ * (paired) or n_groups entries.  kind: bits 0-1 are 0 none, 1 fragment, 2 pair; bit 2 is set when a paired input's fragment is the second read.  end1 is all-ones
+ * for a fragment, both ends for none.  MCX_ERR_ARG, with nothing written and nothing read outside d_recs[0 .. n_bytes): offsets that do not ascend from 0 to n_bytes,
+ * a block_size below 32, a record that leaves its group or is shorter than its name, CIGAR, SEQ and QUAL — and, said apart, a placed read outside the packing's range.
+ * mcx_dup_resolve_dev: d_dup[u] = 1 when unit u is a duplicate, else 0, for all n_units (device, one byte a unit), by stable radix sorts: no result depends on
+ * anything but the units and their order.  Scratch (56 bytes a unit and the sorts' own) stays with the context; when HBM does not hold it: MCX_ERR_CAPACITY, the
+ * bytes needed in words, nothing written.  kind values other than the above: MCX_ERR_ARG.
+ * mcx_bam_dup_mark_dev: sets flag bit 0x400 — bit 2 of byte 19, a byte store — in every record i (d_rec_off: n_records + 1 entries, device) with d_rec_dup[i] != 0
+ * (device, one byte a record) and touches nothing else.  Offsets that descend, leave n_bytes or leave a record less than 20 bytes: MCX_ERR_ARG, nothing written.
+ * All three run on the context's stream and are waited for. */
+typedef struct mcx_dup_unit { uint64_t end0, end1; uint32_t score, kind; } mcx_dup_unit;
+int mcx_bam_dup_units_dev(mcx_ctx *, const uint8_t *d_recs, uint64_t n_bytes, const uint64_t *d_grp_off, uint32_t n_groups, int paired, mcx_dup_unit *d_units, uint64_t *n_units);
+int mcx_dup_resolve_dev(mcx_ctx *, const mcx_dup_unit *d_units, uint64_t n_units, uint8_t *d_dup);
+int mcx_bam_dup_mark_dev(mcx_ctx *, uint8_t *d_recs, uint64_t n_bytes, const uint64_t *d_rec_off, uint32_t n_records, const uint8_t *d_rec_dup);
+/* the device times in ms of the context's last call of each: units, resolve, mark */
+int mcx_markdup_last_ms(mcx_ctx *, float ms[3]);
 
 /* ---- BGZF input inflated on the device -------------------------------------------------------------
  * bgzip's container is a row of independent gzip members of at most 64 KB of text, each of which says how long it is ('BC' extra
@@ -713,6 +738,14 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * the host keeps 24 bytes a stretch of records with one (contig, bin).  The index is written — under another name, then renamed — once the BAM file is complete
  * and closed, and removed when the call fails; the BAM file's bytes are those of a run without the bit.  MCX_ERR_UNSUPPORTED before anything is opened: the bit
  * without bit 8, sam_path "-" (no name to put the index beside), a contig longer than 2^29 (BAI cannot address it; CSI is not offered).  (route: MCX_ROUTE_INDEX.)
+ * bit 32 (MCX_SAM_MARKDUP; mapcaller-mi355x -markdup; only with bit 8) sets flag bit 0x400 on every record that is a duplicate by the rule at mcx_bam_dup_units_dev;
+ * the file's bytes after gzip -d are those of a run without the bit but for that flag bit, and a function of the input alone.  Before a part is sorted its units are
+ * made from the records in read order (a pair's mates are neighbouring groups: a paired part with an odd number of reads is refused in words) and come back beside
+ * the keys and lengths, with the group every sorted record came from; behind the last batch all units go to HBM once, mcx_dup_resolve_dev decides, and every
+ * chunk of the merge marks its sorted records before they are compressed (-index reads marked records).  Host memory on top of -sort's 12 bytes a record: 4 bytes
+ * a record and 24 bytes a unit (12 a record for pairs) until the resolve, 1 byte a record from there on.  There is no optical-duplicate distance, no library or
+ * read-group distinction (-sort takes one library), and same-strand pairs are not told apart by which mate comes first.  One line on stderr says what was found.
+ * MCX_ERR_UNSUPPORTED before anything is opened: the bit without bit 8; a context with -m (mcx_ctx_set_multi).  (route: MCX_ROUTE_MARKDUP.)
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -732,7 +765,8 @@ enum mcx_sam_bits {
     MCX_SAM_BGZF = 2,   /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
     MCX_SAM_BAM = 4,    /* ... which hold BAM records instead of SAM text (implies both) */
     MCX_SAM_SORT = 8,   /* ... in coordinate order (only with MCX_SAM_BAM) */
-    MCX_SAM_INDEX = 16  /* ... with its .bai written beside it (only with MCX_SAM_SORT) */
+    MCX_SAM_INDEX = 16, /* ... with its .bai written beside it (only with MCX_SAM_SORT) */
+    MCX_SAM_MARKDUP = 32 /* ... and flag bit 0x400 on its duplicate records (only with MCX_SAM_SORT) */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
@@ -746,7 +780,8 @@ enum mcx_route {
     MCX_ROUTE_BGZF = 16,   /* ... and compressed to BGZF blocks there */
     MCX_ROUTE_BAM = 32,    /* ... as BAM records, not text */
     MCX_ROUTE_SORT = 64,   /* ... sorted by coordinate and merged on the device */
-    MCX_ROUTE_INDEX = 128  /* ... and indexed there: the .bai is made of what the merge's chunks say of their records */
+    MCX_ROUTE_INDEX = 128, /* ... and indexed there: the .bai is made of what the merge's chunks say of their records */
+    MCX_ROUTE_MARKDUP = 256 /* ... their duplicates decided and flagged there */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 /* What the context's last mcx_map_files* call with MCX_SAM_SORT did: runs, chunks of the merge, slices, slices that start inside a BGZF block, bytes read back from
@@ -755,6 +790,9 @@ int mcx_files_sort_stats(mcx_ctx *, uint64_t stats[6]);
 /* What the context's last mcx_map_files* call with MCX_SAM_INDEX wrote: stretches (maximal runs of records with one contig and bin, after joining across the
  * merge's chunks), bins written (the pseudo-bins included), linear-index entries, and the .bai file's bytes.  All 0 after an indexed run that failed. */
 int mcx_files_index_stats(mcx_ctx *, uint64_t stats[4]);
+/* What the context's last mcx_map_files* call with MCX_SAM_MARKDUP found: pair units, duplicate pair units, fragment units, duplicate fragment units, groups (keys
+ * that two or more pair units share, plus ends on which a fragment is a duplicate), and the microseconds the units, the resolve and the marks took.  All 0 after a run that failed. */
+int mcx_files_markdup_stats(mcx_ctx *, uint64_t stats[6]);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,7 @@ SYMBOLS = [
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
     "mcx_bam_format_dev", "mcx_bam_format", "mcx_bam_header", "mcx_bam_sort_dev", "mcx_bam_sort_last_ms", "mcx_bam_header_sorted", "mcx_files_sort_stats",
     "mcx_bam_index_dev", "mcx_bam_index_last_ms", "mcx_bgzf_deflate_blocks", "mcx_files_index_stats",
+    "mcx_bam_dup_units_dev", "mcx_dup_resolve_dev", "mcx_bam_dup_mark_dev", "mcx_markdup_last_ms", "mcx_files_markdup_stats",
     "mcx_pass_last_shape",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
@@ -268,6 +269,10 @@ ROUTE_BGZF = 16
 ROUTE_BAM = 32
 ROUTE_SORT = 64
 ROUTE_INDEX = 128
+ROUTE_MARKDUP = 256
+SAM_MARKDUP = 32  # (mcx_sam_bits, below)
+DUP_NONE, DUP_FRAGMENT, DUP_PAIR, DUP_SECOND_MATE = 0, 1, 2, 4  # mcx_dup_unit.kind: bits 0-1 the kind, bit 2 a paired input's fragment is the second read
+DUP_UNIT_DTYPE = np.dtype([("end0", "<u8"), ("end1", "<u8"), ("score", "<u4"), ("kind", "<u4")])  # mcx_dup_unit, 24 bytes
 SAM_INDEX = 16  # (mcx_sam_bits, below)
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
 SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam); SAM_INDEX = 16 above
@@ -490,6 +495,16 @@ def lib() -> C.CDLL:
                                     C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mcx_bam_index_last_ms.restype = C.c_int
     L.mcx_bam_index_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_bam_dup_units_dev.restype = C.c_int
+    L.mcx_bam_dup_units_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_dup_resolve_dev.restype = C.c_int
+    L.mcx_dup_resolve_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.mcx_bam_dup_mark_dev.restype = C.c_int
+    L.mcx_bam_dup_mark_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.mcx_markdup_last_ms.restype = C.c_int
+    L.mcx_markdup_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_files_markdup_stats.restype = C.c_int
+    L.mcx_files_markdup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_files_index_stats.restype = C.c_int
     L.mcx_files_index_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_bgzf_deflate_blocks.restype = C.c_int
@@ -693,7 +708,7 @@ class Mapper:
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
                   device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
-                  index: bool = False) -> dict:
+                  index: bool = False, markdup: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -710,13 +725,15 @@ class Mapper:
         on the device into a run of a temporary file beside ``sam`` (removed again), the runs merged chunk by chunk on the device behind the last batch; ERR_UNSUPPORTED without ``bam``,
         with ``append_sam`` or sharded; ``sort_stats()`` says what the merge did.  ``index`` = -index, only with ``sort``: ``sam`` + ".bai" is written as well (what samtools index makes of the file), built on the
         device from the merge's chunks and written once the BAM file is complete; ERR_UNSUPPORTED without ``sort``, for ``sam`` "-" and for a contig longer than 2^29; ``index_stats()``
-        says what was written.  ``last_route()`` says which stages ran on the device."""
+        says what was written.  ``markdup`` = -markdup, only with ``sort``: flag bit 0x400 on every record that is a duplicate (the rule: mcx.h at mcx_bam_dup_units_dev) — units made per
+        part, resolved once on the device behind the last batch, the bits set in the merge; ERR_UNSUPPORTED without ``sort`` and on a mapper with ``multi``; ``markdup_stats()`` says what was found.
+        ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -799,6 +816,55 @@ class Mapper:
         v = (C.c_uint64 * 4)()
         _check(lib().mcx_files_index_stats(self._h, v), "mcx_files_index_stats")
         return dict(zip(("stretches", "bins", "intervals", "bytes"), (int(x) for x in v)))
+
+    def markdup_stats(self) -> dict:
+        """mcx_files_markdup_stats: what the last map_files(markdup=True) found — pair units, duplicate pair units, fragment units, duplicate fragment units, groups
+        (keys two or more pairs share, plus ends on which a fragment is a duplicate), seconds (all 0 after a run that failed)"""
+        v = (C.c_uint64 * 6)()
+        _check(lib().mcx_files_markdup_stats(self._h, v), "mcx_files_markdup_stats")
+        d = dict(zip(("pairs", "duplicate_pairs", "fragments", "duplicate_fragments", "groups"), (int(x) for x in v)))
+        d["seconds"] = int(v[5]) / 1e6
+        return d
+
+    def bam_dup_units(self, recs, grp_off, paired: bool):
+        """mcx_bam_dup_units_dev over torch tensors on the mapper's device: ``recs`` uint8 — whole BAM records in read order —, ``grp_off`` 64-bit [n_groups + 1], the
+        reads' offsets (mcx_bam_format_dev's rec_off).  Returns a uint8 tensor of 24 bytes a unit (view it as DUP_UNIT_DTYPE on the host): one unit per pair of
+        groups when ``paired``, else per group."""
+        import torch
+        assert recs.dtype == torch.uint8 and recs.is_contiguous() and grp_off.element_size() == 8 and grp_off.is_contiguous()
+        n_groups = max(0, grp_off.numel() - 1)
+        units = torch.zeros(24 * max(1, n_groups), dtype=torch.uint8, device=recs.device)
+        torch.cuda.synchronize()
+        n = C.c_uint64()
+        _check(lib().mcx_bam_dup_units_dev(self._h, recs.data_ptr() if recs.numel() else None, recs.numel(), grp_off.data_ptr(), n_groups, int(paired), units.data_ptr(), C.byref(n)),
+               "mcx_bam_dup_units_dev")
+        return units[:24 * n.value]
+
+    def dup_resolve(self, units):
+        """mcx_dup_resolve_dev: ``units`` as bam_dup_units returns them (or a host array of DUP_UNIT_DTYPE brought to the device as bytes); returns a uint8 tensor, one
+        byte a unit: 1 for a duplicate"""
+        import torch
+        assert units.dtype == torch.uint8 and units.is_contiguous() and units.numel() % 24 == 0
+        n = units.numel() // 24
+        dup = torch.zeros(max(1, n), dtype=torch.uint8, device=units.device)
+        torch.cuda.synchronize()
+        _check(lib().mcx_dup_resolve_dev(self._h, units.data_ptr() if n else None, n, dup.data_ptr()), "mcx_dup_resolve_dev")
+        return dup[:n]
+
+    def bam_dup_mark(self, recs, rec_off, rec_dup) -> None:
+        """mcx_bam_dup_mark_dev: flag bit 0x400 on record i of ``recs`` (uint8, in place; ``rec_off`` 64-bit [n + 1]) where ``rec_dup`` (uint8 [n]) is not 0"""
+        import torch
+        assert recs.dtype == torch.uint8 and recs.is_contiguous() and rec_off.element_size() == 8 and rec_off.is_contiguous() and rec_dup.dtype == torch.uint8 and rec_dup.is_contiguous()
+        n = max(0, rec_off.numel() - 1)
+        assert rec_dup.numel() >= n
+        torch.cuda.synchronize()
+        _check(lib().mcx_bam_dup_mark_dev(self._h, recs.data_ptr() if recs.numel() else None, recs.numel(), rec_off.data_ptr(), n, rec_dup.data_ptr()), "mcx_bam_dup_mark_dev")
+
+    def markdup_last_ms(self) -> Tuple[float, float, float]:
+        """the device times in ms of the last mcx_bam_dup_units_dev, mcx_dup_resolve_dev and mcx_bam_dup_mark_dev"""
+        ms = (C.c_float * 3)()
+        _check(lib().mcx_markdup_last_ms(self._h, ms), "mcx_markdup_last_ms")
+        return tuple(float(x) for x in ms)
 
     def bam_index(self, recs, rec_off, block: int, block_coff, lin, lin_base, runs=None):
         """mcx_bam_index_dev over torch tensors on the mapper's device: ``recs`` uint8 — coordinate-sorted BAM records back to back —, ``rec_off`` 64-bit [n + 1], their

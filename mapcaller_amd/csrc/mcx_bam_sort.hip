@@ -108,6 +108,17 @@ __global__ void __launch_bounds__(256) k_sort_lens(const uint32_t *__restrict__ 
     len_sorted[i] = i < n ? len[idx_sorted[i]] : 0;
 }
 
+// -markdup: the group a sorted record came from — record r in read order lies in the last group g with first[g] <= r (the empty groups before it share its entry)
+__global__ void __launch_bounds__(256) k_sort_groups(const uint32_t *__restrict__ idx_sorted, const uint32_t *__restrict__ first, uint32_t n_groups, uint32_t n, uint32_t *grp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = idx_sorted[i];
+    uint32_t a = 0, z = n_groups;
+    while (z - a > 1) { const uint32_t m = (a + z) / 2; if (first[m] <= r) a = m; else z = m; }
+    grp[i] = a;
+}
+
 // the aligned 16 bytes at p, of which only those inside [lo, hi) are read (the others come as 0)
 __device__ inline uint4 load16_inside(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
 {
@@ -323,6 +334,14 @@ int mcx_bam_sort_part(mcx_ctx *c, uint32_t n_reads, uint64_t n_bytes, mcx_sort_s
         HIP_TRY(hipMemcpy(sink->keys.data(), b.d_key_s, (size_t)n * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(sink->lens.data(), b.d_len_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
+    if (sink->dup) { // -markdup: which group each sorted record came from (d_idx, the sort's input, is free again)
+        sink->dup->grp.resize((size_t)n);
+        if (n) {
+            k_sort_groups<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)mcx_ctx_stream(c)>>>(b.d_idx_s, b.d_first, n_reads, (uint32_t)n, b.d_idx);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(sink->dup->grp.data(), b.d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+    }
     sink->run_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     *d_sorted = b.d_sorted;
     return 0;
@@ -332,9 +351,10 @@ int mcx_bam_sort_part(mcx_ctx *c, uint32_t n_reads, uint64_t n_bytes, mcx_sort_s
 // row (members: dst_off in that row, text_bytes of it), the records — lens[n_records] in (run, index) order; slice k's start at record slice_first[k], byte
 // slice_base[k] of the row — are sorted by the core, deflated, and their blocks brought to (*h_out)[0 .. *n_out), a page-locked buffer that grows as needed.
 // bai (-index; null: none): the chunk's blocks will lie at byte file_at of the file, and its records are indexed before they leave HBM (mcx_bai.hip).
+// dup (-markdup; null: none): dup_bytes[n_records], in the lengths' order, say which records get flag bit 0x400 once they are sorted, before they are deflated.
 int mcx_bam_sort_chunk(mcx_ctx *c, mcx_inflater *inf, mcx_deflater *def, uint32_t block, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n_members,
                        uint64_t text_bytes, const uint32_t *lens, uint64_t n_records, const uint64_t *slice_first, const uint64_t *slice_base, uint32_t n_slices, uint64_t rec_bytes,
-                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], mcx_bai_sink *bai, uint64_t file_at)
+                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], mcx_bai_sink *bai, uint64_t file_at, mcx_dup_sink *dup, const uint8_t *dup_bytes)
 {
     *n_out = 0;
     if (n_records == 0) return 0;
@@ -390,6 +410,7 @@ int mcx_bam_sort_chunk(mcx_ctx *c, mcx_inflater *inf, mcx_deflater *def, uint32_
     if ((rc = sort_core(st, s, b.d_inflated, text_bytes, n, b.d_sorted, nullptr, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if ((rc = core_times(st))) return rc;
+    if (dup && (rc = mcx_markdup_chunk(c, dup, b.d_sorted, b.d_dst_off, n, dup_bytes, b.d_idx_s))) return rc;
     secs[2] += since(t0);
     // deflate and out
     t0 = now();

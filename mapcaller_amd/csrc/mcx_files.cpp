@@ -45,7 +45,7 @@ extern "C" void mcx_file_opts_default(mcx_file_opts *o) { memset(o, 0, sizeof *o
 // last call ran on the device
 namespace {
 typedef std::unique_ptr<Batch> BatchPtr;
-struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; uint64_t sort_stats[6] = {0, 0, 0, 0, 0, 0}; uint64_t index_stats[4] = {0, 0, 0, 0}; };
+struct Kept { std::vector<BatchPtr> objects; uint32_t route[2] = {0, 0}; uint64_t sort_stats[6] = {0, 0, 0, 0, 0, 0}; uint64_t index_stats[4] = {0, 0, 0, 0}; uint64_t markdup_stats[6] = {0, 0, 0, 0, 0, 0}; };
 Kept *kept_of(mcx_ctx *c)
 {
     void **slot = mcx_ctx_files_slot(c, [](void *p) { delete (Kept *)p; });
@@ -73,6 +73,13 @@ extern "C" int mcx_files_index_stats(mcx_ctx *c, uint64_t stats[4])
 {
     if (!c || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_files_index_stats: null argument");
     memcpy(stats, kept_of(c)->index_stats, sizeof kept_of(c)->index_stats);
+    return 0;
+}
+
+extern "C" int mcx_files_markdup_stats(mcx_ctx *c, uint64_t stats[6])
+{
+    if (!c || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_files_markdup_stats: null argument");
+    memcpy(stats, kept_of(c)->markdup_stats, sizeof kept_of(c)->markdup_stats);
     return 0;
 }
 
@@ -194,6 +201,7 @@ struct Run {
     const bool bam;             // ... of BAM records, not text (mcx_bam.hip)
     const bool sort;            // ... in coordinate order: sorted runs to a temporary file, merged behind the last batch (mcx_bam_sort.hip, mcx_sort_plan.h)
     const bool index;           // ... with its .bai beside it, made of what the merge's chunks say of their records (mcx_bai.hip, mcx_bai.h)
+    const bool markdup;         // ... and flag bit 0x400 on its duplicates: units per part, one resolve behind the last batch, marks in the merge (mcx_markdup.hip)
     Timing t;
     Shards sh;
     Pool pool;                  // parse + pack
@@ -233,6 +241,12 @@ struct Run {
     // -index: the stretches and windows of the merge's chunks, and — once the EOF block is written — the bytes of <sam_path>.bai, which close_output writes
     mcx_bai_sink bai;
     std::vector<uint8_t> bai_bytes;
+    // -markdup: the run's units (the mapper's thread), and per run of the merge the group every sorted record came from — 4 bytes a record — with the number of
+    // the part's first unit; behind the resolve one byte a record instead: does it get the flag bit
+    mcx_dup_sink dsink;
+    struct DupRun { std::vector<uint32_t> grp; uint64_t base = 0; int paired = 0; std::vector<uint8_t> bits; };
+    std::vector<DupRun> dup_runs;
+    double dup_host_seconds = 0;
     uint64_t indexed_records = 0;
     ~Run() { drop_tmp(); }
     uint8_t bgzf_eof[28];
@@ -272,7 +286,7 @@ struct Run {
           shard_count(o.shard_count > 1 ? (uint64_t)o.shard_count : 1), shard_rank(shard_count > 1 ? (uint64_t)o.shard_rank : 0), sharded(shard_count > 1),
           batch_reads(std::max<uint64_t>(kReadChunkSize, mcx_ctx_max_reads(ctx) / kReadChunkSize * kReadChunkSize)), per_file((uint32_t)(two ? batch_reads / 2 : batch_reads)),
           threads(o.host_threads > 0 ? o.host_threads : (int)std::min<unsigned>(64, std::max<unsigned>(1, mcx_usable_cpus() * 3 / 4 / (unsigned)shard_count))),
-          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), sort((o.device_sam & MCX_SAM_SORT) != 0 && bam), index((o.device_sam & MCX_SAM_INDEX) != 0 && sort), pool(threads), fpool(threads),
+          wants_sam(sam && sam[0]), dev_sam(o.device_sam != 0 && wants_sam), bgzf((o.device_sam & MCX_SAM_BGZF) != 0 && wants_sam), bam((o.device_sam & MCX_SAM_BAM) != 0 && bgzf), sort((o.device_sam & MCX_SAM_SORT) != 0 && bam), index((o.device_sam & MCX_SAM_INDEX) != 0 && sort), markdup((o.device_sam & MCX_SAM_MARKDUP) != 0 && sort), pool(threads), fpool(threads),
           n_objects(sharded ? 16 : 12), parsed(2), mapped(2), formatted(2), spare((size_t)n_objects),
           profile(mcx_ctx_has_profile(ctx)), multi(mcx_ctx_multi(ctx))
     {
@@ -304,7 +318,7 @@ struct Run {
         if (route != kFastaDev) route = resident ? kResident : !plain ? kSequential : opt.device_parse ? kMappedDev : kMapped;
         if (mapped_input()) { if (int e = open_mapped()) return e; }
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
-        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u) | (index ? (uint32_t)MCX_ROUTE_INDEX : 0u);
+        const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u) | (index ? (uint32_t)MCX_ROUTE_INDEX : 0u) | (markdup ? (uint32_t)MCX_ROUTE_MARKDUP : 0u);
         for (int f = 0; f < nf; f++)
             route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
@@ -407,6 +421,7 @@ struct Run {
             sam_fd = ::open(tmp_path.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0600);
             sam_stream = false; sam_base = 0;
             zs.sort = &sink;
+            if (markdup) sink.dup = &dsink;
             if (sam_fd < 0) {
                 e = mcx_set_error(MCX_ERR_IO, "-sort: cannot write the temporary file " + tmp_path);
                 tmp_path.clear();
@@ -1164,6 +1179,12 @@ struct Run {
         runs.emplace_back();
         sortplan::Run &r = runs.back();
         r.keys.swap(sink.keys); r.lens.swap(sink.lens);
+        if (markdup) {
+            dup_runs.emplace_back();
+            DupRun &d = dup_runs.back();
+            d.grp.swap(dsink.grp); d.base = dsink.part_base; d.paired = dsink.part_paired;
+            if (d.grp.size() != r.lens.size()) return false;
+        }
         uint64_t u = 0;
         for (uint64_t o = 0; o < bytes;) { // BSIZE at byte 16 of a block of ours, ISIZE in its last four
             if (bytes - o < 26 || blocks[o] != 0x1f || blocks[o + 1] != 0x8b || blocks[o + 12] != 'B' || blocks[o + 13] != 'C') return false;
@@ -1190,6 +1211,7 @@ struct Run {
     int merge()
     {
         const Tick t_begin = now();
+        if (markdup) if (const int e = resolve_duplicates()) return e;
         uint64_t chunk_bytes = 256ull << 20;
         if (const char *env = getenv("MCX_SORT_CHUNK")) { const long long v = atoll(env); if (v >= 1) chunk_bytes = (uint64_t)v; } // (debug override)
         sortplan::Plan plan;
@@ -1220,6 +1242,7 @@ struct Run {
         uint64_t h_src_cap = 0, h_out_cap = 0;
         std::vector<mcx_deflate_member> members;
         std::vector<uint32_t> lens;
+        std::vector<uint8_t> bits;
         std::vector<uint64_t> first, base;
         for (size_t k = 0; k < plan.chunks.size() && e == 0; k++) {
             const sortplan::Chunk &ch = plan.chunks[k];
@@ -1231,7 +1254,7 @@ struct Run {
                 h_src_cap = src_bytes + src_bytes / 8 + 4096;
                 if (!(h_src = (uint8_t *)mcx_pinned_alloc(h_src_cap))) { h_src_cap = 0; e = mcx_set_error(MCX_ERR_DEVICE, "-sort: cannot allocate pinned host memory for a chunk's blocks"); break; }
             }
-            members.clear(); lens.clear(); first.clear(); base.clear();
+            members.clear(); lens.clear(); bits.clear(); first.clear(); base.clear();
             uint64_t so = 0, to = 0;
             const Tick t0 = now();
             for (const sortplan::Slice &sl : ch.slices) {
@@ -1245,6 +1268,7 @@ struct Run {
                 first.push_back(lens.size());
                 base.push_back(to + (sl.b0 - r.blocks[sl.k0].u_off));
                 lens.insert(lens.end(), r.lens.begin() + (ptrdiff_t)sl.r0, r.lens.begin() + (ptrdiff_t)sl.r1);
+                if (markdup) bits.insert(bits.end(), dup_runs[sl.run].bits.begin() + (ptrdiff_t)sl.r0, dup_runs[sl.run].bits.begin() + (ptrdiff_t)sl.r1);
                 for (uint64_t j = sl.k0; j < sl.k1; j++) {
                     const sortplan::Block &b = r.blocks[j];
                     if (b.u_size) {
@@ -1265,7 +1289,7 @@ struct Run {
             memset(h_src + so, 0, 8);
             uint64_t made = 0;
             e = mcx_bam_sort_chunk(c, inf, zs.deflater, zs.block, h_src, so + 8, members.data(), (uint32_t)members.size(), to, lens.data(), lens.size(), first.data(), base.data(), (uint32_t)first.size(),
-                                   ch.bytes, &h_out, &h_out_cap, &made, sort_secs + 1, index ? &bai : nullptr, place);
+                                   ch.bytes, &h_out, &h_out_cap, &made, sort_secs + 1, index ? &bai : nullptr, place, markdup ? &dsink : nullptr, bits.data());
             if (e) break;
             indexed_records += lens.size();
             const Tick t1 = now();
@@ -1283,12 +1307,55 @@ struct Run {
         merge_seconds = secs(t_begin, now());
         return e;
     }
+    // -markdup, behind the last batch and ahead of the plan: the run's units are resolved on the device once, and every run's groups become its records' bytes —
+    // a pair unit's verdict goes to both reads, a fragment unit's to the read that is placed, never to a mate without a place
+    int resolve_duplicates()
+    {
+        std::vector<uint8_t> dup;
+        if (const int e = mcx_markdup_resolve(c, &dsink, &dup)) return e;
+        const Tick t0 = now();
+        const std::vector<mcx_dup_unit> &units = dsink.units;
+        uint64_t *ms = kept->markdup_stats;
+        // per unit, which of its reads take the verdict: bit 0 the first (or only) read, bit 1 the second — the loop over the records then reads a byte, not a unit
+        std::vector<uint8_t> takes(units.size());
+        for (size_t u = 0; u < units.size(); u++) {
+            const uint32_t kind = units[u].kind & 3u, second = (units[u].kind >> 2) & 1u;
+            if (kind == 2) { ms[0]++; ms[1] += dup[u]; } else if (kind == 1) { ms[2]++; ms[3] += dup[u]; }
+            takes[u] = !dup[u] ? 0 : kind == 2 ? 3 : kind == 1 ? (second ? 2 : 1) : 0;
+        }
+        ms[4] = dsink.groups;
+        if (dup_runs.size() != runs.size()) return mcx_set_error(MCX_ERR_DEVICE, "-markdup: the runs and their groups do not match");
+        for (DupRun &d : dup_runs) {
+            d.bits.resize(d.grp.size());
+            const uint32_t shift = d.paired ? 1 : 0;
+            for (size_t i = 0; i < d.grp.size(); i++) {
+                const uint32_t g = d.grp[i];
+                const uint64_t u = d.base + (g >> shift);
+                if (u >= takes.size()) return mcx_set_error(MCX_ERR_DEVICE, "-markdup: a record's group has no unit");
+                d.bits[i] = (uint8_t)((takes[u] >> (g & shift)) & 1u);
+            }
+            std::vector<uint32_t>().swap(d.grp);
+        }
+        std::vector<mcx_dup_unit>().swap(dsink.units); // (the units go: from here on a byte a record)
+        dup_host_seconds += secs(t0, now());
+        return 0;
+    }
     // behind the threads: the merge when all went well, and the end of the temporary file whatever happened
     void finish_sort()
     {
         if (!sort) return;
         memset(kept->sort_stats, 0, sizeof kept->sort_stats);
+        memset(kept->markdup_stats, 0, sizeof kept->markdup_stats);
         if (rc == 0 && write_rc.load() == 0 && out_fd >= 0) rc = merge();
+        if (markdup) {
+            uint64_t *ms = kept->markdup_stats;
+            if (rc) memset(ms, 0, sizeof kept->markdup_stats);
+            else {
+                ms[5] = (uint64_t)((dsink.seconds[0] + dsink.seconds[1] + dsink.seconds[2] + dup_host_seconds) * 1e6);
+                fprintf(stderr, "markdup: %llu of %llu pairs and %llu of %llu single reads are duplicates, in %llu groups\n", (unsigned long long)ms[1], (unsigned long long)ms[0],
+                        (unsigned long long)ms[3], (unsigned long long)ms[2], (unsigned long long)ms[4]);
+            }
+        }
         drop_tmp();
     }
 
@@ -1314,6 +1381,9 @@ struct Run {
         if (index) fprintf(stderr, "[mcx_map_files] index: %llu records in %llu stretches, %llu bins and %llu linear entries written, %llu bytes; %.3f s of the merge (on the device: records %.3f, stretches %.3f, windows %.3f ms)\n",
                            (unsigned long long)indexed_records, (unsigned long long)bai.stats.stretches, (unsigned long long)bai.stats.bins, (unsigned long long)bai.stats.intervals, (unsigned long long)bai.stats.bytes,
                            bai.seconds, bai.ms[0], bai.ms[1], bai.ms[2]);
+        if (markdup) fprintf(stderr, "[mcx_map_files] markdup: %llu pair units (%llu duplicates), %llu fragment units (%llu duplicates), %llu groups; units %.3f s of the mapper's time (on the device %.3f ms), resolve %.3f s (on the device %.3f ms) and %.3f s on the host, marks %.3f s of the merge's sort (on the device %.3f ms)\n",
+                             (unsigned long long)kept->markdup_stats[0], (unsigned long long)kept->markdup_stats[1], (unsigned long long)kept->markdup_stats[2], (unsigned long long)kept->markdup_stats[3], (unsigned long long)kept->markdup_stats[4],
+                             dsink.seconds[0], dsink.ms[0], dsink.seconds[1], dsink.ms[1], dup_host_seconds, dsink.seconds[2], dsink.ms[2]);
         fprintf(stderr, "[mcx_map_files] busy seconds: parse + pack %.3f (lines %.3f, rows %.3f; waited for a free batch %.3f) | map %.3f | format %.3f write %.3f  (%d + %d host threads, %s input)\n",
                 t.parse, t.p_lines, t.p_pack, t.p_wait, t.map, t.format, t.write, threads, threads, mapped_input() ? "mapped" : "sequential");
         fprintf(stderr, "[mcx_map_files] waits: reader for room behind it %.3f | mapper for a parsed batch %.3f, for copies out %.3f | formatter for the writer %.3f || mapper's calls: submit %.3f, next %.3f, map_batch_dev %.3f, mapped %.3f\n", t.p_push, t.m_take, t.m_collect, t.f_push, t.m_submit, t.m_in, t.m_dev, t.m_out);
@@ -1340,6 +1410,10 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write a sorted BAM file (-sort with -gpus N / -devices): map on one GPU");
     if ((opt.device_sam & MCX_SAM_INDEX) && !(opt.device_sam & MCX_SAM_SORT))
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index writes the .bai of a coordinate-sorted BAM file and needs -sort (MCX_SAM_INDEX without MCX_SAM_SORT); an unsorted file has no index");
+    if ((opt.device_sam & MCX_SAM_MARKDUP) && !(opt.device_sam & MCX_SAM_SORT))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -markdup flags the duplicates of a coordinate-sorted BAM file and needs -sort (MCX_SAM_MARKDUP without MCX_SAM_SORT)");
+    if ((opt.device_sam & MCX_SAM_MARKDUP) && mcx_ctx_multi(c))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -markdup takes one record a read: it cannot be combined with -m (a line for every equal-best alignment)");
     if ((opt.device_sam & MCX_SAM_INDEX) && sam_path && strcmp(sam_path, "-") == 0)
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index writes <file>.bai beside the BAM file: a file that goes to stdout has no name to put it beside");
     if (opt.device_sam & MCX_SAM_INDEX)

@@ -44,7 +44,15 @@ void *mcx_ctx_stream(mcx_ctx *);
 // not a part's SAM text but its BAM records (mcx_bam.hip), and dropped counts the lines that made none
 // sort (-sort; null: none): the part's records are put into coordinate order before they are compressed (mcx_bam_sort.hip), and the sorted keys and lengths of
 // the part — a run of the merge — arrive in the sink
-struct mcx_sort_sink { std::vector<uint64_t> keys; std::vector<uint32_t> lens; double run_seconds = 0; };
+// dup (-markdup; null: none): the run's units so far — the part's own from part_base on, made before it is sorted (mcx_markdup.hip) — and per sorted record of the
+// part the group (read) it came from; behind the last batch the resolve's groups; device ms and seconds of the calling thread for units, resolve and marks
+struct mcx_dup_sink {
+    std::vector<mcx_dup_unit> units; uint64_t part_base = 0; int part_paired = 0;
+    std::vector<uint32_t> grp;
+    uint64_t groups = 0;
+    float ms[3] = {0, 0, 0}; double seconds[3] = {0, 0, 0};
+};
+struct mcx_sort_sink { std::vector<uint64_t> keys; std::vector<uint32_t> lens; double run_seconds = 0; mcx_dup_sink *dup = nullptr; };
 struct mcx_sam_bgzf { mcx_deflater *deflater; uint32_t block; uint64_t text_bytes, out_bytes; double seconds; int bam; uint64_t dropped; mcx_sort_sink *sort; };
 // -gpu_sam (mcx_sam.hip): the text of one mapped part of a batch, from its slot in HBM to (*text)[at ..] in page-locked host memory; bgzf (null: none): the text is
 // compressed in HBM first and its BGZF blocks arrive instead, *n_bytes their size
@@ -58,7 +66,13 @@ int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t
 int mcx_bam_sort_part(mcx_ctx *, uint32_t n_reads, uint64_t n_bytes, mcx_sort_sink *sink, const uint8_t **d_sorted);
 int mcx_bam_sort_chunk(mcx_ctx *, mcx_inflater *, mcx_deflater *, uint32_t block, const uint8_t *src, uint64_t src_bytes, const mcx_deflate_member *members, uint32_t n_members,
                        uint64_t text_bytes, const uint32_t *lens, uint64_t n_records, const uint64_t *slice_first, const uint64_t *slice_base, uint32_t n_slices, uint64_t rec_bytes,
-                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], struct mcx_bai_sink *bai, uint64_t file_at);
+                       uint8_t **h_out, uint64_t *h_out_cap, uint64_t *n_out, double secs[4], struct mcx_bai_sink *bai, uint64_t file_at, mcx_dup_sink *dup, const uint8_t *dup_bytes);
+// -markdup (mcx_markdup.hip).  part: the units of what mcx_bam_part_dev just made (n_reads groups in read order, n_bytes; paired: reads 2i and 2i + 1 are mates)
+// behind the sink's units.  resolve: all of the sink's units to HBM, *dup one byte a unit back.  chunk: a sorted chunk of the merge (d_rec_off: n + 1 entries)
+// gets its flag bits — h_dup[n] in the order the chunk's records came in, d_perm the sort's permutation.
+int mcx_markdup_part(mcx_ctx *, uint32_t n_reads, uint64_t n_bytes, int paired, mcx_dup_sink *);
+int mcx_markdup_resolve(mcx_ctx *, mcx_dup_sink *, std::vector<uint8_t> *dup);
+int mcx_markdup_chunk(mcx_ctx *, mcx_dup_sink *, uint8_t *d_recs, const uint64_t *d_rec_off, uint32_t n, const uint8_t *h_dup, const uint32_t *d_perm);
 // -index (mcx_bai.hip): the index of the file the merge writes.  begin: the windows' table of the context's contigs in HBM, all-ones.  chunk: the records just
 // deflated (d_rec_off: n + 1 entries; the deflater still knows where their blocks lie) whose blocks will go to byte file_at of the file: their stretches join the
 // accumulator, their windows the table.  end: the table comes back and the file's bytes are made, eof_at the byte the EOF block is written at.  The sink's

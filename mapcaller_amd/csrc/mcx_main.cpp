@@ -61,6 +61,9 @@ static void usage(const char *prog)
             "                       one library (one -f / -f2 pair); not with -gpus N / -devices; -index writes its .bai\n"
             "         -index        with -bam -sort: write the file's index beside it (out.bam.bai, what samtools index makes: format BAI), built on the GPU while the\n"
             "                       merge writes the file; not to stdout; contigs up to 2^29 bases (no .csi)\n"
+            "         -markdup      with -bam -sort: set flag bit 0x400 on duplicate records — pairs with both unclipped 5' ends and strands equal, single reads with one;\n"
+            "                       the one with the highest sum of base qualities of 15 or more stays — decided on the GPU behind the last batch; 4 more bytes of host\n"
+            "                       memory a record and 24 a pair until the merge; no optical distance, one library; not with -m\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -113,6 +116,7 @@ int main(int argc, char **argv)
     bool bam = false;     // -bam: the output file holds BAM records
     bool want_sort = false; // -sort: ... in coordinate order
     bool want_index = false; // -index: ... with its .bai beside it
+    bool want_markdup = false; // -markdup: ... and flag bit 0x400 on its duplicates
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -171,6 +175,7 @@ int main(int argc, char **argv)
         else if (p == "-bgzf") fo.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF;
         else if (p == "-sort") want_sort = true;
         else if (p == "-index") want_index = true;
+        else if (p == "-markdup") want_markdup = true;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
@@ -187,6 +192,9 @@ int main(int argc, char **argv)
     if (want_index && !want_sort) { fprintf(stderr, "Error! -index writes the .bai of a coordinate-sorted BAM file: it needs -bam -sort (an unsorted file has no index)\n"); return 1; }
     if (want_index && sam == "-") { fprintf(stderr, "Error! -index writes <file>.bai beside the BAM file: a file that goes to stdout has no name to put it beside\n"); return 1; }
     if (want_index) fo.device_sam |= MCX_SAM_INDEX;
+    if (want_markdup && !want_sort) { fprintf(stderr, "Error! -markdup flags the duplicates of a coordinate-sorted BAM file: it needs -bam -sort\n"); return 1; }
+    if (want_markdup && multi) { fprintf(stderr, "Error! -markdup takes one record a read: it cannot be combined with -m\n"); return 1; }
+    if (want_markdup) fo.device_sam |= MCX_SAM_MARKDUP;
     if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the

@@ -279,6 +279,8 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
     const uint8_t *d_plain = st->d_text;
     if (bam && bgzf->sort) {
         bgzf->sort->keys.clear(); bgzf->sort->lens.clear();
+        // -markdup: the part's units while its records still lie in read order, a pair's mates side by side
+        if (bgzf->sort->dup && (rc = mcx_markdup_part(c, n_reads, total, paired, bgzf->sort->dup))) return rc;
         if (total && (rc = mcx_bam_sort_part(c, n_reads, total, bgzf->sort, &d_plain))) return rc;
     }
     // -bgzf: the part's text is compressed where it lies (a fresh block at its start), and only the blocks leave the device

@@ -45,6 +45,38 @@ struct BaiBufs {
     }
 };
 
+// -markdup (mcx_markdup.hip): a call's units before they are known to be whole (d_units; the front end's resolve: the whole run's, with their bytes in d_dup), a
+// chunk's duplicate bytes (d_bits), and the resolve's tables: two key and two index arrays of two entries a unit, the heads' flags, hipcub's scratch
+struct DupBufs {
+    mcx_dup_unit *d_units = nullptr; uint64_t cap_units = 0;
+    uint8_t *d_bits = nullptr, *d_dup = nullptr; uint64_t cap_bits = 0, cap_dup = 0;
+    uint64_t *d_ka = nullptr, *d_kb = nullptr; uint32_t *d_ia = nullptr, *d_ib = nullptr, *d_flag = nullptr; uint64_t cap = 0;
+    void *d_tmp = nullptr; size_t tmp_bytes = 0;
+    uint32_t *d_error = nullptr; // [0] the error bits, [1] and [2] the groups the resolve counted among pairs and among fragments
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms[3] = {0, 0, 0}; // the last units, resolve and mark call
+    uint64_t groups = 0;     // the last resolve's
+    void drop_run() // what the front end's one resolve held: the run's units and their bytes
+    {
+        if (d_units) (void)hipFree(d_units);
+        if (d_dup) (void)hipFree(d_dup);
+        d_units = nullptr; d_dup = nullptr; cap_units = 0; cap_dup = 0;
+    }
+    void drop_tables()       // the resolve's arrays, which are as large as the whole run's units
+    {
+        void *p[] = {d_ka, d_kb, d_ia, d_ib, d_flag, d_tmp};
+        for (void *q : p) if (q) (void)hipFree(q);
+        d_ka = d_kb = nullptr; d_ia = d_ib = d_flag = nullptr; d_tmp = nullptr; cap = 0; tmp_bytes = 0;
+    }
+    ~DupBufs()
+    {
+        drop_tables();
+        void *p[] = {d_units, d_bits, d_dup, d_error};
+        for (void *q : p) if (q) (void)hipFree(q);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 // the contigs' names (once), the lengths and offsets of a batch, and — for the file front end — the names, qualities and text (or records) of a batch part in HBM
 struct SamState {
     char *d_cn_text = nullptr; uint32_t *d_cn_off = nullptr;
@@ -58,6 +90,7 @@ struct SamState {
     uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
     SortBufs sort;
     BaiBufs bai;
+    DupBufs dup;
     ~SamState()
     {
         void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf};
