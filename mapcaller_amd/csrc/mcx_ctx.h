@@ -76,7 +76,7 @@ constexpr int kDpBuckets = 1024; // shapes the problems of a long DP list are de
 struct Knobs {
     bool timing = false, seed_one_base = false, dp_by_wave = false, dp_lane_always = false, late_reseed = false, no_work_order = false, no_simple = false,
          simple_no_dp = false, cluster_by_lane = false, rescue_in_line = false, build_by_lane = false, no_sums_cache = false, prof_by_column = false,
-         tier1_hist = false, dp_hist = false, no_tier_overlap = false, no_late_overlap = false, no_prof_overlap = false, no_prepack = false, no_tier1_grow = false, cluster_in_line = false, cluster_split = false;
+         tier1_hist = false, dp_hist = false, no_tier_overlap = false, no_late_overlap = false, no_prof_overlap = false, no_prepack = false, no_tier1_grow = false, cluster_in_line = false, cluster_split = false, cluster_mem = false;
     int seed_fm_budget = 6, build_wave_limit = 0x7fffffff;
     uint32_t order_min = 16384u;
 };
@@ -211,6 +211,7 @@ struct mcx_ctx {
     bool overlap_late = false;
     hipEvent_t ev_clustered = nullptr;
     bool light_fit = false;       // light_pairs_fit(tier 0's capacities): asked once, where the capacities are made
+    bool regs_fit = false;        // packed_hits_fit(the index's text length, max_read_len): k_cluster may keep a read's seeds in registers (asked once, where the context is made)
     bool aside_pays = true;       // the last large tier-0 pass had a straight-line path for the heavy pairs' clustering to hide behind (pass_finish: kAsideGatePairs)
     uint32_t last_shape[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // mcx_pass_last_shape: the last tier-0 pass
     // mcx_stream_*: three batches in flight (copy in | kernels | copy out), each in a slot of its own

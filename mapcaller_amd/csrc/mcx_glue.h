@@ -744,6 +744,158 @@ static inline MCX_HD void stage_cluster_pair(const Ctx &cx, int64_t pair, const 
     *g_hdr = h;
 }
 
+// ---- the same stage with a read's seeds in registers (k_cluster, tier 0) ----------------------------------------------------------
+// prep_seeds sorts a read's hits in the record — every comparison a fetch, every move a store — and cluster_seeds_to fetches them all again: most of
+// what the clustering kernel asks of L2 goes back to lines the lane has had.  Here a read of at most CAP hits is fetched once into CAP packed words
+// (mcx_types.h hit_pack), sorted by a fixed network of compare-exchanges, stored back once where something moved, and clustered out of the words.
+// Every index into the words is a compile-time one (a register array indexed at run time lives in scratch memory).
+
+// (The whole word is compared, so len takes part in the order, and the network is not stable, while prep_seeds orders by (PosDiff, rPos) alone: the list
+//  stored back equals prep_seeds' because hits of equal (PosDiff, rPos) are equal seeds — a seed at a read position has one length.)
+template <int CAP>
+static inline MCX_HD void sort_packed(uint64_t (&w)[CAP]) // bitonic network, ascending; CAP a power of two
+{
+    constexpr int LOG = CAP == 4 ? 2 : CAP == 8 ? 3 : CAP == 16 ? 4 : 5;
+    static_assert(CAP == (1 << LOG), "capacities: 4, 8, 16, 32");
+    MCX_UNROLL
+    for (int lk = 1; lk <= LOG; lk++) {
+        MCX_UNROLL
+        for (int lj = lk - 1; lj >= 0; lj--) {
+            MCX_UNROLL
+            for (int i = 0; i < CAP; i++) {
+                const int l = i ^ (1 << lj);
+                if (l > i) {
+                    const uint64_t a = w[i], b = w[l];
+                    const bool swap = (i & (1 << lk)) == 0 ? a > b : a < b;
+                    w[i] = swap ? b : a; w[l] = swap ? a : b;
+                }
+            }
+        }
+    }
+}
+
+// One read: prep_seeds + cluster_seeds with the same outcome in the record — the kept hits in [0, m) in (PosDiff, rPos) order, the rest of the list
+// untouched, the candidates as cand_init writes them.  Returns the clusters found (more than `cap`: the caller's overflow), m_out = hits kept.
+// A read with more than CAP hits takes the memory path.
+template <int CAP>
+static inline MCX_HD int cluster_read(const IndexView &ix, const Params &pm, int rlen, Hit *h, int n, Cand *out, int cap, int &m_out)
+{
+    if (n > CAP) {
+        m_out = prep_seeds(h, n);
+        return cluster_seeds(ix, pm, rlen, h, m_out, out, cap);
+    }
+    uint64_t w[CAP];
+    int m = 0, moved = CAP; // moved: the first place whose element is not the one that was fetched from it
+    bool in_order = true;
+    uint64_t prev = 0;
+    MCX_UNROLL
+    for (int i = 0; i < CAP; i++) {
+        w[i] = kHitPad;
+        if (i < n) {
+            const Hit x = h[i];
+            const int64_t pd = hit_pd(x);
+            if (pd > 0) {
+                const uint64_t p = hit_pack(pd, x.rPos, x.len);
+                if (m > 0 && (prev >> kPackPosBits) > (p >> kPackPosBits)) in_order = false; // (PosDiff, rPos): prep_seeds' test
+                if (m != i && moved > m) moved = m;
+                w[i] = p; prev = p; m++;
+            }
+        }
+    }
+    m_out = m;
+    if (m == 0) return 0;
+    if (!in_order) moved = 0;
+    if (moved < m) { // out of order, or a dropped hit in front of a kept one (the padding sorts last: the kept ones close up, in their order)
+        sort_packed<CAP>(w);
+        MCX_UNROLL
+        for (int i = 0; i < CAP; i++)
+            if (i >= moved && i < m) h[i] = hit_unpack(w[i]);
+    }
+    // cluster_seeds_to's walk; the head's PosDiff is carried along
+    int nc = 0, head = 0, score = packed_len(w[0]), thr = rlen >> 2;
+    int64_t pd_prev = packed_pd(w[0]), pd_head = pd_prev;
+    int64_t g_end = boundary_of(ix, pd_prev + packed_rpos(w[0]));
+    MCX_UNROLL
+    for (int j = 1; j <= CAP; j++) {
+        if (j <= m) {
+            const uint64_t wj = j < CAP ? w[j < CAP ? j : 0] : kHitPad; // (j == CAP is the terminal pair of a full list; the inner test only keeps the index a valid constant there)
+            const bool real = j < m;
+            const int64_t pdj = real ? packed_pd(wj) : ix.G2, gj = real ? pdj + packed_rpos(wj) : ix.G2;
+            const int lenj = real ? packed_len(wj) : 0;
+            int64_t d = pdj - pd_prev;
+            pd_prev = pdj;
+            if (d < 0) d = -d;
+            if (gj > g_end || d > pm.max_pos_diff) {
+                if (score > thr) {
+                    if (thr < (score >> 1)) thr = score >> 1;
+                    int b = head, e = j, s = score;
+                    int64_t pd0 = pd_head;
+                    if (score >= rlen) { // tandem repeats (rare; run-time indices): out of the record, which holds the sorted list by now
+                        int run_b = head, rs = h[head].len;
+                        s = 0; b = e = head;
+                        int k;
+                        for (k = head + 1; k < j; k++) {
+                            if (hit_pd(h[k]) != hit_pd(h[run_b])) {
+                                if (rs > s) { s = rs; b = run_b; e = k; }
+                                run_b = k; rs = h[k].len;
+                            } else rs += h[k].len;
+                        }
+                        if (rs > s) { s = rs; b = run_b; e = k; }
+                        pd0 = hit_pd(h[b]);
+                    }
+                    if (nc < cap) cand_init(out[nc], s, b, e - b, pd0);
+                    nc++;
+                }
+                head = j; pd_head = pdj;
+                if (real) { g_end = boundary_of(ix, gj); score = lenj; }
+            } else score += lenj;
+        }
+    }
+    return nc;
+}
+
+// what k_cluster does with a pair it has clustered: listed for the large tier (it ran over and the launch keeps an early list) or for mate rescue
+static inline MCX_HD void cluster_outcome(bool paired, bool early, uint32_t flags, int n_paired, uint32_t &need, uint32_t &over)
+{
+    need = (paired && !(flags & kOvAny) && n_paired == 0) ? 1u : 0u;
+    over = (early && (flags & kOvAny)) ? 1u : 0u;
+}
+
+// stage_cluster_pair for k_cluster's lanes: the reads through cluster_read<CAP>, one after the other (one read's words live at a time), and the header
+// in ONE store — kDispatched / kAwaitRescue are decided here; the flags (without the two) and what the pair is listed for (cluster_outcome, which reads
+// flags and n_paired) go back to the kernel in registers: nothing is fetched back from the record.
+template <int CAP>
+static inline MCX_HD void stage_cluster_pair_regs(const Ctx &cx, int64_t pair, const ReadRef *rd, int est, const int *n_hits_in, bool early,
+                                                  uint32_t &flags_out, uint32_t &need, uint32_t &over)
+{
+    PairState st = pair_state(cx.state, cx.lay, cx.caps, pair);
+    PairHdr h;
+    h.n_frags = 0; h.n_ops = 0; h.pair_dist = 0; h.n_jobs = 0; h.pair_ok = 0; h.mapped = 0; h.pad[0] = h.pad[1] = 0;
+    h.sum[0].best = h.sum[1].best = -1; h.sum[0].score = h.sum[1].score = 0; h.sum[0].sub = h.sum[1].sub = 0;
+    const int nr = cx.pm.paired ? 2 : 1;
+    const int rl0 = rd[0].rlen, rl1 = nr == 2 ? rd[1].rlen : 0;
+    uint32_t flags = 0;
+    int nh0 = n_hits_in[0], nh1 = n_hits_in[1], nc0 = 0, nc1 = 0;
+    MCX_NOUNROLL // (one copy of the read's code; what depends on the mate number is picked by hand — an array indexed by it lives in scratch memory)
+    for (int s = 0; s < nr; s++) {
+        int n = s ? nh1 : nh0, m;
+        if (n > cx.caps.hit_seed) { flags |= kOvHits; n = 0; }
+        int nc = cluster_read<CAP>(cx.ix, cx.pm, s ? rl1 : rl0, s ? st.hits[1] : st.hits[0], n, s ? st.cands[1] : st.cands[0], cx.caps.cand_seed, m);
+        if (nc > cx.caps.cand_seed) { flags |= kOvCands; nc = 0; }
+        if (s) { nh1 = m; nc1 = nc; } else { nh0 = m; nc0 = nc; }
+    }
+    h.n_hits[0] = (int16_t)nh0; h.n_hits[1] = (int16_t)nh1; h.n_cands[0] = (int16_t)nc0; h.n_cands[1] = (int16_t)nc1;
+    h.est = est; h.est_lo = 0; h.est_hi = 0x7fffffff;
+    int n_paired = 0;
+    if (cx.pm.paired && !(flags & kOvAny))
+        n_paired = pair_by_distance(est, st.cands[0], nc0, st.cands[1], nc1, h.est_lo, h.est_hi);
+    h.n_paired = (int16_t)n_paired;
+    cluster_outcome(cx.pm.paired != 0, early, flags, n_paired, need, over);
+    h.flags = flags | (over ? (uint32_t)kDispatched : need ? (uint32_t)kAwaitRescue : 0u);
+    *st.hdr = h;
+    flags_out = flags;
+}
+
 // stage R: mate rescue for pairs left unpaired (ReadMapping.cpp:463)
 template <class Eval>
 static inline MCX_HD void stage_rescue(const Ctx &cx, int64_t pair, const ReadRef *rd, const Eval &ev)

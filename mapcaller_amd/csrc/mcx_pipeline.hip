@@ -529,14 +529,23 @@ static __device__ __forceinline__ uint32_t listed_pairs(const PairSel &sel, cons
 
 // (cls_lo .. cls_hi: with the pairs listed by weight, the launch takes the pairs of these classes only: all classes in one launch, heaviest
 //  first inside it, or — run_pairs, the heavy pairs aside — the heavy classes on a side stream beside k_simple and the light ones behind it)
+// (regs: tier 0, with the packed form's guard passed (mcx_ctx::regs_fit) and without MCX_CLUSTER_MEM — a read's seeds are sorted and clustered in registers
+//  (mcx_glue.h cluster_read<CAP>) and the header is stored once.  CAP is the workgroup's: a weight class bounds a read's hits — 4, 8, 16, 32 for classes
+//  5, 4, 3, 2 — and the workgroup's first slot holds its heaviest pair, so the class counts say which one will do for every lane; classes 0 and 1 keep
+//  the memory path, a pass without the order takes 4 (a read with more hits takes the memory path by itself).)
 __global__ void __launch_bounds__(256) k_cluster(Ctx cx, ReadBatch rb, PairSel sel, RescueList rl, const uint32_t *read_blocks, EarlyList el, const uint32_t *order,
-                                                 const uint32_t *order_cnt, int cls_lo, int cls_hi)
+                                                 const uint32_t *order_cnt, int cls_lo, int cls_hi, int regs)
 {
     __shared__ EndsLds ends;
     uint32_t first = 0, n_listed = listed_pairs(sel, order_cnt);
+    int cap = regs ? 4 : 0;
     if (order_cnt && order) {
         uint32_t at = 0;
         for (int k = 0; k < kWorkClasses; k++) { if (k == cls_lo) first = at; at += order_cnt[k * kCntPad]; if (k == cls_hi) n_listed = at; }
+        int cls = 0; // of the block's first slot: the classes that end at or before it
+        at = 0;
+        for (int k = 0; k < kWorkClasses - 1; k++) { at += order_cnt[k * kCntPad]; if (first + blockIdx.x * blockDim.x >= at) cls = k + 1; }
+        if (regs) cap = cls >= 2 ? 4 << (kWorkClasses - 1 - cls) : 0; // classes 5, 4, 3, 2: 4, 8, 16, 32
     }
     if (first + blockIdx.x * blockDim.x >= n_listed) return; // (uniform over the block)
     stage_ends(cx.ix, ends);
@@ -551,13 +560,26 @@ __global__ void __launch_bounds__(256) k_cluster(Ctx cx, ReadBatch rb, PairSel s
         const uint32_t pair = sel_pair(sel, local);
         const int nr = cx.pm.paired ? 2 : 1;
         int nh[2] = {(int)(read_blocks[pair * nr] >> 20), nr == 2 ? (int)(read_blocks[pair * nr + 1] >> 20) : 0}; // k_seed's hit counts
-        stage_cluster_pair(cx, local, rd, sel.est[local], nh);
-        const uint32_t fl = st.hdr->flags;
-        need = (cx.pm.paired && !(fl & kOvAny) && st.hdr->n_paired == 0) ? 1u : 0u;
-        over = (el.ids && (fl & kOvAny)) ? 1u : 0u;
-        if (over && (fl & kOvHits)) atomicAdd(el.n_hits, 1u); // (diagnosis: how many of the listed pairs were known to run over once k_seed was done)
-        if (over) st.hdr->flags = fl | kDispatched; // the later stages of this tier leave the pair alone (they skip kOvAny) and k_finish writes nothing for it
-        else if (need) st.hdr->flags = fl | kAwaitRescue;
+        if (cap) { // (uniform over the block)
+            uint32_t fl = 0;
+            const int e = sel.est[local];
+            const bool early = el.ids != nullptr;
+            switch (cap) {
+            case 4: stage_cluster_pair_regs<4>(cx, local, rd, e, nh, early, fl, need, over); break;
+            case 8: stage_cluster_pair_regs<8>(cx, local, rd, e, nh, early, fl, need, over); break;
+            case 16: stage_cluster_pair_regs<16>(cx, local, rd, e, nh, early, fl, need, over); break;
+            default: stage_cluster_pair_regs<32>(cx, local, rd, e, nh, early, fl, need, over); break;
+            }
+            if (over && (fl & kOvHits)) atomicAdd(el.n_hits, 1u);
+        } else {
+            stage_cluster_pair(cx, local, rd, sel.est[local], nh);
+            const uint32_t fl = st.hdr->flags;
+            need = (cx.pm.paired && !(fl & kOvAny) && st.hdr->n_paired == 0) ? 1u : 0u;
+            over = (el.ids && (fl & kOvAny)) ? 1u : 0u;
+            if (over && (fl & kOvHits)) atomicAdd(el.n_hits, 1u); // (diagnosis: how many of the listed pairs were known to run over once k_seed was done)
+            if (over) st.hdr->flags = fl | kDispatched; // the later stages of this tier leave the pair alone (they skip kOvAny) and k_finish writes nothing for it
+            else if (need) st.hdr->flags = fl | kAwaitRescue;
+        }
     }
     const uint32_t at = wave_reserve(rl.n, need);
     if (need && at < rl.cap) rl.ids[at] = local;
@@ -1356,6 +1378,7 @@ static Knobs knobs_read()
     k.no_sums_cache = on("MCX_NO_SUMS_CACHE"); k.prof_by_column = on("MCX_PROF_BY_COLUMN"); k.tier1_hist = on("MCX_TIER1_HIST"); k.dp_hist = on("MCX_DP_HIST");
     k.no_tier_overlap = on("MCX_NO_TIER_OVERLAP"); k.no_late_overlap = on("MCX_NO_LATE_OVERLAP"); k.no_prof_overlap = on("MCX_NO_PROF_OVERLAP"); k.no_tier1_grow = on("MCX_NO_TIER1_GROW");
     k.cluster_in_line = on("MCX_CLUSTER_IN_LINE"); k.cluster_split = on("MCX_CLUSTER_SPLIT");
+    k.cluster_mem = on("MCX_CLUSTER_MEM"); // (A/B tests, measurements: k_cluster sorts and clusters in the pair record, as the other tiers do)
     // A batch packed on its way in (mcx_stream_submit_packed; MCX_PREPACK=1) pays on runtimes whose copies in and out overlap: 16.2-16.3 against 16.7-16.8 ms per
     // step on ROCm 7.2's; on one that puts both directions on one SDMA engine (HIP 7.0, what torch's wheel carries) the copy in ends late and the longer chain
     // behind it reaches into the next step: 17.5 against 17.1.  Off unless asked for: one fuzz round in 480 of the CLI with it on did not come out
@@ -1555,7 +1578,7 @@ static int ctx_fill(mcx_ctx *c, const mcx_index *idx, const mcx_opts &o)
     HIP_TRY(hipSetDevice(idx->device));
     for (auto &e : c->ev_pack) HIP_TRY(hipEventCreate(&e));
     int rc = 0;
-    c->tier[0].caps = tier0_caps(); c->light_fit = light_pairs_fit(c->tier[0].caps); c->tier[0].lay = make_layout(c->tier[0].caps); c->tier[0].max_pairs = (uint32_t)c->max_reads;
+    c->tier[0].caps = tier0_caps(); c->light_fit = light_pairs_fit(c->tier[0].caps); c->regs_fit = packed_hits_fit(idx->view.G2, c->rlen_max); c->tier[0].lay = make_layout(c->tier[0].caps); c->tier[0].max_pairs = (uint32_t)c->max_reads;
     c->tier[1].caps = tier1_caps(c->rlen_max); c->tier[1].lay = make_layout(c->tier[1].caps);
     // (the heavy pairs of a batch in as few passes as possible — a pass is bound by its slowest pair, not by its size, and passes follow
     //  one another: BASELINE config 5 sends 4.5 % of its pairs here, five passes of 36 k pairs with 8 GB of records — with room in
@@ -1846,6 +1869,7 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
     // MCX_CLUSTER_IN_LINE: one launch over all classes on the pass's stream, as it is for the other tiers, without the order, and without side streams.
     // Not where there is nothing to hide behind: with hardly a straight-line pair in the batch (250-base reads at 5 % indels: nearly every pair is heavy)
     // k_simple ends in 0.2 ms, the two clustering launches only share the chip, and the step was measured 1 % longer.  What the last large pass saw decides.
+    const int regs = tier == 0 && c->regs_fit && !kn.cluster_mem ? 1 : 0; // k_cluster: a read's seeds in registers (tier 0 only)
     const bool aside = ordered && R.dp_stream[0] && R.ev_seeded && c->light_fit && c->aside_pays && !kn.cluster_in_line && !kn.cluster_split;
     hipStream_t hs = aside ? R.dp_stream[0] : s;
     if (aside) {
@@ -1856,7 +1880,7 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
         k_order_place<<<ob, 256, 0, hs>>>(sel, so.read_blocks, nr, R.d_cnt + CNT_ORDER, c->d_order, nullptr, 0, kHeavyClasses - 1);
         HIP_TRY(hipEventRecord(R.ev_order_h, hs));
         // (a grid for every pair of the pass: how many are heavy stays on the device, and a block past the launch's classes ends at once)
-        k_cluster<<<pb, 256, 0, hs>>>(cx, rb, sel, rl, so.read_blocks, el, c->d_order, R.d_cnt + CNT_ORDER, 0, kHeavyClasses - 1);
+        k_cluster<<<pb, 256, 0, hs>>>(cx, rb, sel, rl, so.read_blocks, el, c->d_order, R.d_cnt + CNT_ORDER, 0, kHeavyClasses - 1, regs);
         if (early && c->h_early) k_publish_early<<<1, 64, 0, hs>>>(R.d_cnt + CNT_EARLY, c->d_batch_flags + 3, c->d_early);
         if (early) HIP_TRY(hipEventRecord(c->ev_clustered, hs));
         HIP_TRY(hipEventRecord(R.ev_heavy, hs));
@@ -1904,12 +1928,12 @@ static int run_pairs(mcx_ctx *c, int tier, const PassRes &R, const ReadBatch &rb
             k_cluster_wave<<<std::min<unsigned>(sel.n, 8192u), 64, cl_bytes, s>>>(cx, rb, sel, rl, so.read_blocks, small, 1 << 30, cx.caps.hit_cap, cx.caps.cand_cap);
     } else if (aside) { // the light pairs; none of them can run over: no early list.  Then the heavy side joins (the time stamp below: behind the join)
         EarlyList none = el; none.ids = nullptr; none.est = nullptr; none.cap = 0;
-        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, none, order, order_cnt, kHeavyClasses, kWorkClasses - 1);
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, none, order, order_cnt, kHeavyClasses, kWorkClasses - 1, regs);
         HIP_TRY(hipStreamWaitEvent(s, R.ev_heavy, 0));
     } else if (ordered && kn.cluster_split) { // (MCX_CLUSTER_SPLIT, measurements: the two launches of the aside path one after the other on the pass's stream)
-        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kHeavyClasses - 1);
-        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, kHeavyClasses, kWorkClasses - 1);
-    } else k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kWorkClasses - 1);
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kHeavyClasses - 1, regs);
+        k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, kHeavyClasses, kWorkClasses - 1, regs);
+    } else k_cluster<<<pb, 256, 0, s>>>(cx, rb, sel, rl, so.read_blocks, el, order, order_cnt, 0, kWorkClasses - 1, regs);
     if (!aside) {
         if (early && c->h_early) k_publish_early<<<1, 64, 0, s>>>(R.d_cnt + CNT_EARLY, c->d_batch_flags + 3, c->d_early);
         if (early) HIP_TRY(hipEventRecord(c->ev_clustered, s));

@@ -14,9 +14,11 @@
 #include <hip/hip_runtime.h>
 #define MCX_HD __host__ __device__
 #define MCX_UNROLL _Pragma("unroll")
+#define MCX_NOUNROLL _Pragma("nounroll")
 #else
 #define MCX_HD
 #define MCX_UNROLL
+#define MCX_NOUNROLL
 #endif
 
 namespace mcx {
@@ -91,6 +93,31 @@ struct alignas(16) Hit { // one seed occurrence: FragPair_t with bSimple (struct
     int32_t rPos;
     int32_t len;
 };
+
+// A hit in one 64-bit word, for the clustering kernel's register path (mcx_glue.h cluster_read): PosDiff = gPos - rPos in the top 34 bits, then rPos
+// and len in 10 bits each, so that an unsigned compare of two words is the order the seeds are sorted by, (PosDiff, rPos) — equal keys are equal seeds —
+// and gPos comes back as the sum.  Only hits with PosDiff > 0 are packed.  The all-ones word is the padding and sorts last: no hit of a text the guard
+// admits packs to it (its gPos would lie beyond 2^34).
+constexpr int kPackPdBits = 34, kPackPosBits = 10;
+constexpr uint64_t kHitPad = ~(uint64_t)0;
+// asked once, where the context is made: every text position below 2^34 (the index builder takes genomes up to 4.29 Gbp: 2 G < 2^34), rPos and len at most 1023
+static inline MCX_HD bool packed_hits_fit(int64_t text_len, int max_read_len)
+{
+    return text_len >= 0 && text_len < ((int64_t)1 << kPackPdBits) && max_read_len >= 0 && max_read_len < (1 << kPackPosBits);
+}
+static inline MCX_HD uint64_t hit_pack(int64_t pd, int rPos, int len)
+{
+    return ((uint64_t)pd << (2 * kPackPosBits)) | ((uint64_t)(uint32_t)rPos << kPackPosBits) | (uint64_t)(uint32_t)len;
+}
+static inline MCX_HD int64_t packed_pd(uint64_t w) { return (int64_t)(w >> (2 * kPackPosBits)); }
+static inline MCX_HD int packed_rpos(uint64_t w) { return (int)((w >> kPackPosBits) & ((1u << kPackPosBits) - 1u)); }
+static inline MCX_HD int packed_len(uint64_t w) { return (int)(w & ((1u << kPackPosBits) - 1u)); }
+static inline MCX_HD Hit hit_unpack(uint64_t w)
+{
+    Hit h;
+    h.rPos = packed_rpos(w); h.len = packed_len(w); h.gPos = packed_pd(w) + h.rPos;
+    return h;
+}
 
 struct alignas(16) Cand { // AlnCan_t (structure.h:125-133) as ranges into the pair state; two 16-byte groups
     int64_t pd0;      // FragPairVec[0].PosDiff while sorted by PosDiff
