@@ -107,6 +107,16 @@ void mcx_ctx_free(mcx_ctx *);
  * searched from start[i] to its end.  len/freq: n each; loc: n*50 (freq[i] entries used). */
 int mcx_bwt_search_batch(mcx_ctx *, const uint8_t *seqs, const uint32_t *seq_off, const int32_t *start, uint32_t n,
                          int32_t *len, int32_t *freq, uint64_t *loc);
+/* Test entry: the greedy seeding walk of one read (IdentifySimplePairs' loop, reference src/ReadMapping.cpp:133-150, before its
+ * PosDiff filter) as the batch pipeline's seeding kernel runs it — the same device functions in the same phase loop, on whatever
+ * the index holds (jump table, rank records, pair records, full or sampled suffix array) — for n reads in host memory.  seqs: the
+ * reads' ASCII bases as mcx_map_batch takes them, concatenated, seq_off[n + 1]; no read is reverse-complemented.  fm_budget >= 1:
+ * FM steps a search takes per turn of the loop (the pipeline's resumable shape; results do not depend on it).  hits: n * cap
+ * records, read i's first min(n_hits[i], cap) at hits + i * cap in the order the walk finds them (a search's rows in suffix
+ * order), gPos a text position in [0, 2G); n_hits[i] counts past cap, as the kernel's own counter does. */
+typedef struct mcx_seed_hit { int64_t gPos; int32_t rPos; int32_t len; } mcx_seed_hit;
+int mcx_seed_walk_batch(mcx_ctx *, const uint8_t *seqs, const uint32_t *seq_off, uint32_t n, int fm_budget, uint32_t cap,
+                        int32_t *n_hits, mcx_seed_hit *hits);
 /* nw_alignment / ksw2_alignment (reference src/nw_alignment.cpp:18, src/ksw2_alignment.cpp:250;
  * declared src/structure.h:289,292; called from src/ReadAlignment.cpp:186-187).  q = read
  * fragments, t = genome fragments (ASCII), concatenated with offset arrays of n+1 entries.

@@ -60,7 +60,7 @@ def pack_reads(bases, lens=None):
 SYMBOLS = [
     "mcx_last_error", "mcx_device_count", "mcx_pack_row", "mcx_host_cpus", "mcx_gz_inflate", "mcx_index_load", "mcx_index_build", "mcx_index_from_codes", "mcx_index_save", "mcx_index_free", "mcx_index_trim",
     "mcx_index_genome_size", "mcx_index_n_chr", "mcx_index_chr_name", "mcx_index_chr_len", "mcx_index_hbm_bytes",
-    "mcx_opts_default", "mcx_ctx_create", "mcx_ctx_create_fit", "mcx_ctx_free", "mcx_bwt_search_batch", "mcx_extend_batch", "mcx_extend_lanes",
+    "mcx_opts_default", "mcx_ctx_create", "mcx_ctx_create_fit", "mcx_ctx_free", "mcx_bwt_search_batch", "mcx_seed_walk_batch", "mcx_extend_batch", "mcx_extend_lanes",
     "mcx_avg_init", "mcx_map_batch_dev", "mcx_map_batch", "mcx_cigar_words", "mcx_map_files", "mcx_map_files_ex", "mcx_file_opts_default",
     "mcx_profile_attach", "mcx_profile_settle", "mcx_profile_finalize", "mcx_profile_sparse", "mcx_planes_alloc", "mcx_planes_free", "mcx_planes_bytes",
     "mcx_vcf_defaults", "mcx_call_variants", "mcx_vc_dense_dev",
@@ -408,6 +408,7 @@ def lib() -> C.CDLL:
     L.mcx_ctx_create.argtypes = [C.c_void_p, C.POINTER(Opts), C.POINTER(C.c_void_p)]
     L.mcx_ctx_create_fit.argtypes = [C.c_void_p, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Fit)]
     L.mcx_bwt_search_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
+    L.mcx_seed_walk_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_uint32, C.c_int, C.c_uint32] + [C.c_void_p] * 2
     L.mcx_extend_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 3
     L.mcx_extend_lanes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 4
     L.mcx_avg_init.argtypes = [C.POINTER(C.c_int64)]
@@ -1108,6 +1109,19 @@ class Mapper:
         _check(lib().mcx_bwt_search_batch(self._h, buf.ctypes.data, off.ctypes.data, st.ctypes.data, n, ln.ctypes.data,
                                           fr.ctypes.data, loc.ctypes.data), "mcx_bwt_search_batch")
         return ln, fr, loc
+
+    def seed_walk(self, seqs: List[bytes], fm_budget: int = 1 << 30, cap: int = 1024):
+        """The greedy seeding walk of each read (ASCII bases) as the seeding kernel runs it (mcx_seed_walk_batch).  Returns
+        (n_hits[n], hits[n, cap] with fields gPos, rPos, len): read i's first min(n_hits[i], cap) seeds in the walk's order."""
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(s) for s in seqs])
+        buf = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy()
+        n_hits = np.zeros(n, dtype=np.int32)
+        hits = np.zeros((n, cap), dtype=np.dtype([("gPos", np.int64), ("rPos", np.int32), ("len", np.int32)]))
+        _check(lib().mcx_seed_walk_batch(self._h, buf.ctypes.data, off.ctypes.data, n, int(fm_budget), int(cap), n_hits.ctypes.data,
+                                         hits.ctypes.data), "mcx_seed_walk_batch")
+        return n_hits, hits
 
     def extend(self, alg: str, qs: List[bytes], ts: List[bytes]):
         """nw_alignment / ksw2_alignment for many (read fragment, genome fragment) pairs (ASCII).

@@ -283,7 +283,8 @@ int mcx_build_suffix_index(const uint8_t *d_fwd, uint64_t G, bool want_full_sa, 
     uint64_t max_nb = 0;
     bk.base[0] = 0;
     for (int k = 0; k < bk.n; k++) { bk.base[k + 1] = bk.base[k] + h_count[k]; max_nb = std::max<uint64_t>(max_nb, h_count[k]); }
-    HIP_TRYB(hipMalloc(&sa, N * 8)); HIP_TRYB(hipMalloc(&rank, N * 8)); HIP_TRYB(hipMalloc(&key, N * 8));
+    // (rank doubles as the 4 x n_blocks block counts of the last pass: more than N entries for a text of two positions)
+    HIP_TRYB(hipMalloc(&sa, N * 8)); HIP_TRYB(hipMalloc(&rank, std::max<uint64_t>(N, 4 * ((N + 127) / 128)) * 8)); HIP_TRYB(hipMalloc(&key, N * 8));
     HIP_TRYB(hipMalloc(&key_alt, max_nb * 8)); HIP_TRYB(hipMalloc(&val_alt, max_nb * 8)); HIP_TRYB(hipMalloc(&head, max_nb * 4));
     {
         unsigned long long cur[256];

@@ -17,6 +17,8 @@ se    same genome as mc; 2000 single-end FASTA reads x 100 bp with some N
 long  synthetic 2-contig genome; 600 pairs x 250 bp at 1 % sub / 1 % ins / 1 % del per base
 Each set has ref.<alg>.sam.gz for nw and ksw2, and for one algorithm ref.<alg>.prof.gz / .maps.gz: the\nalignment profile (10 x u16 per position) and the sparse maps the reference holds after Mapping() with -vcf on.
 func  bwt_search.json (queries on the toy index) and dp.json (nw/ksw2 strings, ez.score)
+fm_edges  index files (and, for three texts, BWT_Search results) for the small texts of tests/fm_cases.py;
+      `python scripts/make_golden.py fm_edges` makes this set alone
 """
 import gzip
 import json
@@ -227,9 +229,81 @@ def make_func_vectors():
     print("func vectors done:", len(queries), "searches,", len(cases), "DP cases")
 
 
+FM_SEARCH_TEXTS = ("threshold", "at600", "palindrome")  # texts whose reads' searches are kept as the reference's BWT_Search gives them
+
+
+def make_fm_edges():
+    """tests/golden/fm_edges/<name>/: the five files `MapCaller index` writes for every text of tests/fm_cases.py that it can
+    index, and for a few texts what BWT_Search returns along the greedy walk of each read (searches.json.gz).  Texts the
+    indexer cannot take are listed in README.md and stay on the plain restatement (tests/fm_ref.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fm_cases
+    out_root = os.path.join(GOLD, "fm_edges")
+    shutil.rmtree(out_root, ignore_errors=True)
+    os.makedirs(out_root)
+    left_out, total = [], 0
+    for case in fm_cases.cases().values():
+        if not case.has_fixture:
+            left_out.append((case.name, case.G, "shorter than 15 bases: the reference's indexer exits with an error below 8 bases and did not finish within 60 s at 9"))
+            continue
+        with tempfile.TemporaryDirectory() as tmp:
+            fa = os.path.join(tmp, "ref.fa.gz" if case.gz else "ref.fa")
+            open(fa, "wb").write(case.fasta_file_bytes())
+            prefix = os.path.join(tmp, "idx")
+            try:
+                r = subprocess.run([REF_BIN, "index", fa, prefix], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=60)
+                failed = None if r.returncode == 0 and all(os.path.exists(f"{prefix}.{e}") for e in ("bwt", "sa", "pac", "ann", "amb")) else f"exit status {r.returncode}"
+            except subprocess.TimeoutExpired:
+                failed = "ran past 60 s"
+            if failed:
+                left_out.append((case.name, case.G, f"the reference's indexer failed on it ({failed})"))
+                continue
+            if case.note:  # the same text as another case in another wrapping: the files must be that case's, nothing more is kept
+                for e in ("bwt", "sa", "pac", "ann", "amb"):
+                    assert open(f"{prefix}.{e}", "rb").read() == open(os.path.join(out_root, case.note, f"idx.{e}"), "rb").read(), (case.name, e)
+                continue
+            dst = os.path.join(out_root, case.name)
+            os.makedirs(dst)
+            # (the long-line case is about the FASTA reader: its .bwt / .sa, 200 KB, are not kept)
+            for e in ("pac", "ann", "amb") if case.G > fm_cases.MAX_WALK_G else ("bwt", "sa", "pac", "ann", "amb"):
+                shutil.copy(f"{prefix}.{e}", os.path.join(dst, f"idx.{e}"))
+                total += os.path.getsize(os.path.join(dst, f"idx.{e}"))
+            if case.name in FM_SEARCH_TEXTS:
+                tool = RefTool(prefix)
+                recs = []
+                for _tag, codes in fm_cases.reads_for(case):
+                    found, pos = [], 0
+                    while pos < len(codes) - 16:  # IdentifySimplePairs' loop (ReadMapping.cpp:133-150)
+                        if codes[pos] > 3:
+                            pos += 1
+                            continue
+                        ln, fr, loc = tool.search(codes, pos)
+                        found.append([pos, ln, fr, loc])
+                        pos += ln + 1
+                    if codes and codes[0] <= 3 and not found:  # (a read too short for the walk: one search all the same)
+                        ln, fr, loc = tool.search(codes, 0)
+                        found.append([0, ln, fr, loc])
+                    recs.append({"seq": "".join("ACGTN"[c] for c in codes), "searches": found})
+                tool.p.stdin.close()
+                tool.p.wait()
+                gz_write(os.path.join(dst, "searches.json.gz"), json.dumps(recs, separators=(",", ":")).encode())
+                total += os.path.getsize(os.path.join(dst, "searches.json.gz"))
+    with open(os.path.join(out_root, "README.md"), "w") as fh:
+        fh.write("# fm_edges\n\nIndex files written by the reference's `index` command for the texts of `tests/fm_cases.py`\n"
+                 "(made by `scripts/make_golden.py fm_edges`), and for " + ", ".join(FM_SEARCH_TEXTS) + " the results of its `BWT_Search`\n"
+                 "along each read's greedy walk (`searches.json.gz`).  `shape_three_gz` is `shape_three` gzip-compressed and shares its files;\n"
+                 "of `shape_longline` (one 70 000-character sequence line) only `.pac`, `.ann` and `.amb` are kept.\n\n"
+                 "Texts without files here are held to the plain restatement in `tests/fm_ref.py` alone:\n\n| text | bases | why |\n|---|---|---|\n")
+        for name, G, why in left_out:
+            fh.write(f"| {name} | {G} | {why} |\n")
+    print("fm_edges done:", total, "bytes;", len(left_out), "texts left out:", [n for n, _g, _w in left_out])
+
+
 def main():
     if not (os.path.exists(REF_BIN) and os.path.exists(REF_TOOL)):
         sys.exit("build the reference first: make -C oracle ref")
+    if sys.argv[1:] == ["fm_edges"]:
+        return make_fm_edges()
     os.makedirs(os.path.join(GOLD, "func"), exist_ok=True)
     mut = synth.read_fasta("/root/reference/test/mut.fa")
     make_set("toy", "/root/reference/test/ref.fa", mut, 1500, 150, True, seed=7,
@@ -258,6 +332,7 @@ def main():
                            ("opts", "ksw2", ["-ad", "3", "-min_gap", "20", "-min_cnv", "20", "-size", "400", "-dup", "3", "-maxclip", "10", "-id", "s1"])])
     make_io_set()
     make_func_vectors()
+    make_fm_edges()
     torch.manual_seed(0)
 
 

@@ -67,7 +67,7 @@ static void set_view(Emu &e)
     }
     v.ktab = e.ktab.data(); v.ktab_k = K;
     if (getenv("MCX_EMU_RANK2")) {
-        e.sa_full.assign(h.seq_len + 1, 0);
+        e.sa_full.assign(h.seq_len + 3, 0); // (+2: seed_take fetches rows in pairs, as the device's array has room for)
         for (uint64_t r = 0; r <= h.seq_len; r++) { int lf = 0; e.sa_full[r] = r == 0 ? ~0ull : fm_sa(v, r, lf); }
         v.sa_full = e.sa_full.data();
         const uint64_t n_chunks = (h.seq_len + 31) / 32;
@@ -534,6 +534,54 @@ extern "C" int64_t hostemu_pair_check(const char *prefix, int64_t trials)
     int64_t bad = 0;
     for (int64_t t = 0; t < trials; t++) bad += fm_pair_step_agrees(e.view, (uint64_t)t) ? 0 : 1;
     return bad;
+}
+
+// The seeding walk by itself on the host index (the K = 7 jump table, counts in the .bwt blocks; pairs != 0: every suffix-array entry and
+// the host-made pair records as well), in k_seed's phase loop with fm_budget FM steps per turn: the counterpart of mcx_seed_walk_batch.
+// seqs: ASCII reads, off[n + 1]; hits: n * cap records, n_hits[i] counts past cap.  Returns 0, -1 when the index cannot be read.
+extern "C" int64_t hostemu_seed_walk(const char *prefix, int pairs, const uint8_t *seqs, const uint32_t *off, uint32_t n, int fm_budget, uint32_t cap,
+                                     int32_t *n_hits, Hit *hits)
+{
+    Emu e;
+    std::string err;
+    if (!host_index_load(prefix, e.hix, err)) return -1;
+    if (pairs) setenv("MCX_EMU_RANK2", "1", 1); else unsetenv("MCX_EMU_RANK2");
+    set_view(e);
+    unsetenv("MCX_EMU_RANK2");
+    const IndexView &ix = e.view;
+    std::vector<uint8_t> buf((size_t)off[n] + 64, 'N'); // (the packer fetches whole aligned 16-byte chunks)
+    uint8_t *base = buf.data() + ((16 - ((uintptr_t)buf.data() & 15)) & 15);
+    memcpy(base, seqs, off[n]);
+    for (uint32_t i = 0; i < n; i++) {
+        ReadRef rd; rd.ascii = base + off[i]; rd.rlen = (int)(off[i + 1] - off[i]); rd.flipped = 0;
+        const int rlen = rd.rlen;
+        std::vector<uint32_t> words((size_t)packed_words(rlen) + 4);
+        PackedRead pk; pk.w = words.data(); pk.stride = 1; pk.n_code = 0;
+        pack_read(rd, pk);
+        Hit *mine = hits + (size_t)i * cap;
+        int nh = 0, p = 0;
+        int64_t ext = 0, blocks = 0;
+        uint32_t nm = 0;
+        SeedWalk walk; walk.phase = 0;
+        bool have = seed_next_start(pk, rlen, p, nm);
+        while (have) {
+            if (walk.phase == 0) seed_begin(ix, pk, rlen, nm, p, walk);
+            if (walk.phase == 1) seed_fm(ix, pk, rlen, p, walk, blocks, fm_budget);
+            if (walk.phase == 2) seed_compare_wide(ix, pk, rlen, p, walk, 1 << 30);
+            if (walk.phase == 3) {
+                seed_take(ix, p, walk, mine, (int)cap, nh, ext);
+                have = seed_next_start(pk, rlen, p, nm);
+            }
+        }
+        if (!ix.sa_full)
+            for (int k = 0; k < std::min(nh, (int)cap); k++) {
+                if (mine[k].len & kHitResolved) { mine[k].len &= ~kHitResolved; continue; }
+                int lf = 0;
+                mine[k].gPos = (int64_t)fm_sa(ix, (uint64_t)mine[k].gPos, lf);
+            }
+        n_hits[i] = nh;
+    }
+    return 0;
 }
 
 extern "C" {
