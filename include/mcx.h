@@ -468,6 +468,7 @@ typedef struct mcx_sam_in {
     const mcx_aln *aln; const uint32_t *cigar;         /* the batch's records and CIGAR pool */
     const uint32_t *x_index; const mcx_aln *x_recs; const uint32_t *x_cigar; /* -m extras as mcx_multi_lines hands them out; NULL: none */
     uint32_t n_reads; int32_t paired;
+    const uint8_t *md; const uint32_t *md_off;         /* the lines' MD strings as mcx_md[_dev] makes them (below); NULL: no MD:Z tag, the bytes of before */
 } mcx_sam_in;
 /* d_in: the struct in host memory, every pointer in it a device pointer.  d_text[0 .. cap) receives the text, d_line_off (device, may be
  * NULL) n_reads + 1 byte offsets of the reads' first lines, the last one the total; *n_bytes is always the exact size of the batch's
@@ -479,6 +480,31 @@ int mcx_sam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *text, uint64_t cap,
 /* OutputSamHeaders (reference src/ReadMapping.cpp:101-123): the @PG / @SQ lines the file front end writes ahead of the first
  * batch; *n_bytes their size, MCX_ERR_CAPACITY (nothing written) when cap is smaller. */
 int mcx_sam_header(const mcx_index *, char *out, uint64_t cap, uint64_t *n_bytes);
+
+/* ---- MD:Z strings ------------------------------------------------------------------------------------
+ * The string that says, against the CIGAR, which reference bases a line mismatches or deletes — what `samtools calmd` writes, which the reference does not — made in
+ * HBM from the mcx_sam_in the formatters take and the index's genome.  MD is defined for a mapped line (chr >= 0, n_cigar > 0) by walking its CIGAR over the
+ * line's printed SEQ (the reversal, complement and twice-complement rules of mcx_sam_format_dev applied) against the forward reference from chr_fwd[chr] + pos - 1:
+ *   M columns (and = and X)  a match extends the current run u; a mismatch writes u, then the reference letter, and sets u = 0 — two adjacent mismatches
+ *                            give "..A0C..", a mismatch in the first column a leading "0"
+ *   D                        writes u, '^', the deleted reference letters, and sets u = 0 ("^AC0T": a mismatch directly behind a deletion)
+ *   I, S                     take read bases only and do not end a run; N skips reference bases without text; H and P do nothing
+ *   the end                  the final u is always written: 150M without a mismatch gives "150"
+ *   a column matches         iff the 4-bit BAM code of the SEQ byte (case ignored; 15 for anything outside "=ACMGRSVTWYHKDBN") equals the reference letter's and
+ *                            is not 15: a read N never matches, not even a reference N
+ *   the reference letter     "ACGT"[the two bits of the .pac], or, inside an ambiguity hole of the index's .amb file (lines of "offset length letter"), the
+ *                            hole's own letter in upper case — not the random base the packer put into the .pac; 'N' outside the genome
+ * Unmapped lines and lines without a CIGAR get no tag.  d_md[0 .. cap) receives the strings back to back, no NULs, no "MD:Z:"; d_md_off (device, may be NULL) has
+ * n_reads + n_extras + 1 entries: read r's own record at [r], the -m extra i (the index into x_recs; n_extras = x_index[n_reads]) at [n_reads + i], the last one
+ * the total; a zero-length entry means no tag.  *n_bytes is always exact; cap smaller than that: nothing is written to d_md, MCX_ERR_CAPACITY (cap = 0 asks for the
+ * size).  More than 4 GiB of strings: MCX_ERR_UNSUPPORTED.  names, name_off and qual of d_in are not read.  On the context's stream, waited for.
+ * A pool handed to the formatters through mcx_sam_in.md / md_off appends "\tMD:Z:" + the string behind XS:i of a SAM line, and 'M' 'D' 'Z', the string and a NUL
+ * behind the XS tag of a BAM record (block_size grows by that); the strings are copied from the pool, never recomputed. */
+int mcx_md_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_md, uint64_t cap, uint32_t *d_md_off, uint64_t *n_bytes);
+/* same with host buffers (staged inside) */
+int mcx_md(mcx_ctx *, const mcx_sam_in *in, uint8_t *md, uint64_t cap, uint32_t *md_off, uint64_t *n_bytes);
+/* the last call's device times in ms: length kernel, scan, write kernel */
+int mcx_md_last_ms(mcx_ctx *, float ms[3]);
 
 /* ---- BAM records ---------------------------------------------------------------------------------
  * The same batch as uncompressed BAM records (the reference's -bam: every SAM line through htslib's sam_parse1 / sam_write1, src/ReadMapping.cpp:548-606),
@@ -756,6 +782,10 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * a record and 24 bytes a unit (12 a record for pairs) until the resolve, 1 byte a record from there on.  There is no optical-duplicate distance, no library or
  * read-group distinction (-sort takes one library), and same-strand pairs are not told apart by which mate comes first.  One line on stderr says what was found.
  * MCX_ERR_UNSUPPORTED before anything is opened: the bit without bit 8; a context with -m (mcx_ctx_set_multi).  (route: MCX_ROUTE_MARKDUP.)
+ * bit 64 (MCX_SAM_MD; mapcaller-mi355x -md) puts an MD:Z tag behind XS on every mapped line (mcx_md_dev's strings): behind a batch part's mapping its strings are
+ * made in HBM from the part's reads, records, CIGAR pool and (-m) extras, which carry their own; with bit 1 they feed the device formatters where they lie (SAM
+ * text, BGZF, BAM; -sort, -markdup and -index see only longer records), without it they come to the host with the part's records and the host formatter appends
+ * them.  Without the bit every file is byte for byte what it was.  MCX_ERR_UNSUPPORTED before anything is opened: shard_count > 1.
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -776,7 +806,8 @@ enum mcx_sam_bits {
     MCX_SAM_BAM = 4,    /* ... which hold BAM records instead of SAM text (implies both) */
     MCX_SAM_SORT = 8,   /* ... in coordinate order (only with MCX_SAM_BAM) */
     MCX_SAM_INDEX = 16, /* ... with its .bai written beside it (only with MCX_SAM_SORT) */
-    MCX_SAM_MARKDUP = 32 /* ... and flag bit 0x400 on its duplicate records (only with MCX_SAM_SORT) */
+    MCX_SAM_MARKDUP = 32, /* ... and flag bit 0x400 on its duplicate records (only with MCX_SAM_SORT) */
+    MCX_SAM_MD = 64      /* an MD:Z tag on every mapped line, made on the device (mcx_md_dev); with any of the above, and with none: the host formatter appends it */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);

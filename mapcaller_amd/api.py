@@ -78,6 +78,7 @@ SYMBOLS = [
     "mcx_bam_index_dev", "mcx_bam_index_last_ms", "mcx_bgzf_deflate_blocks", "mcx_files_index_stats",
     "mcx_bam_dup_units_dev", "mcx_dup_resolve_dev", "mcx_bam_dup_mark_dev", "mcx_markdup_last_ms", "mcx_files_markdup_stats",
     "mcx_pass_last_shape",
+    "mcx_md_dev", "mcx_md", "mcx_md_last_ms",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -254,7 +255,7 @@ class FileOpts(C.Structure):
 class SamIn(C.Structure):
     """mcx_sam_in: what mcx_sam_format[_dev] makes a batch's SAM text from (pointers as integers: host or device)."""
     _fields_ = [(n, C.c_void_p) for n in ("bases", "off", "qual", "names", "name_off", "aln", "cigar", "x_index", "x_recs", "x_cigar")] + \
-               [("n_reads", C.c_uint32), ("paired", C.c_int32)]
+               [("n_reads", C.c_uint32), ("paired", C.c_int32), ("md", C.c_void_p), ("md_off", C.c_void_p)]  # (md / md_off: mcx_md[_dev]'s strings; null: no MD:Z tag)
 
 
 ERR_IO, ERR_ARG = -1, -2  # MCX_ERR_IO, MCX_ERR_ARG
@@ -274,6 +275,7 @@ SAM_MARKDUP = 32  # (mcx_sam_bits, below)
 DUP_NONE, DUP_FRAGMENT, DUP_PAIR, DUP_SECOND_MATE = 0, 1, 2, 4  # mcx_dup_unit.kind: bits 0-1 the kind, bit 2 a paired input's fragment is the second read
 DUP_UNIT_DTYPE = np.dtype([("end0", "<u8"), ("end1", "<u8"), ("score", "<u4"), ("kind", "<u4")])  # mcx_dup_unit, 24 bytes
 SAM_INDEX = 16  # (mcx_sam_bits, below)
+SAM_MD = 64  # (mcx_sam_bits: an MD:Z tag on every mapped line; with the host formatter too)
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
 SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam); SAM_INDEX = 16 above
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
@@ -510,6 +512,11 @@ def lib() -> C.CDLL:
     L.mcx_files_index_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mcx_bgzf_deflate_blocks.restype = C.c_int
     L.mcx_bgzf_deflate_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    for f in (L.mcx_md_dev, L.mcx_md):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_md_last_ms.restype = C.c_int
+    L.mcx_md_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_bam_last_ms.restype = C.c_int
     L.mcx_bam_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_inflater_create.restype = C.c_int
@@ -709,7 +716,7 @@ class Mapper:
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
                   device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
-                  index: bool = False, markdup: bool = False) -> dict:
+                  index: bool = False, markdup: bool = False, md: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -728,13 +735,15 @@ class Mapper:
         device from the merge's chunks and written once the BAM file is complete; ERR_UNSUPPORTED without ``sort``, for ``sam`` "-" and for a contig longer than 2^29; ``index_stats()``
         says what was written.  ``markdup`` = -markdup, only with ``sort``: flag bit 0x400 on every record that is a duplicate (the rule: mcx.h at mcx_bam_dup_units_dev) — units made per
         part, resolved once on the device behind the last batch, the bits set in the merge; ERR_UNSUPPORTED without ``sort`` and on a mapper with ``multi``; ``markdup_stats()`` says what was found.
+        ``md`` = -md: an MD:Z tag behind XS on every mapped line, its strings made on the device behind each part's mapping (mcx_md_dev) — with every output above and
+        with the host formatter; ERR_UNSUPPORTED in a sharded run.
         ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0) | (SAM_MD if md else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -776,13 +785,44 @@ class Mapper:
             return aln, cigars
         return aln, cigars, self.multi_lines(n)
 
+    def _md_into(self, si: "SamIn", keep: list) -> Tuple[np.ndarray, np.ndarray]:
+        """mcx_md over the host arrays of ``si``: (the strings back to back, their n_reads + n_extras + 1 offsets), which si.md / si.md_off then point at"""
+        n_x = int(np.ctypeslib.as_array(C.cast(si.x_index, C.POINTER(C.c_uint32)), shape=(si.n_reads + 1,))[-1]) if si.x_index and si.n_reads else 0
+        md_off = np.zeros(si.n_reads + n_x + 1, dtype=np.uint32)
+        nb = C.c_uint64()
+        rc = lib().mcx_md(self._h, C.byref(si), None, 0, md_off.ctypes.data, C.byref(nb))
+        if rc not in (0, ERR_CAPACITY):
+            _check(rc, "mcx_md")
+        md = np.zeros(max(1, nb.value), dtype=np.uint8)
+        _check(lib().mcx_md(self._h, C.byref(si), md.ctypes.data, nb.value, md_off.ctypes.data, C.byref(nb)), "mcx_md")
+        si.md, si.md_off = md.ctypes.data, md_off.ctypes.data
+        keep += [md, md_off]
+        return md[:nb.value], md_off
+
+    def md_strings(self, bases: np.ndarray, off: np.ndarray, paired: bool, aln: np.ndarray, pool: np.ndarray, extras=None) -> List[Optional[bytes]]:
+        """The MD:Z strings of a mapped batch, made on the device (mcx_md) from what sam_text takes (no names, no qualities): one entry per read's own
+        record, then one per extra of ``extras`` in its order; None where the line gets no tag (unmapped, no CIGAR)."""
+        n = np.asarray(off).size - 1
+        si, keep = _sam_in(bases, off, [b""] * n, None, paired, aln, pool, extras)
+        md, md_off = self._md_into(si, keep)
+        buf = md.tobytes()
+        return [buf[int(a):int(b)] if b > a else None for a, b in zip(md_off[:-1], md_off[1:])]
+
+    def md_last_ms(self) -> Tuple[float, float, float]:
+        """the last mcx_md[_dev]'s device times in ms: length kernel, scan, write kernel"""
+        ms = (C.c_float * 3)()
+        _check(lib().mcx_md_last_ms(self._h, ms), "mcx_md_last_ms")
+        return ms[0], ms[1], ms[2]
+
     def sam_text(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
-                 pool: np.ndarray, extras=None) -> bytes:
+                 pool: np.ndarray, extras=None, md: bool = False) -> bytes:
         """The SAM lines of a mapped batch, made on the device (mcx_sam_format).  ``bases`` / ``off`` as given to map_batch, ``names`` the
         QNAMEs, ``quals`` per read the bytes of its quality line that count (at most the read's length; shorter ones are NUL-padded here;
         None: QUAL is '*'), ``aln`` the records and ``pool`` CIGAR words such that read r's are pool[aln[r].cigar_off:][:n_cigar] — map_batch's
-        list of per-read arrays is accepted too —, ``extras`` what multi_lines returns."""
+        list of per-read arrays is accepted too —, ``extras`` what multi_lines returns.  ``md``: an MD:Z tag behind XS on every mapped line (mcx_md)."""
         si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
+        if md and si.n_reads:
+            self._md_into(si, keep)
         nb = C.c_uint64()
         rc = lib().mcx_sam_format(self._h, C.byref(si), None, 0, None, C.byref(nb))
         if rc not in (0, ERR_CAPACITY):
@@ -792,11 +832,13 @@ class Mapper:
         return text[:nb.value].tobytes()
 
     def bam_records(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
-                    pool: np.ndarray, extras=None) -> Tuple[bytes, int]:
+                    pool: np.ndarray, extras=None, md: bool = False) -> Tuple[bytes, int]:
         """The uncompressed BAM records of a mapped batch, made on the device (mcx_bam_format), from what sam_text takes: (the records back to
         back — the record of every line sam_text would give, in its order —, the lines that made none: a name of 252 bytes or more, a QUAL that
-        is not '*' and not as long as the read)."""
+        is not '*' and not as long as the read).  ``md``: an MD:Z tag behind XS in every mapped record (mcx_md)."""
         si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
+        if md and si.n_reads:
+            self._md_into(si, keep)
         nb, nd = C.c_uint64(), C.c_uint64()
         rc = lib().mcx_bam_format(self._h, C.byref(si), None, 0, None, C.byref(nb), C.byref(nd))
         if rc not in (0, ERR_CAPACITY):

@@ -55,7 +55,7 @@ __device__ inline void wave_sync()
 }
 
 // one record by one wavefront; returns its bytes (0: the line makes none)
-__device__ inline uint32_t wave_record(const SamRead &d, const mcx_aln &rec, const uint32_t *cig, uint8_t *stage, uint8_t *dst, uint32_t lane)
+__device__ inline uint32_t wave_record(const SamRead &d, const mcx_aln &rec, const uint32_t *cig, uint8_t *stage, uint8_t *dst, uint32_t lane, const uint8_t *md, uint32_t ml)
 {
     const SamTurn t = sam_turn(d, rec);
     uint32_t ql = 1; // '*'
@@ -66,12 +66,17 @@ __device__ inline uint32_t wave_record(const SamRead &d, const mcx_aln &rec, con
     }
     if (!bam_keep_ql(d, t, ql)) return 0; // (the whole wavefront: d, rec and ql are the same in every lane)
     const bool star = bam_qual_star(d, t, ql);
-    const BamLayout l = bam_layout(d, rec);
+    const BamLayout l = bam_layout(d, rec, ml);
     const uint32_t L = l.total;
     const uint32_t sh = (uint32_t)((uintptr_t)dst & 15u);
     const bool staged = sh + L <= (uint32_t)kBamStage;
     uint8_t *o = staged ? stage + sh : dst; // (the staging is 16-byte aligned: o and dst sit alike within their 16 bytes; a record too long for it goes straight to its place)
     if (lane == 0) { bam_fixed_put(d, rec, cig, L, o); o[kBamFixed + d.name_len] = 0; bam_tags_put(rec, o + l.tags_at); }
+    if (ml) { // the MD tag behind XS: its string is the pool's
+        const uint32_t md_at = L - bam_md_len(ml);
+        if (lane == 0) { o[md_at] = 'M'; o[md_at + 1] = 'D'; o[md_at + 2] = 'Z'; o[L - 1] = 0; }
+        for (uint32_t k = lane; k < ml; k += 64) o[md_at + 3 + k] = md[k];
+    }
     for (uint32_t k = lane; k < d.name_len; k += 64) o[kBamFixed + k] = d.name[k];
     for (uint32_t k = l.cigar_at + lane; k < l.seq_at; k += 64) o[k] = bam_cigar_byte(cig, k - l.cigar_at);
     for (uint32_t k = l.seq_at + lane; k < l.qual_at; k += 64) o[k] = bam_seq_out(d, t, k - l.seq_at);
@@ -97,12 +102,15 @@ __global__ void __launch_bounds__(64 * kBamWaves) k_bam_write(mcx_sam_in in, con
     const SamRead d = sam_read_of(in, r);
     uint8_t *dst = out + rec_off[r];
     const mcx_aln rec = in.aln[r];
-    dst += wave_record(d, rec, in.cigar + (uint32_t)rec.cigar_off, stage[w], dst, lane);
+    const uint8_t *md;
+    uint32_t ml = sam_md_of(in, r, md);
+    dst += wave_record(d, rec, in.cigar + (uint32_t)rec.cigar_off, stage[w], dst, lane, md, ml);
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
     for (uint32_t i = lo; i < hi; i++) {
         const mcx_aln x = in.x_recs[i];
-        dst += wave_record(d, x, in.x_cigar + (uint32_t)x.cigar_off, stage[w], dst, lane);
+        ml = sam_md_of(in, in.n_reads + i, md);
+        dst += wave_record(d, x, in.x_cigar + (uint32_t)x.cigar_off, stage[w], dst, lane, md, ml);
     }
 }
 
@@ -196,6 +204,7 @@ extern "C" int mcx_bam_format(mcx_ctx *c, const mcx_sam_in *in, uint8_t *out, ui
     const uint64_t n_x = in->x_index ? in->x_index[n] : 0;
     for (uint64_t i = 0; i < n_x; i++) x_words = std::max<uint64_t>(x_words, (uint64_t)(uint32_t)in->x_recs[i].cigar_off + (uint64_t)std::max(in->x_recs[i].n_cigar, 0));
     struct Piece { const void *src; uint64_t bytes; void **dst; };
+    const bool with_md = in->md && in->md_off; // the lines' MD strings: one entry per read and per extra, and the total
     mcx_sam_in d = *in;
     uint64_t *d_off64 = nullptr; uint8_t *d_out = nullptr;
     const Piece pieces[] = {
@@ -203,6 +212,7 @@ extern "C" int mcx_bam_format(mcx_ctx *c, const mcx_sam_in *in, uint8_t *out, ui
         {in->names, in->name_off[n], (void **)&d.names}, {in->name_off, (n + 1) * 4, (void **)&d.name_off},
         {in->aln, n * sizeof(mcx_aln), (void **)&d.aln}, {in->cigar, words * 4, (void **)&d.cigar},
         {in->x_index, in->x_index ? (n + 1) * 4 : 0, (void **)&d.x_index}, {in->x_recs, n_x * sizeof(mcx_aln), (void **)&d.x_recs}, {in->x_cigar, x_words * 4, (void **)&d.x_cigar},
+        {with_md ? in->md : nullptr, with_md ? in->md_off[n + n_x] : 0, (void **)&d.md}, {with_md ? in->md_off : nullptr, with_md ? (n + n_x + 1) * 4 : 0, (void **)&d.md_off},
     };
     uint64_t all = 0;
     for (const Piece &p : pieces) all += (p.bytes + 15) / 16 * 16 + 16;

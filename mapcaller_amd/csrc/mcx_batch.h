@@ -55,6 +55,10 @@ struct Batch {
     // recs[index[r] .. index[r + 1]), their cigar_off into cig
     struct Extras { std::vector<uint32_t> index, cig; std::vector<mcx_aln> recs; } mx[2];
     bool has_mx = false;
+    // -md without device_sam: each part's MD strings, copied out behind its mapping (mcx_md_part_host): those of the part's read r at off[r], of its extra i at
+    // off[part's reads + i] (the layout of mcx_md_dev)
+    struct Md { std::vector<uint8_t> bytes; std::vector<uint32_t> off; } md[2];
+    bool has_md = false;
     std::deque<bool> parts_out; // the parts on their way out, oldest first (true: the single-read part)
     // device_sam: the names and NUL-padded qualities of the batch's two parts on their way to the device (page-locked; a part's names back to back with
     // offsets that start at 0: the pairs' are sam_name_off[0 .. n_pair_reads], the single reads' sam_name_off[n_pair_reads + 1 .. n + 1]), and the text that came back
@@ -119,7 +123,7 @@ inline size_t sam_bound(const HostIndex &ix, size_t name_len, size_t rlen, int c
 }
 
 // one SAM line of read r: `rec` with its operations at `cigar`
-inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx_aln &rec, const uint32_t *cigar, Text &o)
+inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx_aln &rec, const uint32_t *cigar, Text &o, const uint8_t *md = nullptr, uint32_t md_len = 0)
 {
     static const char opc[8] = {'M', 'I', 'D', 'N', 'S', 'H', 'P', '='};
     const char *base;
@@ -158,7 +162,17 @@ inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx
         else if (e.q_take == e.rlen) { char *w = o.w; for (int k = rlen - 1; k >= 0 && qual[k] != '\0'; k--) *w++ = qual[k]; o.w = w; }
     }
     if (!mapped) o.lit("\tAS:i:0\tXS:i:0\n");
-    else { o.lit("\tNM:i:"); o.num(rec.nm); o.lit("\tAS:i:"); o.num(rec.as); o.lit("\tXS:i:"); o.num(rec.xs); o.put('\n'); }
+    else { o.lit("\tNM:i:"); o.num(rec.nm); o.lit("\tAS:i:"); o.num(rec.as); o.lit("\tXS:i:"); o.num(rec.xs); if (md_len) { o.lit("\tMD:Z:"); o.put((const char *)md, md_len); } o.put('\n'); }
+}
+
+// -md: the string of entry k of a part's pool (none without -md, or for a line without a tag)
+inline uint32_t md_entry(const Batch &bt, int part, size_t k, const uint8_t *&md)
+{
+    md = nullptr;
+    const Batch::Md &m = bt.md[part];
+    if (!bt.has_md || k + 1 >= m.off.size()) return 0;
+    md = m.bytes.data() + m.off[k];
+    return m.off[k + 1] - m.off[k];
 }
 
 // -m: read r's extra lines (none without -m) — where they lie in its part's extras
@@ -178,10 +192,14 @@ inline void sam_record(const HostIndex &ix, const Batch &bt, uint32_t r, Text &o
     mcx_aln_unpack(&bt.recs[r], &rec);
     // the batch's CIGAR pool (the single-read part of a batch has one of its own behind the pairs'), cigar_off = the read's place in it
     const uint32_t *cigar = bt.cig + (r < bt.n_pair_reads ? 0 : MCX_CIGAR_POOL_WORDS(bt.n_pair_reads)) + (size_t)(uint32_t)rec.cigar_off;
-    sam_line(ix, bt, r, rec, cigar, o);
+    const int part = r < bt.n_pair_reads ? 0 : 1;
+    const uint32_t part_reads = part ? bt.n - bt.n_pair_reads : bt.n_pair_reads;
+    const uint8_t *md;
+    uint32_t ml = md_entry(bt, part, part ? r - bt.n_pair_reads : r, md);
+    sam_line(ix, bt, r, rec, cigar, o, md, ml);
     const Batch::Extras *x; uint32_t lo, hi;
     extra_range(bt, r, x, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) sam_line(ix, bt, r, x->recs[i], x->cig.data() + (uint32_t)x->recs[i].cigar_off, o);
+    for (uint32_t i = lo; i < hi; i++) { ml = md_entry(bt, part, (size_t)part_reads + i, md); sam_line(ix, bt, r, x->recs[i], x->cig.data() + (uint32_t)x->recs[i].cigar_off, o, md, ml); }
 }
 
 // bytes read r's line(s) can take at most
@@ -191,6 +209,13 @@ inline size_t sam_bound_read(const HostIndex &ix, const Batch &bt, uint32_t r, s
     const Batch::Extras *x; uint32_t lo, hi;
     extra_range(bt, r, x, lo, hi);
     for (uint32_t i = lo; i < hi; i++) b += sam_bound(ix, name_len, rlen, x->recs[i].chr, x->recs[i].n_cigar);
+    if (bt.has_md) { // the lines' MD tags
+        const int part = r < bt.n_pair_reads ? 0 : 1;
+        const uint32_t part_reads = part ? bt.n - bt.n_pair_reads : bt.n_pair_reads;
+        const uint8_t *md;
+        b += 6 + md_entry(bt, part, part ? r - bt.n_pair_reads : r, md);
+        for (uint32_t i = lo; i < hi; i++) b += 6 + md_entry(bt, part, (size_t)part_reads + i, md);
+    }
     return b;
 }
 

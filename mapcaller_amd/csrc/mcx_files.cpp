@@ -279,6 +279,7 @@ struct Run {
     // the part of `cur` that is on the device, and how many of its parts are on their way out
     const uint8_t *d_bases = nullptr; const uint32_t *d_off = nullptr; mcx_aln *d_aln = nullptr; uint32_t *d_cig = nullptr; uint32_t n_dev = 0;
     int parts_out = 0;
+    bool host_md = false; // -md without device_sam: every mapped part's MD strings come to the host for the formatter's threads (part_md)
 
     Run(mcx_ctx *ctx, const char *f1, const char *f2, const mcx_file_opts &o, const char *sam, mcx_stats *st)
         : c(ctx), fq1(f1), fq2(f2), sam_path(sam), opt(o), stats(st), idx(mcx_ctx_index(ctx)), hix(idx->host), max_len(mcx_ctx_max_read_len(ctx)), kept(kept_of(ctx)),
@@ -1073,11 +1074,19 @@ struct Run {
         }
         t.m_sam += secs(tq, now());
     }
+    void part_md(Batch *p, bool second, uint32_t cnt) // -md for the host formatter: the mapped part's MD strings, made where its records lie
+    {
+        if (!host_md || rc || !cnt) return;
+        const Tick tq = now();
+        Batch::Md &m = p->md[second ? 1 : 0];
+        if (const int e = mcx_md_part_host(c, d_bases, d_off, cnt, second ? 0 : 1, d_aln, d_cig, &m.bytes, &m.off)) rc = e;
+        t.m_sam += secs(tq, now());
+    }
     // one shard: the batch's parts are mapped as they are
     void map_alone(Batch *p, uint32_t n_pr, uint32_t n_sg)
     {
-        if (n_pr && part_in()) { const Tick tq = now(); if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_pr, 1, avg, d_aln, d_cig, stats); t.m_dev += secs(tq, now()); t.each_dev.push_back(secs(tq, now())); part_text(p, false, n_pr); part_out(p, false); }
-        if (n_sg && part_in()) { if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_sg, 0, avg, d_aln, d_cig, stats); part_text(p, true, n_sg); part_out(p, true); }
+        if (n_pr && part_in()) { const Tick tq = now(); if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_pr, 1, avg, d_aln, d_cig, stats); t.m_dev += secs(tq, now()); t.each_dev.push_back(secs(tq, now())); part_md(p, false, n_pr); part_text(p, false, n_pr); part_out(p, false); }
+        if (n_sg && part_in()) { if (rc == 0) rc = mcx_map_batch_dev(c, d_bases, d_off, n_sg, 0, avg, d_aln, d_cig, stats); part_md(p, true, n_sg); part_text(p, true, n_sg); part_out(p, true); }
     }
     // one round of a sharded run (mcx_shards.h): what every shard holds, the paired parts, the single reads, the places of an earlier round's text
     void map_round(Batch *p, uint32_t n_pr, uint32_t n_sg)
@@ -1138,6 +1147,8 @@ struct Run {
             parts_out = 0;
             d_bases = nullptr; d_off = nullptr; d_aln = nullptr; d_cig = nullptr; n_dev = 0;
             p->has_mx = multi;
+            p->has_md = host_md;
+            for (Batch::Md &m : p->md) { m.bytes.clear(); m.off.clear(); }
             for (Batch::Extras &x : p->mx) { x.index.clear(); x.recs.clear(); x.cig.clear(); }
             p->parts_out.clear();
             p->dev_bytes = 0;
@@ -1422,7 +1433,14 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
                 return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -index: a contig is longer than 2^29 bases, which a .bai cannot address (a .csi could: not offered)");
     if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_BGZF))
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF or as BAM (-bgzf / -bam with -gpus N / -devices): map on one GPU, or without them");
+    if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_MD))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run does not make MD tags (-md with -gpus N / -devices): map on one GPU, or without -md");
+    // -md is no output route of its own: the bit comes off, and where the text is made on the device the context's formatter calls are told (until the run is over)
+    const bool with_md = (opt.device_sam & MCX_SAM_MD) != 0 && sam_path && sam_path[0];
+    opt.device_sam &= ~(int32_t)MCX_SAM_MD;
+    struct MdSwitch { mcx_ctx *c; bool on; MdSwitch(mcx_ctx *ctx, bool o) : c(ctx), on(o) { if (on) mcx_md_set(c, 1); } ~MdSwitch() { if (on) mcx_md_set(c, 0); } } md_switch(c, with_md && opt.device_sam != 0);
     Run run(c, fq1, fq2, opt, sam_path, stats);
+    run.host_md = with_md && opt.device_sam == 0;
     if (int e = run.open_input()) return e;
     if (int e = run.open_output()) return e;
     run.begin();

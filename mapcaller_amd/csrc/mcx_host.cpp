@@ -86,6 +86,16 @@ bool host_index_load(const std::string &prefix, HostIndex &ix, std::string &err)
     if ((uint64_t)ix.G * 2 != ix.seq_len) { err = prefix + ".ann and .bwt disagree on the genome size"; return false; }
     f = fopen((prefix + ".amb").c_str(), "r"); // presence is required by the reference (GetData.cpp:148-166)
     if (!f) { err = "cannot read " + prefix + ".amb"; return false; }
+    { // its holes (bns_dump, bntseq.c:78-91: a line of totals, then "offset length letter" per hole), for the MD strings: kept sorted by offset, clipped to the genome
+        long long l = 0, off = 0; int n_seqs2 = 0, n_holes = 0, len = 0; char letter = 0;
+        struct Hole { int64_t off; int32_t len; uint8_t letter; };
+        std::vector<Hole> holes;
+        if (fscanf(f, "%lld%d%d", &l, &n_seqs2, &n_holes) == 3)
+            while ((int)holes.size() < n_holes && fscanf(f, "%lld%d %c", &off, &len, &letter) == 3)
+                if (off >= 0 && len > 0 && off < ix.G) holes.push_back(Hole{off, (int32_t)std::min<long long>(len, ix.G - off), (uint8_t)letter});
+        std::stable_sort(holes.begin(), holes.end(), [](const Hole &a, const Hole &b) { return a.off < b.off; });
+        for (const Hole &h : holes) { ix.hole_off.push_back(h.off); ix.hole_len.push_back(h.len); ix.hole_letter.push_back(h.letter); }
+    }
     fclose(f);
     if (!read_file(prefix + ".pac", ix.pac) || (int64_t)ix.pac.size() < ix.G / 4 + 1) { err = "cannot read " + prefix + ".pac"; return false; }
     ix.pac.resize(ix.pac.size() + 32, 0); // readers fetch aligned 16-byte chunks

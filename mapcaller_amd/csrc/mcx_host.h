@@ -20,6 +20,10 @@ struct HostIndex {
     std::vector<int64_t> chr_fwd;
     std::vector<int64_t> end_pos;
     std::vector<int32_t> end_chr;
+    // the .amb file's ambiguity holes, sorted by offset: stretches of the forward genome whose FASTA letter is not ACGT (the .pac holds random bases there)
+    std::vector<int64_t> hole_off;
+    std::vector<int32_t> hole_len;
+    std::vector<uint8_t> hole_letter;
 };
 
 bool host_index_load(const std::string &prefix, HostIndex &out, std::string &err);

@@ -175,6 +175,11 @@ static int index_to_device(mcx_index *ix, int full_sa)
     if ((rc = upload(&ix->d_end_pos, h.end_pos.data(), h.end_pos.size() * 8, 0, ix->hbm_bytes))) return rc;
     if ((rc = upload(&ix->d_end_chr, h.end_chr.data(), h.end_chr.size() * 4, 0, ix->hbm_bytes))) return rc;
     if ((rc = upload(&ix->d_chr_fwd, h.chr_fwd.data(), h.chr_fwd.size() * 8, 0, ix->hbm_bytes))) return rc;
+    if (!h.hole_off.empty()) { // the ambiguity holes, beside the index: not part of the view the mapping kernels are passed
+        if ((rc = upload(&ix->d_hole_off, h.hole_off.data(), h.hole_off.size() * 8, 0, ix->hbm_bytes))) return rc;
+        if ((rc = upload(&ix->d_hole_len, h.hole_len.data(), h.hole_len.size() * 4, 0, ix->hbm_bytes))) return rc;
+        if ((rc = upload(&ix->d_hole_letter, h.hole_letter.data(), h.hole_letter.size(), 0, ix->hbm_bytes))) return rc;
+    }
     IndexView &v = ix->view;
     v.bwt = (const uint32_t *)ix->d_bwt; v.sa = (const uint64_t *)ix->d_sa; v.sa_full = nullptr; v.ktab = nullptr; v.ktab_k = 0; v.rank = nullptr; v.rank_chunks = 0; for (auto &x : v.rank_cross) x = ~0ull; v.rank2 = nullptr; v.rank2_c2 = nullptr; v.rank2_lone = ~0ull; v.rank2_t0 = 0;
     v.pac = (const uint8_t *)ix->d_pac;
@@ -329,11 +334,12 @@ extern "C" int mcx_index_save(const mcx_index *ix, const char *prefix)
 extern "C" void mcx_index_free(mcx_index *ix)
 {
     if (!ix) return;
-    void *p[] = {ix->d_bwt, ix->d_sa, ix->d_sa_full, ix->d_pac, ix->d_end_pos, ix->d_end_chr, ix->d_chr_fwd, ix->d_ktab, ix->d_rank, ix->d_rank2, ix->d_rank2_c2};
+    void *p[] = {ix->d_bwt, ix->d_sa, ix->d_sa_full, ix->d_pac, ix->d_end_pos, ix->d_end_chr, ix->d_chr_fwd, ix->d_ktab, ix->d_rank, ix->d_rank2, ix->d_rank2_c2, ix->d_hole_off, ix->d_hole_len, ix->d_hole_letter};
     for (void *q : p) if (q) (void)hipFree(q);
     // (a caller that frees the index before its contexts — allowed: a context that is only freed afterwards touches no device memory of the index — leaves
     //  the host object to the last mcx_ctx_free, which still counts itself out of it)
     ix->d_bwt = ix->d_sa = ix->d_sa_full = ix->d_pac = ix->d_end_pos = ix->d_end_chr = ix->d_chr_fwd = ix->d_ktab = ix->d_rank = ix->d_rank2 = ix->d_rank2_c2 = nullptr;
+    ix->d_hole_off = ix->d_hole_len = ix->d_hole_letter = nullptr;
     if (ix->n_ctx.load() > 0) { ix->orphan.store(true); return; }
     delete ix;
 }

@@ -15,6 +15,7 @@ struct mcx_index {
     int device = 0;
     void *d_bwt = nullptr, *d_sa = nullptr, *d_sa_full = nullptr, *d_pac = nullptr;
     void *d_end_pos = nullptr, *d_end_chr = nullptr, *d_chr_fwd = nullptr, *d_ktab = nullptr, *d_rank = nullptr;
+    void *d_hole_off = nullptr, *d_hole_len = nullptr, *d_hole_letter = nullptr; // the .amb file's ambiguity holes (host.hole_*), for the MD strings alone (mcx_md.hip); null: none
     void *d_rank2 = nullptr, *d_rank2_c2 = nullptr; // pair records (mcx_fm.h PairSlot): built when the index is made with full_sa = 2
     int64_t rank2_bytes = 0;
     int pair_records = 0;
@@ -61,6 +62,14 @@ int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint3
 // -bam (mcx_bam.hip): mcx_bam_format_dev for sam_part's input — the records of a part into d_out[0 .. cap), *n_bytes their exact size (MCX_ERR_CAPACITY, nothing
 // written, when cap is smaller), *n_dropped the lines that made none; the context's device is current
 int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t cap, uint64_t *n_bytes, uint64_t *n_dropped);
+// -md (mcx_md.hip).  set: the context's following mcx_sam_part[_dev] calls make their part's MD strings first and hand them to the formatter.  part_dev: the
+// strings of `in`'s lines (n_extras: the context's extras of the part) into the formatter state's own pool, which in->md / in->md_off then point at.  part_host:
+// the same for a part still in its slot whose text the host makes: the strings and their offsets (n_reads + extras + 1 entries) come back with the part.
+void mcx_md_set(mcx_ctx *, int on);
+bool mcx_md_wanted(mcx_ctx *);
+int mcx_md_part_dev(mcx_ctx *, mcx_sam_in *in, uint32_t n_extras, uint64_t *n_bytes);
+int mcx_md_part_host(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint32_t n_reads, int paired, const mcx_aln *d_aln, const uint32_t *d_cigar,
+                     std::vector<uint8_t> *md, std::vector<uint32_t> *md_off);
 // -sort (mcx_bam_sort.hip).  part: what mcx_bam_part_dev just made (n_reads groups, n_bytes) in key order in a buffer of the state's own, *d_sorted; keys and
 // lengths into the sink.  chunk: one chunk of the merge, from the blocks read back from the temporary file to the blocks of the sorted file (see there).
 int mcx_bam_sort_part(mcx_ctx *, uint32_t n_reads, uint64_t n_bytes, mcx_sort_sink *sink, const uint8_t **d_sorted);

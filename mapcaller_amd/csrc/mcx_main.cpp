@@ -64,6 +64,8 @@ static void usage(const char *prog)
             "         -markdup      with -bam -sort: set flag bit 0x400 on duplicate records — pairs with both unclipped 5' ends and strands equal, single reads with one;\n"
             "                       the one with the highest sum of base qualities of 15 or more stays — decided on the GPU behind the last batch; 4 more bytes of host\n"
             "                       memory a record and 24 a pair until the merge; no optical distance, one library; not with -m\n"
+            "         -md           an MD:Z tag behind XS on every mapped line (what samtools calmd adds), its strings made on the GPU behind each batch's mapping; with -sam,\n"
+            "                       -gpu_sam, -bgzf, -bam and its -sort / -markdup / -index, and -m; not with -gpus N / -devices\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -176,6 +178,7 @@ int main(int argc, char **argv)
         else if (p == "-sort") want_sort = true;
         else if (p == "-index") want_index = true;
         else if (p == "-markdup") want_markdup = true;
+        else if (p == "-md") fo.device_sam |= MCX_SAM_MD;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
@@ -196,6 +199,7 @@ int main(int argc, char **argv)
     if (want_markdup && multi) { fprintf(stderr, "Error! -markdup takes one record a read: it cannot be combined with -m\n"); return 1; }
     if (want_markdup) fo.device_sam |= MCX_SAM_MARKDUP;
     if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
+    if (n_gpus > 1 && (fo.device_sam & MCX_SAM_MD)) { fprintf(stderr, "Error! -md makes its MD tags on one GPU: it cannot be combined with -gpus N / -devices\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the
     // early ones (a failed build leaves partial files behind it)

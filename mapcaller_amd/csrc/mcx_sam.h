@@ -128,12 +128,32 @@ static inline MCX_HD uint8_t sam_qual_byte(const SamRead &d, const SamTurn &t, u
     return !d.qual ? (uint8_t)'*' : t.qual_forward ? d.qual[k] : d.qual[d.rlen - 1 - k];
 }
 
-// one line: its bytes; the same written at o (returns the end)
-static inline MCX_HD uint64_t sam_one_len(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn)
+// A line's MD string in the batch's pool (mcx_md.h makes it; include/mcx.h: entry r is read r's own record, n_reads + i the -m extra i): its bytes, 0 without
+// a pool or a tag.  The tag goes behind XS — "\tMD:Z:" and the string, copied — ahead of the newline.
+static inline MCX_HD uint32_t sam_md_of(const mcx_sam_in &in, uint32_t entry, const uint8_t *&md)
 {
-    return (uint64_t)d.name_len + sam_head_len(rec, cigar, cn) + d.rlen + 1 + sam_qual_len(d, sam_turn(d, rec)) + sam_tags_len(rec);
+    md = nullptr;
+    if (!in.md || !in.md_off) return 0;
+    md = in.md + in.md_off[entry];
+    return in.md_off[entry + 1] - in.md_off[entry];
 }
-static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o)
+static inline MCX_HD uint32_t sam_md_len(uint32_t md_len) { return md_len ? 6 + md_len : 0; }
+static inline MCX_HD uint8_t *sam_md_lit(uint8_t *o) { return sam_lit(o, "\tMD:Z:"); } // (over the newline sam_tags_put ended the line with)
+
+// one line: its bytes; the same written at o (returns the end)
+static inline MCX_HD uint64_t sam_one_len(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint32_t md_len = 0)
+{
+    return (uint64_t)d.name_len + sam_head_len(rec, cigar, cn) + d.rlen + 1 + sam_qual_len(d, sam_turn(d, rec)) + sam_tags_len(rec) + sam_md_len(md_len);
+}
+static inline MCX_HD uint8_t *sam_md_put(uint8_t *o, const uint8_t *md, uint32_t md_len) // o: behind the line's newline
+{
+    if (!md_len) return o;
+    o = sam_md_lit(o - 1);
+    for (uint32_t k = 0; k < md_len; k++) *o++ = md[k];
+    *o++ = '\n';
+    return o;
+}
+static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o, const uint8_t *md = nullptr, uint32_t md_len = 0)
 {
     for (uint32_t k = 0; k < d.name_len; k++) *o++ = d.name[k];
     o = sam_head_put(rec, cigar, cn, o);
@@ -142,7 +162,7 @@ static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, 
     *o++ = '\t';
     const uint32_t ql = sam_qual_len(d, t);
     for (uint32_t k = 0; k < ql; k++) *o++ = sam_qual_byte(d, t, k);
-    return sam_tags_put(rec, o);
+    return sam_md_put(sam_tags_put(rec, o), md, md_len);
 }
 
 // -m: read r's extra lines (SamReport.cpp:364-488: every further candidate with the best score), none without x_index
@@ -157,20 +177,23 @@ static inline MCX_HD uint64_t sam_line_len(const mcx_sam_in &in, const SamContig
 {
     const SamRead d = sam_read_of(in, r);
     const mcx_aln rec = in.aln[r];
-    uint64_t n = sam_one_len(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn);
+    const uint8_t *md;
+    uint64_t n = sam_one_len(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, sam_md_of(in, r, md));
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; n += sam_one_len(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn); }
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; n += sam_one_len(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, sam_md_of(in, in.n_reads + i, md)); }
     return n;
 }
 static inline MCX_HD uint64_t sam_line_put(const mcx_sam_in &in, const SamContigs &cn, uint32_t r, uint8_t *out)
 {
     const SamRead d = sam_read_of(in, r);
     const mcx_aln rec = in.aln[r];
-    uint8_t *o = sam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, out);
+    const uint8_t *md;
+    uint32_t ml = sam_md_of(in, r, md);
+    uint8_t *o = sam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, out, md, ml);
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; o = sam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, o); }
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; ml = sam_md_of(in, in.n_reads + i, md); o = sam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, o, md, ml); }
     return (uint64_t)(o - out);
 }
 

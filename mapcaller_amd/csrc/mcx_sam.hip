@@ -51,7 +51,7 @@ __device__ inline void wave_sync()
 }
 
 // one line by one wavefront; returns its bytes
-__device__ inline uint32_t wave_line(const SamRead &d, const mcx_aln &rec, const uint32_t *cig, const SamContigs &cn, uint8_t *stage, uint8_t *dst, uint32_t lane)
+__device__ inline uint32_t wave_line(const SamRead &d, const mcx_aln &rec, const uint32_t *cig, const SamContigs &cn, uint8_t *stage, uint8_t *dst, uint32_t lane, const uint8_t *md, uint32_t ml)
 {
     const SamTurn t = sam_turn(d, rec);
     uint32_t ql = 1; // '*'
@@ -61,12 +61,16 @@ __device__ inline uint32_t wave_line(const SamRead &d, const mcx_aln &rec, const
         for (int s = 32; s; s >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)ql, s, 64); ql = o < ql ? o : ql; }
     }
     const uint32_t hl = sam_head_len(rec, cig, cn), tl = sam_tags_len(rec);
-    const uint32_t seq_at = d.name_len + hl, q_at = seq_at + d.rlen + 1, L = q_at + ql + tl;
+    const uint32_t seq_at = d.name_len + hl, q_at = seq_at + d.rlen + 1, md_at = q_at + ql + tl - 1, L = q_at + ql + tl + sam_md_len(ml); // (md_at: the tags' newline)
     const uint32_t sh = (uint32_t)((uintptr_t)dst & 15u);
     const bool staged = sh + L <= (uint32_t)kSamStage;
     uint8_t *o = staged ? stage + sh : dst; // (the staging is 16-byte aligned: o and dst sit alike within their 16 bytes; a line too long for it goes straight to its place)
     for (uint32_t k = lane; k < d.name_len; k += 64) o[k] = d.name[k];
-    if (lane == 0) { sam_head_put(rec, cig, cn, o + d.name_len); o[q_at - 1] = '\t'; sam_tags_put(rec, o + q_at + ql); }
+    if (lane == 0) {
+        sam_head_put(rec, cig, cn, o + d.name_len); o[q_at - 1] = '\t'; sam_tags_put(rec, o + q_at + ql);
+        if (ml) { sam_md_lit(o + md_at); o[L - 1] = '\n'; } // the MD tag goes over the newline; its string is the pool's
+    }
+    for (uint32_t k = lane; k < ml; k += 64) o[md_at + 6 + k] = md[k];
     for (uint32_t k = lane; k < d.rlen; k += 64) o[seq_at + k] = sam_seq_byte(d, t, k);
     for (uint32_t k = lane; k < ql; k += 64) o[q_at + k] = sam_qual_byte(d, t, k);
     if (!staged) return L;
@@ -90,12 +94,15 @@ __global__ void __launch_bounds__(64 * kSamWaves) k_sam_write(mcx_sam_in in, Sam
     const SamRead d = sam_read_of(in, r);
     uint8_t *dst = text + line_off[r];
     const mcx_aln rec = in.aln[r];
-    dst += wave_line(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, stage[w], dst, lane);
+    const uint8_t *md;
+    uint32_t ml = sam_md_of(in, r, md);
+    dst += wave_line(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, stage[w], dst, lane, md, ml);
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
     for (uint32_t i = lo; i < hi; i++) {
         const mcx_aln x = in.x_recs[i];
-        dst += wave_line(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, stage[w], dst, lane);
+        ml = sam_md_of(in, in.n_reads + i, md);
+        dst += wave_line(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, stage[w], dst, lane, md, ml);
     }
 }
 
@@ -176,6 +183,7 @@ extern "C" int mcx_sam_format(mcx_ctx *c, const mcx_sam_in *in, uint8_t *text, u
     const uint64_t n_x = in->x_index ? in->x_index[n] : 0;
     for (uint64_t i = 0; i < n_x; i++) x_words = std::max<uint64_t>(x_words, (uint64_t)(uint32_t)in->x_recs[i].cigar_off + (uint64_t)std::max(in->x_recs[i].n_cigar, 0));
     struct Piece { const void *src; uint64_t bytes; void **dst; };
+    const bool with_md = in->md && in->md_off; // the lines' MD strings: one entry per read and per extra, and the total
     mcx_sam_in d = *in;
     uint64_t *d_off64 = nullptr; uint8_t *d_text = nullptr;
     const Piece pieces[] = {
@@ -183,6 +191,7 @@ extern "C" int mcx_sam_format(mcx_ctx *c, const mcx_sam_in *in, uint8_t *text, u
         {in->names, in->name_off[n], (void **)&d.names}, {in->name_off, (n + 1) * 4, (void **)&d.name_off},
         {in->aln, n * sizeof(mcx_aln), (void **)&d.aln}, {in->cigar, words * 4, (void **)&d.cigar},
         {in->x_index, in->x_index ? (n + 1) * 4 : 0, (void **)&d.x_index}, {in->x_recs, n_x * sizeof(mcx_aln), (void **)&d.x_recs}, {in->x_cigar, x_words * 4, (void **)&d.x_cigar},
+        {with_md ? in->md : nullptr, with_md ? in->md_off[n + n_x] : 0, (void **)&d.md}, {with_md ? in->md_off : nullptr, with_md ? (n + n_x + 1) * 4 : 0, (void **)&d.md_off},
     };
     uint64_t all = 0;
     for (const Piece &p : pieces) all += (p.bytes + 15) / 16 * 16 + 16;
@@ -260,10 +269,11 @@ static int sam_part(mcx_ctx *c, const uint8_t *d_bases, const uint32_t *d_off, u
     in.bases = d_bases; in.off = d_off;
     in.qual = on_device ? qual : qual ? st->d_qual : nullptr; in.names = on_device ? names : st->d_names; in.name_off = on_device ? name_off : st->d_name_off;
     in.aln = d_aln; in.cigar = d_cigar; in.n_reads = n_reads; in.paired = paired;
-    if (mcx_ctx_multi(c)) {
-        uint32_t n_recs = 0, n_words = 0;
-        if ((rc = mcx_multi_lines(c, &in.x_index, &in.x_recs, &in.x_cigar, &n_recs, &n_words))) return rc;
-    }
+    uint32_t n_recs = 0, n_words = 0;
+    if (mcx_ctx_multi(c) && (rc = mcx_multi_lines(c, &in.x_index, &in.x_recs, &in.x_cigar, &n_recs, &n_words))) return rc;
+    // -md: the lines' MD strings first, into a pool of the state's own that the formatter copies them from
+    uint64_t md_bytes = 0;
+    if (st->want_md && (rc = mcx_md_part_dev(c, &in, in.x_index ? n_recs : 0, &md_bytes))) return rc;
     // the size first (nothing is written into a text buffer that is too small), then room for it on both sides; -bam: the part's records instead of its text
     const bool bam = bgzf && bgzf->bam;
     uint64_t total = 0, dropped = 0;

@@ -88,12 +88,15 @@ struct SamState {
     float ms[3] = {0, 0, 0}; // the last call's length kernel, scan, write kernel
     uint8_t *d_names = nullptr, *d_qual = nullptr, *d_text = nullptr, *d_bgzf = nullptr; uint32_t *d_name_off = nullptr; // (d_bgzf: -bgzf, the text's blocks)
     uint64_t cap_names = 0, cap_qual = 0, cap_text = 0, cap_name_off = 0, cap_bgzf = 0;
+    uint8_t *d_md = nullptr; uint32_t *d_md_off = nullptr; uint64_t cap_md = 0, cap_md_off = 0; // -md (mcx_md.hip): a batch part's MD strings and their offsets
+    bool want_md = false;                                                                        // the file front end's -md is on (mcx_md_set)
+    float md_ms[3] = {0, 0, 0};                                                                 // the last mcx_md[_dev]'s length kernel, scan, write kernel
     SortBufs sort;
     BaiBufs bai;
     DupBufs dup;
     ~SamState()
     {
-        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf};
+        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf, d_md, d_md_off};
         for (void *q : p) if (q) (void)hipFree(q);
         if (h_total) (void)hipHostFree(h_total);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
