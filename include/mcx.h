@@ -481,6 +481,36 @@ int mcx_sam_format(mcx_ctx *, const mcx_sam_in *in, uint8_t *text, uint64_t cap,
  * batch; *n_bytes their size, MCX_ERR_CAPACITY (nothing written) when cap is smaller. */
 int mcx_sam_header(const mcx_index *, char *out, uint64_t cap, uint64_t *n_bytes);
 
+/* ---- Read-group and mate tags ------------------------------------------------------------------------
+ * What `samtools addreplacerg` and `samtools fixmate -m` add to a finished file — which the reference does not write —, made inside the formatters while a pair's
+ * two records are neighbours in HBM.  Two independent switches (mapcaller-mi355x -rg, -mc); without them every byte is what it was.
+ * The read-group line (mcx_rg_parse; bwa mem -R's form): the argument as given, every two-character sequence "\t" replaced by a TAB.  It must begin with "@RG" TAB;
+ *   every further TAB-separated field is two characters of [A-Za-z][A-Za-z0-9], ':' and at least one byte; exactly one field is ID; no byte below 0x20 other than
+ *   TAB and none 0x7f; the ID at most 255 bytes, the line at most 4096.  Anything else is MCX_ERR_ARG, the reason in mcx_last_error.
+ * Header: the line, with a newline, is the last line of the header text, behind what mcx_sam_header writes (mcx_sam_header_rg, mcx_bam_header_rg: l_text grows by it).
+ * RG:Z:<ID> goes on every line, mapped or not, the -m extras included.
+ * MC:Z and MQ:i: read r of a batch mapped as pairs has the mate m = r ^ 1.  Both tags are written iff paired, m < n_reads, the mate's own record is mapped
+ *   (chr >= 0 and n_cigar > 0) and the line's own FLAG has bit 0x8 clear — where the reference calls the mate unmapped an MC would contradict the flag (some lines have
+ *   a mapped mate and 0x8 set all the same: they get neither).  An unmapped read whose mate is mapped gets both.  MC is the mate's CIGAR exactly as the mate's own line
+ *   prints it in column 6 (the same code prints both), MQ the mate's mapq.  A batch of single reads gets neither.  FLAG, RNEXT, PNEXT and TLEN stay the reference's.
+ *   An -m extra is paired with another candidate of the mate than the one whose CIGAR is held: mate_tags with a non-null x_index is MCX_ERR_UNSUPPORTED, nothing written.
+ * Order: mapped lines NM AS XS [MD] [MC MQ] [RG]; unmapped lines AS XS [MC MQ] [RG].
+ * BAM: 'M' 'C' 'Z' the string NUL; MQ as the smallest integer type that holds it ('C' for 0 .. 255); 'R' 'G' 'Z' the ID NUL; block_size grows by those bytes.
+ * mcx_sam_tags travels beside mcx_sam_in (whose layout stays): rg the ID's bytes — a device pointer for the _dev calls, staged inside for the host forms —, NULL
+ * or rg_len 0: no RG tag; mate_tags != 0: MC and MQ.  A NULL mcx_sam_tags is both off: mcx_sam_format[_dev] and mcx_bam_format[_dev] are these calls with NULL. */
+typedef struct mcx_sam_tags { const uint8_t *rg; uint32_t rg_len; int32_t mate_tags; } mcx_sam_tags;
+int mcx_sam_format_tags_dev(mcx_ctx *, const mcx_sam_in *d_in, const mcx_sam_tags *tags, uint8_t *d_text, uint64_t cap, uint64_t *d_line_off, uint64_t *n_bytes);
+int mcx_sam_format_tags(mcx_ctx *, const mcx_sam_in *in, const mcx_sam_tags *tags, uint8_t *text, uint64_t cap, uint64_t *line_off, uint64_t *n_bytes);
+int mcx_bam_format_tags_dev(mcx_ctx *, const mcx_sam_in *d_in, const mcx_sam_tags *tags, uint8_t *d_out, uint64_t cap, uint64_t *d_rec_off, uint64_t *n_bytes, uint64_t *n_dropped);
+int mcx_bam_format_tags(mcx_ctx *, const mcx_sam_in *in, const mcx_sam_tags *tags, uint8_t *out, uint64_t cap, uint64_t *rec_off, uint64_t *n_bytes, uint64_t *n_dropped);
+/* The -rg argument checked and taken apart: line[0 .. cap) receives the line with real TABs, no newline and no NUL, *line_len its size, *id_at / *id_len where
+ * its ID lies in it (any of the four may be NULL).  MCX_ERR_ARG with the reason in words; MCX_ERR_CAPACITY (nothing written) when cap is smaller than the line. */
+int mcx_rg_parse(const char *arg, char *line, uint64_t cap, uint64_t *line_len, uint32_t *id_at, uint32_t *id_len);
+/* mcx_sam_header's bytes, and mcx_bam_header's (sorted != 0: mcx_bam_header_sorted's), with rg_line (NUL-terminated, real TABs, no newline: checked as by
+ * mcx_rg_parse) as the last line of the text.  A NULL rg_line gives those calls' bytes. */
+int mcx_sam_header_rg(const mcx_index *, const char *rg_line, char *out, uint64_t cap, uint64_t *n_bytes);
+int mcx_bam_header_rg(const mcx_index *, const char *rg_line, int sorted, uint8_t *out, uint64_t cap, uint64_t *n_bytes);
+
 /* ---- MD:Z strings ------------------------------------------------------------------------------------
  * The string that says, against the CIGAR, which reference bases a line mismatches or deletes — what `samtools calmd` writes, which the reference does not — made in
  * HBM from the mcx_sam_in the formatters take and the index's genome.  MD is defined for a mapped line (chr >= 0, n_cigar > 0) by walking its CIGAR over the
@@ -786,6 +816,12 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * made in HBM from the part's reads, records, CIGAR pool and (-m) extras, which carry their own; with bit 1 they feed the device formatters where they lie (SAM
  * text, BGZF, BAM; -sort, -markdup and -index see only longer records), without it they come to the host with the part's records and the host formatter appends
  * them.  Without the bit every file is byte for byte what it was.  MCX_ERR_UNSUPPORTED before anything is opened: shard_count > 1.
+ * bit 128 (MCX_SAM_MC; mapcaller-mi355x -mc) puts MC:Z and MQ:i on the lines of pairs, and read_group of mcx_map_files_rg (mapcaller-mi355x -rg) an @RG line into the
+ * header and RG:Z on every line: the rule stands at mcx_sam_tags.  The ID goes to HBM once per run and the device formatters make the tags where they make the
+ * line (SAM text, BGZF, BAM; -sort, -markdup and -index see only longer records); without bit 1 the host formatter writes the same bytes — a pair's mates are always
+ * in the same part of a batch.  The header line is written on every route, also by the merge of a sorted file; an append_sam library gets the same group's tags and
+ * no second header line.  MCX_ERR_UNSUPPORTED before anything is opened: either of them with shard_count > 1; bit 128 on a context with -m (mcx_ctx_set_multi);
+ * read_group works with -m.  A read_group that mcx_rg_parse would refuse: MCX_ERR_ARG before anything is opened.
  * Debug override (no result depends on it): MCX_BGZF_BLOCK=n, the bytes of text per BGZF block (1 .. 65280, the default; the tests put many blocks into small files with it).
  * Debug override (no result depends on it): MCX_RESIDENT_LAUNCH_BYTES=n, the bytes of text one inflate launch of the resident route makes (default 128 MB: sixteen
  * stretches; smaller than a stretch: the stretch takes several launches — the tests put many launch and carry boundaries into small files with it). */
@@ -807,10 +843,14 @@ enum mcx_sam_bits {
     MCX_SAM_SORT = 8,   /* ... in coordinate order (only with MCX_SAM_BAM) */
     MCX_SAM_INDEX = 16, /* ... with its .bai written beside it (only with MCX_SAM_SORT) */
     MCX_SAM_MARKDUP = 32, /* ... and flag bit 0x400 on its duplicate records (only with MCX_SAM_SORT) */
-    MCX_SAM_MD = 64      /* an MD:Z tag on every mapped line, made on the device (mcx_md_dev); with any of the above, and with none: the host formatter appends it */
+    MCX_SAM_MD = 64,     /* an MD:Z tag on every mapped line, made on the device (mcx_md_dev); with any of the above, and with none: the host formatter appends it */
+    MCX_SAM_MC = 128     /* MC:Z and MQ:i on the lines of pairs (the rule: mcx_sam_tags); with any of the above, and with none */
 };
 void mcx_file_opts_default(mcx_file_opts *);
 int mcx_map_files_ex(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *sam_path, mcx_stats *stats);
+/* mcx_map_files_ex with a read group: read_group is the validated @RG line with real TABs and no newline (mcx_rg_parse's line, NUL-terminated); NULL: none, and
+ * the call is mcx_map_files_ex.  (mcx_file_opts keeps its layout: the line travels beside it.) */
+int mcx_map_files_rg(mcx_ctx *, const char *fq1, const char *fq2, const mcx_file_opts *, const char *read_group, const char *sam_path, mcx_stats *stats);
 /* Which stages of the context's last mcx_map_files* call ran on the device, per read file (route[1] = 0 for one file): the opt-in switches that do not apply
  * to an input are ignored without a word, and the output is the same bytes by design.  MCX_TIMING=1 prints it. */
 enum mcx_route {

@@ -79,6 +79,7 @@ SYMBOLS = [
     "mcx_bam_dup_units_dev", "mcx_dup_resolve_dev", "mcx_bam_dup_mark_dev", "mcx_markdup_last_ms", "mcx_files_markdup_stats",
     "mcx_pass_last_shape",
     "mcx_md_dev", "mcx_md", "mcx_md_last_ms",
+    "mcx_sam_format_tags_dev", "mcx_sam_format_tags", "mcx_bam_format_tags_dev", "mcx_bam_format_tags", "mcx_rg_parse", "mcx_sam_header_rg", "mcx_bam_header_rg", "mcx_map_files_rg",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -258,6 +259,11 @@ class SamIn(C.Structure):
                [("n_reads", C.c_uint32), ("paired", C.c_int32), ("md", C.c_void_p), ("md_off", C.c_void_p)]  # (md / md_off: mcx_md[_dev]'s strings; null: no MD:Z tag)
 
 
+class SamTags(C.Structure):
+    """mcx_sam_tags: what travels beside mcx_sam_in for -rg / -mc — the read group's ID (host or device bytes; null: no RG:Z) and the MC:Z / MQ:i switch"""
+    _fields_ = [("rg", C.c_void_p), ("rg_len", C.c_uint32), ("mate_tags", C.c_int32)]
+
+
 ERR_IO, ERR_ARG = -1, -2  # MCX_ERR_IO, MCX_ERR_ARG
 ERR_CAPACITY = -4  # MCX_ERR_CAPACITY
 # mcx_deflate_member: one BGZF member's raw deflate stream src[src_off:][:src_len] -> dst[dst_off:][:isize], with the CRC-32 of its text
@@ -276,6 +282,7 @@ DUP_NONE, DUP_FRAGMENT, DUP_PAIR, DUP_SECOND_MATE = 0, 1, 2, 4  # mcx_dup_unit.k
 DUP_UNIT_DTYPE = np.dtype([("end0", "<u8"), ("end1", "<u8"), ("score", "<u4"), ("kind", "<u4")])  # mcx_dup_unit, 24 bytes
 SAM_INDEX = 16  # (mcx_sam_bits, below)
 SAM_MD = 64  # (mcx_sam_bits: an MD:Z tag on every mapped line; with the host formatter too)
+SAM_MC = 128  # (mcx_sam_bits: MC:Z and MQ:i on the lines of pairs; with the host formatter too)
 ERR_UNSUPPORTED = -5  # MCX_ERR_UNSUPPORTED
 SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_opts.device_sam); SAM_INDEX = 16 above
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
@@ -515,6 +522,20 @@ def lib() -> C.CDLL:
     for f in (L.mcx_md_dev, L.mcx_md):
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+    for f in (L.mcx_sam_format_tags_dev, L.mcx_sam_format_tags):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.POINTER(SamTags), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+    for f in (L.mcx_bam_format_tags_dev, L.mcx_bam_format_tags):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(SamIn), C.POINTER(SamTags), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mcx_rg_parse.restype = C.c_int
+    L.mcx_rg_parse.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.mcx_sam_header_rg.restype = C.c_int
+    L.mcx_sam_header_rg.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_bam_header_rg.restype = C.c_int
+    L.mcx_bam_header_rg.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_map_files_rg.restype = C.c_int
+    L.mcx_map_files_rg.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(FileOpts), C.c_char_p, C.c_char_p, C.POINTER(Stats)]
     L.mcx_md_last_ms.restype = C.c_int
     L.mcx_md_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_bam_last_ms.restype = C.c_int
@@ -716,7 +737,7 @@ class Mapper:
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
                   device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
-                  index: bool = False, markdup: bool = False, md: bool = False) -> dict:
+                  index: bool = False, markdup: bool = False, md: bool = False, read_group: Optional[str] = None, mate_tags: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
         keep one insert-size trajectory and one duplicate-cap order, and write the batches' lines at their
@@ -737,13 +758,16 @@ class Mapper:
         part, resolved once on the device behind the last batch, the bits set in the merge; ERR_UNSUPPORTED without ``sort`` and on a mapper with ``multi``; ``markdup_stats()`` says what was found.
         ``md`` = -md: an MD:Z tag behind XS on every mapped line, its strings made on the device behind each part's mapping (mcx_md_dev) — with every output above and
         with the host formatter; ERR_UNSUPPORTED in a sharded run.
+        ``read_group`` = -rg: an @RG line in bwa mem -R's form (``\\t`` or real TABs between the fields, exactly one ID; checked by rg_parse: ERR_ARG) that ends the header,
+        and RG:Z:<ID> on every line; ``mate_tags`` = -mc: MC:Z and MQ:i on the lines of pairs whose mate is mapped and whose FLAG has 0x8 clear (the rule: mcx.h at
+        mcx_sam_tags) — both with every output above and with the host formatter; ERR_UNSUPPORTED in a sharded run, ``mate_tags`` also on a mapper with ``multi``.
         ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
         lib().mcx_file_opts_default(C.byref(fo))
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
-        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0) | (SAM_MD if md else 0)
+        fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0) | (SAM_MD if md else 0) | (SAM_MC if mate_tags else 0)
         fo.device_inflate = int(device_inflate)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
@@ -754,7 +778,8 @@ class Mapper:
                 raise ValueError("a sharded run needs an exchange (api.dist_exchange())")
             fo.shard_rank, fo.shard_count = int(shard[0]), int(shard[1])
             fo.exchange = C.pointer(exchange)
-        _check(lib().mcx_map_files_ex(self._h, fq1.encode(), (fq2 or "").encode() or None, C.byref(fo), (sam or "").encode() or None,
+        rg = rg_parse(read_group)[0] if read_group is not None else None
+        _check(lib().mcx_map_files_rg(self._h, fq1.encode(), (fq2 or "").encode() or None, C.byref(fo), rg, (sam or "").encode() or None,
                                       C.byref(st)), "mcx_map_files_ex")
         return st.as_dict()
 
@@ -815,36 +840,40 @@ class Mapper:
         return ms[0], ms[1], ms[2]
 
     def sam_text(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
-                 pool: np.ndarray, extras=None, md: bool = False) -> bytes:
+                 pool: np.ndarray, extras=None, md: bool = False, read_group: Optional[str] = None, mate_tags: bool = False) -> bytes:
         """The SAM lines of a mapped batch, made on the device (mcx_sam_format).  ``bases`` / ``off`` as given to map_batch, ``names`` the
         QNAMEs, ``quals`` per read the bytes of its quality line that count (at most the read's length; shorter ones are NUL-padded here;
         None: QUAL is '*'), ``aln`` the records and ``pool`` CIGAR words such that read r's are pool[aln[r].cigar_off:][:n_cigar] — map_batch's
-        list of per-read arrays is accepted too —, ``extras`` what multi_lines returns.  ``md``: an MD:Z tag behind XS on every mapped line (mcx_md)."""
+        list of per-read arrays is accepted too —, ``extras`` what multi_lines returns.  ``md``: an MD:Z tag behind XS on every mapped line (mcx_md).
+        ``read_group`` (an @RG line as map_files takes it): RG:Z:<ID> on every line; ``mate_tags``: MC:Z and MQ:i by the rule at mcx_sam_tags (not with ``extras``)."""
         si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
         if md and si.n_reads:
             self._md_into(si, keep)
+        tg = _sam_tags(read_group, mate_tags, keep)
         nb = C.c_uint64()
-        rc = lib().mcx_sam_format(self._h, C.byref(si), None, 0, None, C.byref(nb))
+        rc = lib().mcx_sam_format_tags(self._h, C.byref(si), tg, None, 0, None, C.byref(nb))
         if rc not in (0, ERR_CAPACITY):
             _check(rc, "mcx_sam_format")
         text = np.zeros(max(1, nb.value), dtype=np.uint8)
-        _check(lib().mcx_sam_format(self._h, C.byref(si), text.ctypes.data, nb.value, None, C.byref(nb)), "mcx_sam_format")
+        _check(lib().mcx_sam_format_tags(self._h, C.byref(si), tg, text.ctypes.data, nb.value, None, C.byref(nb)), "mcx_sam_format")
         return text[:nb.value].tobytes()
 
     def bam_records(self, bases: np.ndarray, off: np.ndarray, names: List[bytes], quals: Optional[List[bytes]], paired: bool, aln: np.ndarray,
-                    pool: np.ndarray, extras=None, md: bool = False) -> Tuple[bytes, int]:
+                    pool: np.ndarray, extras=None, md: bool = False, read_group: Optional[str] = None, mate_tags: bool = False) -> Tuple[bytes, int]:
         """The uncompressed BAM records of a mapped batch, made on the device (mcx_bam_format), from what sam_text takes: (the records back to
         back — the record of every line sam_text would give, in its order —, the lines that made none: a name of 252 bytes or more, a QUAL that
-        is not '*' and not as long as the read).  ``md``: an MD:Z tag behind XS in every mapped record (mcx_md)."""
+        is not '*' and not as long as the read).  ``md``: an MD:Z tag behind XS in every mapped record (mcx_md);
+        ``read_group`` and ``mate_tags`` as sam_text takes them: RG:Z, and MC:Z / MQ:i, behind it."""
         si, keep = _sam_in(bases, off, names, quals, paired, aln, pool, extras)
         if md and si.n_reads:
             self._md_into(si, keep)
+        tg = _sam_tags(read_group, mate_tags, keep)
         nb, nd = C.c_uint64(), C.c_uint64()
-        rc = lib().mcx_bam_format(self._h, C.byref(si), None, 0, None, C.byref(nb), C.byref(nd))
+        rc = lib().mcx_bam_format_tags(self._h, C.byref(si), tg, None, 0, None, C.byref(nb), C.byref(nd))
         if rc not in (0, ERR_CAPACITY):
             _check(rc, "mcx_bam_format")
         out = np.zeros(max(1, nb.value), dtype=np.uint8)
-        _check(lib().mcx_bam_format(self._h, C.byref(si), out.ctypes.data, nb.value, None, C.byref(nb), C.byref(nd)), "mcx_bam_format")
+        _check(lib().mcx_bam_format_tags(self._h, C.byref(si), tg, out.ctypes.data, nb.value, None, C.byref(nb), C.byref(nd)), "mcx_bam_format")
         return out[:nb.value].tobytes(), int(nd.value)
 
     def sort_stats(self) -> dict:
@@ -1476,21 +1505,48 @@ def _sam_in(bases, off, names, quals, paired, aln, pool, extras):
     return si, keep
 
 
-def sam_header(index: "Index") -> bytes:
-    """The @PG / @SQ lines the file front end writes ahead of the first batch (mcx_sam_header)."""
+def rg_parse(arg: str) -> Tuple[bytes, bytes]:
+    """mcx_rg_parse: (the @RG line with real TABs and no newline, its ID) of a -rg argument in bwa mem -R's form; McxError (ERR_ARG) says why it is refused"""
+    buf = C.create_string_buffer(4097)
+    nb, at, n = C.c_uint64(), C.c_uint32(), C.c_uint32()
+    _check(lib().mcx_rg_parse(arg.encode("latin-1") if isinstance(arg, str) else arg, buf, 4096, C.byref(nb), C.byref(at), C.byref(n)), "mcx_rg_parse")
+    line = buf.raw[:nb.value]
+    return line, line[at.value:at.value + n.value]
+
+
+def _sam_tags(read_group, mate_tags, keep):
+    """the SamTags of Mapper.sam_text / bam_records (None: both off)"""
+    if read_group is None and not mate_tags:
+        return None
+    tg = SamTags()
+    tg.mate_tags = int(bool(mate_tags))
+    if read_group is not None:
+        rid = np.frombuffer(rg_parse(read_group)[1] + b"\0", dtype=np.uint8).copy()
+        keep.append(rid)
+        tg.rg, tg.rg_len = rid.ctypes.data, rid.size - 1
+    return C.pointer(tg)
+
+
+def sam_header(index: "Index", read_group: Optional[str] = None) -> bytes:
+    """The @PG / @SQ lines the file front end writes ahead of the first batch (mcx_sam_header); ``read_group``: with its @RG line as the last (mcx_sam_header_rg)."""
+    rg = rg_parse(read_group)[0] if read_group is not None else None
     nb = C.c_uint64()
-    rc = lib().mcx_sam_header(index._h, None, 0, C.byref(nb))
+    rc = lib().mcx_sam_header_rg(index._h, rg, None, 0, C.byref(nb))
     if rc not in (0, ERR_CAPACITY):
         _check(rc, "mcx_sam_header")
     buf = C.create_string_buffer(max(1, nb.value))
-    _check(lib().mcx_sam_header(index._h, buf, nb.value, C.byref(nb)), "mcx_sam_header")
+    _check(lib().mcx_sam_header_rg(index._h, rg, buf, nb.value, C.byref(nb)), "mcx_sam_header")
     return buf.raw[:nb.value]
 
 
-def bam_header(index: "Index", sorted: bool = False) -> bytes:
+def bam_header(index: "Index", sorted: bool = False, read_group: Optional[str] = None) -> bytes:
     """The uncompressed BAM header the file front end writes (as BGZF blocks) ahead of the first batch with ``bam``: magic, sam_header's text, the contigs (mcx_bam_header);
     ``sorted``: the header of a ``sort`` run, whose text begins with @HD VN:1.6 SO:coordinate (mcx_bam_header_sorted)."""
-    call, what = (lib().mcx_bam_header_sorted, "mcx_bam_header_sorted") if sorted else (lib().mcx_bam_header, "mcx_bam_header")
+    if read_group is not None:  # ... with the @RG line as the last line of the text (mcx_bam_header_rg)
+        rg, what = rg_parse(read_group)[0], "mcx_bam_header_rg"
+        call = lambda h, out, cap, nb: lib().mcx_bam_header_rg(h, rg, int(sorted), out, cap, nb)
+    else:
+        call, what = (lib().mcx_bam_header_sorted, "mcx_bam_header_sorted") if sorted else (lib().mcx_bam_header, "mcx_bam_header")
     nb = C.c_uint64()
     rc = call(index._h, None, 0, C.byref(nb))
     if rc not in (0, ERR_CAPACITY):

@@ -106,23 +106,42 @@ static inline MCX_HD bool bam_keep(const SamRead &d, const mcx_aln &rec)
 
 // where the pieces of a kept record lie, from its first byte
 struct BamLayout { uint32_t cigar_at, seq_at, qual_at, tags_at, total; };
-static inline MCX_HD uint32_t bam_md_len(uint32_t md_len) { return md_len ? 4 + md_len : 0; } // 'M' 'D' 'Z', the pool's string (sam_md_of), NUL: behind the XS tag
-static inline MCX_HD uint8_t *bam_md_put(uint8_t *o, const uint8_t *md, uint32_t md_len)
+// the tags behind XS (SamTail; include/mcx.h at mcx_sam_tags): 'M' 'D' 'Z' the pool's string NUL; 'M' 'C' 'Z' the mate's CIGAR as text NUL, MQ as bam_tag_put makes it;
+// 'R' 'G' 'Z' the ID NUL
+static inline MCX_HD uint32_t bam_md_len(uint32_t md_len) { return md_len ? 4 + md_len : 0; }
+static inline MCX_HD uint32_t bam_mc_len(const SamTail &t) { return t.mc_n ? 4 + sam_cigar_len(t.mc, t.mc_n) + bam_tag_len(t.mq) : 0; }
+static inline MCX_HD uint32_t bam_rg_len(uint32_t rg_len) { return rg_len ? 4 + rg_len : 0; }
+static inline MCX_HD uint32_t bam_tail_len(const SamTail &t) { return bam_md_len(t.md_len) + bam_mc_len(t) + bam_rg_len(t.rg_len); }
+static inline MCX_HD uint8_t *bam_mc_put(uint8_t *o, const SamTail &t) // (mc_n > 0)
 {
-    if (!md_len) return o;
-    *o++ = 'M'; *o++ = 'D'; *o++ = 'Z';
-    for (uint32_t k = 0; k < md_len; k++) *o++ = md[k];
+    *o++ = 'M'; *o++ = 'C'; *o++ = 'Z';
+    o = sam_cigar_put(o, t.mc, t.mc_n);
     *o++ = 0;
+    return bam_tag_put(o, 'M', 'Q', t.mq);
+}
+static inline MCX_HD uint8_t *bam_tail_put(uint8_t *o, const SamTail &t)
+{
+    if (t.md_len) {
+        *o++ = 'M'; *o++ = 'D'; *o++ = 'Z';
+        for (uint32_t k = 0; k < t.md_len; k++) *o++ = t.md[k];
+        *o++ = 0;
+    }
+    if (t.mc_n) o = bam_mc_put(o, t);
+    if (t.rg_len) {
+        *o++ = 'R'; *o++ = 'G'; *o++ = 'Z';
+        for (uint32_t k = 0; k < t.rg_len; k++) *o++ = t.rg[k];
+        *o++ = 0;
+    }
     return o;
 }
-static inline MCX_HD BamLayout bam_layout(const SamRead &d, const mcx_aln &rec, uint32_t md_len = 0)
+static inline MCX_HD BamLayout bam_layout(const SamRead &d, const mcx_aln &rec, const SamTail &tail)
 {
     BamLayout l;
     l.cigar_at = (uint32_t)kBamFixed + d.name_len + 1;
     l.seq_at = l.cigar_at + 4 * bam_n_cigar(rec);
     l.qual_at = l.seq_at + (d.rlen + 1) / 2;
     l.tags_at = l.qual_at + d.rlen;
-    l.total = l.tags_at + bam_tags_len(rec) + bam_md_len(md_len);
+    l.total = l.tags_at + bam_tags_len(rec) + bam_tail_len(tail);
     return l;
 }
 
@@ -155,48 +174,46 @@ static inline MCX_HD uint8_t bam_seq_out(const SamRead &d, const SamTurn &t, uin
 static inline MCX_HD uint8_t bam_qual_out(const SamRead &d, const SamTurn &t, bool star, uint32_t k) { return star ? (uint8_t)0xff : (uint8_t)(sam_qual_byte(d, t, k) - 33); }
 
 // one line's record: its bytes (0: the line is dropped); the same written at o (returns the end)
-static inline MCX_HD uint64_t bam_one_len(const SamRead &d, const mcx_aln &rec, uint32_t md_len = 0)
+static inline MCX_HD uint64_t bam_one_len(const SamRead &d, const mcx_aln &rec, const SamTail &tail)
 {
-    return bam_keep(d, rec) ? bam_layout(d, rec, md_len).total : 0;
+    return bam_keep(d, rec) ? bam_layout(d, rec, tail).total : 0;
 }
-static inline MCX_HD uint8_t *bam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, uint8_t *o, const uint8_t *md = nullptr, uint32_t md_len = 0)
+static inline MCX_HD uint8_t *bam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, uint8_t *o, const SamTail &tail)
 {
     const SamTurn t = sam_turn(d, rec);
     const uint32_t ql = sam_qual_len(d, t);
     if (!bam_keep_ql(d, t, ql)) return o;
     const bool star = bam_qual_star(d, t, ql);
-    const BamLayout l = bam_layout(d, rec, md_len);
+    const BamLayout l = bam_layout(d, rec, tail);
     bam_fixed_put(d, rec, cigar, l.total, o);
     for (uint32_t k = 0; k < d.name_len; k++) o[kBamFixed + k] = d.name[k];
     o[kBamFixed + d.name_len] = 0;
     for (uint32_t k = l.cigar_at; k < l.seq_at; k++) o[k] = bam_cigar_byte(cigar, k - l.cigar_at);
     for (uint32_t k = l.seq_at; k < l.qual_at; k++) o[k] = bam_seq_out(d, t, k - l.seq_at);
     for (uint32_t k = 0; k < d.rlen; k++) o[l.qual_at + k] = bam_qual_out(d, t, star, k);
-    return bam_md_put(bam_tags_put(rec, o + l.tags_at), md, md_len);
+    return bam_tail_put(bam_tags_put(rec, o + l.tags_at), tail);
 }
 
 // read r's record(s): the record of unique mode, then its extras' with the same name, bases and quality; *dropped: the lines among them that made none
-static inline MCX_HD uint64_t bam_rec_len(const mcx_sam_in &in, uint32_t r, uint32_t *dropped)
-{
-    const SamRead d = sam_read_of(in, r);
-    const uint8_t *md;
-    uint64_t n = bam_one_len(d, in.aln[r], sam_md_of(in, r, md));
-    uint32_t none = n ? 0u : 1u, lo, hi;
-    sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const uint64_t m = bam_one_len(d, in.x_recs[i], sam_md_of(in, in.n_reads + i, md)); n += m; none += m ? 0u : 1u; }
-    *dropped = none;
-    return n;
-}
-static inline MCX_HD uint64_t bam_rec_put(const mcx_sam_in &in, uint32_t r, uint8_t *out)
+static inline MCX_HD uint64_t bam_rec_len(const mcx_sam_in &in, uint32_t r, uint32_t *dropped, const mcx_sam_tags &tg = mcx_sam_tags())
 {
     const SamRead d = sam_read_of(in, r);
     const mcx_aln rec = in.aln[r];
-    const uint8_t *md;
-    uint32_t ml = sam_md_of(in, r, md);
-    uint8_t *o = bam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, out, md, ml);
+    uint64_t n = bam_one_len(d, rec, sam_tail_of(in, tg, r, r, rec, false));
+    uint32_t none = n ? 0u : 1u, lo, hi;
+    sam_extras_of(in, r, lo, hi);
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; const uint64_t m = bam_one_len(d, x, sam_tail_of(in, tg, in.n_reads + i, r, x, true)); n += m; none += m ? 0u : 1u; }
+    *dropped = none;
+    return n;
+}
+static inline MCX_HD uint64_t bam_rec_put(const mcx_sam_in &in, uint32_t r, uint8_t *out, const mcx_sam_tags &tg = mcx_sam_tags())
+{
+    const SamRead d = sam_read_of(in, r);
+    const mcx_aln rec = in.aln[r];
+    uint8_t *o = bam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, out, sam_tail_of(in, tg, r, r, rec, false));
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; ml = sam_md_of(in, in.n_reads + i, md); o = bam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, o, md, ml); }
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; o = bam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, o, sam_tail_of(in, tg, in.n_reads + i, r, x, true)); }
     return (uint64_t)(o - out);
 }
 

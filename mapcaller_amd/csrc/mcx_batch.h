@@ -2,6 +2,7 @@
 // with its page-locked buffers) and the host formatter over it: SAM text as GeneratePairedSamStream / GenerateSingleSamStream make it.
 #pragma once
 #include "mcx_reader.h"
+#include "mcx_sam.h"
 
 namespace mcx { namespace files {
 
@@ -59,6 +60,9 @@ struct Batch {
     // off[part's reads + i] (the layout of mcx_md_dev)
     struct Md { std::vector<uint8_t> bytes; std::vector<uint32_t> off; } md[2];
     bool has_md = false;
+    // -rg / -mc for the host formatter: the read group's ID (the run's; null: none) and whether the pairs' lines get MC and MQ
+    const std::string *rg = nullptr;
+    bool mate_tags = false;
     std::deque<bool> parts_out; // the parts on their way out, oldest first (true: the single-read part)
     // device_sam: the names and NUL-padded qualities of the batch's two parts on their way to the device (page-locked; a part's names back to back with
     // offsets that start at 0: the pairs' are sam_name_off[0 .. n_pair_reads], the single reads' sam_name_off[n_pair_reads + 1 .. n + 1]), and the text that came back
@@ -123,9 +127,9 @@ inline size_t sam_bound(const HostIndex &ix, size_t name_len, size_t rlen, int c
 }
 
 // one SAM line of read r: `rec` with its operations at `cigar`
-inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx_aln &rec, const uint32_t *cigar, Text &o, const uint8_t *md = nullptr, uint32_t md_len = 0)
+// (tail: what the line carries behind XS — MD, MC and MQ, RG — written by mcx_sam.h's sam_tail_put: the bytes of the device formatter)
+inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx_aln &rec, const uint32_t *cigar, Text &o, const SamTail &tail)
 {
-    static const char opc[8] = {'M', 'I', 'D', 'N', 'S', 'H', 'P', '='};
     const char *base;
     const Rec &e = bt.rec(r, base);
     const char *seq = base + e.seq;
@@ -142,10 +146,7 @@ inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx
     else {
         const std::string &cn = ix.chr_name[rec.chr];
         o.put(cn.data(), cn.size()); o.put('\t'); o.num(rec.pos); o.put('\t'); o.num(rec.mapq); o.put('\t');
-        for (int k = 0; k < rec.n_cigar; k++) {
-            const uint32_t w = cigar[k];
-            o.num(w >> 4); o.put(opc[w & 7]);
-        }
+        o.w = (char *)sam_cigar_put((uint8_t *)o.w, cigar, rec.n_cigar); // (column 6 and the mate's MC:Z through one code)
         if (rec.has_mate) { o.lit("\t=\t"); o.num(rec.mate_pos); o.put('\t'); o.num(rec.tlen); o.put('\t'); }
         else o.lit("\t*\t0\t0\t");
     }
@@ -162,7 +163,26 @@ inline void sam_line(const HostIndex &ix, const Batch &bt, uint32_t r, const mcx
         else if (e.q_take == e.rlen) { char *w = o.w; for (int k = rlen - 1; k >= 0 && qual[k] != '\0'; k--) *w++ = qual[k]; o.w = w; }
     }
     if (!mapped) o.lit("\tAS:i:0\tXS:i:0\n");
-    else { o.lit("\tNM:i:"); o.num(rec.nm); o.lit("\tAS:i:"); o.num(rec.as); o.lit("\tXS:i:"); o.num(rec.xs); if (md_len) { o.lit("\tMD:Z:"); o.put((const char *)md, md_len); } o.put('\n'); }
+    else { o.lit("\tNM:i:"); o.num(rec.nm); o.lit("\tAS:i:"); o.num(rec.as); o.lit("\tXS:i:"); o.num(rec.xs); o.put('\n'); }
+    o.w = (char *)sam_tail_put((uint8_t *)o.w, tail);
+}
+
+// what line `rec` of read r carries behind XS: its MD string (none without -md), the read group, and — for read r's own record in the pairs' part — its mate's
+// CIGAR and MAPQ by the rule at mcx_sam_tags.  The mate is read r ^ 1: a pair's mates are always in the same part of a batch (the pairs' part is reads
+// [0, n_pair_reads), an even number, with its own CIGAR pool), so r ^ 1 < n_pair_reads whenever r is.
+inline SamTail host_tail(const Batch &bt, uint32_t r, const mcx_aln &rec, bool extra, const uint8_t *md, uint32_t md_len)
+{
+    SamTail t;
+    t.md = md; t.md_len = md_len;
+    t.mc = nullptr; t.mc_n = 0; t.mq = 0;
+    if (bt.mate_tags && !extra && r < bt.n_pair_reads && (r ^ 1u) < bt.n_pair_reads && !(rec.flag & 8)) {
+        mcx_aln m;
+        mcx_aln_unpack(&bt.recs[r ^ 1u], &m);
+        if (m.chr >= 0 && m.n_cigar > 0) { t.mc = bt.cig + (size_t)(uint32_t)m.cigar_off; t.mc_n = m.n_cigar; t.mq = m.mapq; }
+    }
+    t.rg = bt.rg && !bt.rg->empty() ? (const uint8_t *)bt.rg->data() : nullptr;
+    t.rg_len = t.rg ? (uint32_t)bt.rg->size() : 0;
+    return t;
 }
 
 // -md: the string of entry k of a part's pool (none without -md, or for a line without a tag)
@@ -196,10 +216,10 @@ inline void sam_record(const HostIndex &ix, const Batch &bt, uint32_t r, Text &o
     const uint32_t part_reads = part ? bt.n - bt.n_pair_reads : bt.n_pair_reads;
     const uint8_t *md;
     uint32_t ml = md_entry(bt, part, part ? r - bt.n_pair_reads : r, md);
-    sam_line(ix, bt, r, rec, cigar, o, md, ml);
+    sam_line(ix, bt, r, rec, cigar, o, host_tail(bt, r, rec, false, md, ml));
     const Batch::Extras *x; uint32_t lo, hi;
     extra_range(bt, r, x, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { ml = md_entry(bt, part, (size_t)part_reads + i, md); sam_line(ix, bt, r, x->recs[i], x->cig.data() + (uint32_t)x->recs[i].cigar_off, o, md, ml); }
+    for (uint32_t i = lo; i < hi; i++) { ml = md_entry(bt, part, (size_t)part_reads + i, md); sam_line(ix, bt, r, x->recs[i], x->cig.data() + (uint32_t)x->recs[i].cigar_off, o, host_tail(bt, r, x->recs[i], true, md, ml)); }
 }
 
 // bytes read r's line(s) can take at most
@@ -216,6 +236,9 @@ inline size_t sam_bound_read(const HostIndex &ix, const Batch &bt, uint32_t r, s
         b += 6 + md_entry(bt, part, part ? r - bt.n_pair_reads : r, md);
         for (uint32_t i = lo; i < hi; i++) b += 6 + md_entry(bt, part, (size_t)part_reads + i, md);
     }
+    const size_t lines = 1 + (hi - lo);
+    if (bt.rg) b += lines * (6 + bt.rg->size()); // the lines' RG tags
+    if (bt.mate_tags && r < bt.n_pair_reads && (r ^ 1u) < bt.n_pair_reads) b += 6 + 11 * (size_t)bt.recs[r ^ 1u].n_cigar + 6 + 11; // MC: the mate's operations; MQ
     return b;
 }
 

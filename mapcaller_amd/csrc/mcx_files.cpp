@@ -32,6 +32,7 @@
 // write_loop) work beside the calling thread's map_loop(), batch objects going round between them through four queues.
 #include <sys/file.h>
 
+#include "mcx_tags.h"
 #include "mcx_batch.h"
 #include "mcx_shards.h"
 #include "mcx_sort_plan.h"
@@ -280,6 +281,10 @@ struct Run {
     const uint8_t *d_bases = nullptr; const uint32_t *d_off = nullptr; mcx_aln *d_aln = nullptr; uint32_t *d_cig = nullptr; uint32_t n_dev = 0;
     int parts_out = 0;
     bool host_md = false; // -md without device_sam: every mapped part's MD strings come to the host for the formatter's threads (part_md)
+    // -rg / -mc: the validated @RG line (real TABs, no newline; empty: none) for the header of every route, its ID, and — for the host formatter — the mate-tag switch
+    std::string rg_line, rg_id;
+    bool host_mate_tags = false;
+    const char *rg_or_null() const { return rg_line.empty() ? nullptr : rg_line.c_str(); }
 
     Run(mcx_ctx *ctx, const char *f1, const char *f2, const mcx_file_opts &o, const char *sam, mcx_stats *st)
         : c(ctx), fq1(f1), fq2(f2), sam_path(sam), opt(o), stats(st), idx(mcx_ctx_index(ctx)), hix(idx->host), max_len(mcx_ctx_max_read_len(ctx)), kept(kept_of(ctx)),
@@ -433,10 +438,13 @@ struct Run {
             std::string hdr;
             if (bam) { // -bam: the binary header, text and contigs
                 uint64_t n = 0;
-                (void)mcx_bam_header(idx, nullptr, 0, &n);
+                (void)mcx_bam_header_rg(idx, rg_or_null(), 0, nullptr, 0, &n);
                 hdr.resize((size_t)n);
-                if (n == 0 || mcx_bam_header(idx, (uint8_t *)&hdr[0], n, &n) != 0) e = mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
-            } else sam_header(hix, hdr);
+                if (n == 0 || mcx_bam_header_rg(idx, rg_or_null(), 0, (uint8_t *)&hdr[0], n, &n) != 0) e = mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
+            } else {
+                sam_header(hix, hdr);
+                if (!rg_line.empty()) hdr += rg_line + "\n"; // (-rg: the last line of the header text)
+            }
             if (bgzf && e == 0) { // the header as BGZF blocks of its own
                 std::string blocks((size_t)mcx_bgzf_bound(hdr.size(), zs.block), '\0');
                 uint64_t made = 0;
@@ -1148,6 +1156,7 @@ struct Run {
             d_bases = nullptr; d_off = nullptr; d_aln = nullptr; d_cig = nullptr; n_dev = 0;
             p->has_mx = multi;
             p->has_md = host_md;
+            p->rg = rg_id.empty() ? nullptr : &rg_id; p->mate_tags = host_mate_tags;
             for (Batch::Md &m : p->md) { m.bytes.clear(); m.off.clear(); }
             for (Batch::Extras &x : p->mx) { x.index.clear(); x.recs.clear(); x.cig.clear(); }
             p->parts_out.clear();
@@ -1237,9 +1246,9 @@ struct Run {
         // the header, blocks of its own
         {
             uint64_t n = 0;
-            (void)mcx_bam_header_sorted(idx, nullptr, 0, &n);
+            (void)mcx_bam_header_rg(idx, rg_or_null(), 1, nullptr, 0, &n);
             std::string hdr((size_t)n, '\0');
-            if (n == 0 || mcx_bam_header_sorted(idx, (uint8_t *)&hdr[0], n, &n) != 0) return mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
+            if (n == 0 || mcx_bam_header_rg(idx, rg_or_null(), 1, (uint8_t *)&hdr[0], n, &n) != 0) return mcx_set_error(MCX_ERR_UNSUPPORTED, std::string("-bam: ") + mcx_last_error());
             std::string blocks((size_t)mcx_bgzf_bound(hdr.size(), zs.block), '\0');
             uint64_t made = 0;
             if ((e = mcx_bgzf_deflate(zs.deflater, (const uint8_t *)hdr.data(), hdr.size(), (uint8_t *)&blocks[0], blocks.size(), &made))) return e;
@@ -1406,6 +1415,11 @@ struct Run {
 
 extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, const mcx_file_opts *fo, const char *sam_path, mcx_stats *stats)
 {
+    return mcx_map_files_rg(c, fq1, fq2, fo, nullptr, sam_path, stats);
+}
+
+extern "C" int mcx_map_files_rg(mcx_ctx *c, const char *fq1, const char *fq2, const mcx_file_opts *fo, const char *read_group, const char *sam_path, mcx_stats *stats)
+{
     if (!c || !fq1) return mcx_set_error(MCX_ERR_ARG, "mcx_map_files: null argument");
     mcx_file_opts opt;
     mcx_file_opts_default(&opt);
@@ -1435,12 +1449,36 @@ extern "C" int mcx_map_files_ex(mcx_ctx *c, const char *fq1, const char *fq2, co
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run cannot write its SAM file as BGZF or as BAM (-bgzf / -bam with -gpus N / -devices): map on one GPU, or without them");
     if (opt.shard_count > 1 && (opt.device_sam & MCX_SAM_MD))
         return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run does not make MD tags (-md with -gpus N / -devices): map on one GPU, or without -md");
+    // -rg / -mc: refused where they cannot be made, before anything is opened
+    std::string rg_line, rg_id;
+    if (read_group) {
+        std::string why;
+        if (!mcx::rg_parse(read_group, rg_line, rg_id, why)) return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_rg: " + why);
+        if (rg_line != read_group) return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_rg: the read-group line must hold real TABs (mcx_rg_parse's line)");
+    }
+    if (opt.shard_count > 1 && (read_group || (opt.device_sam & MCX_SAM_MC)))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run does not make read-group or mate tags (-rg / -mc with -gpus N / -devices): map on one GPU, or without them");
+    if ((opt.device_sam & MCX_SAM_MC) && mcx_ctx_multi(c))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: -mc cannot be combined with -m: an extra line is paired with another candidate of the mate than the one whose CIGAR is held");
+    // ... and, like -md, no output routes of their own: the bit comes off, and the context's device formatter calls are told (until the run is over)
+    const bool with_out = sam_path && sam_path[0];
+    const bool with_mc = (opt.device_sam & MCX_SAM_MC) != 0 && with_out;
+    opt.device_sam &= ~(int32_t)MCX_SAM_MC;
+    if (!with_out) { rg_line.clear(); rg_id.clear(); }
     // -md is no output route of its own: the bit comes off, and where the text is made on the device the context's formatter calls are told (until the run is over)
     const bool with_md = (opt.device_sam & MCX_SAM_MD) != 0 && sam_path && sam_path[0];
     opt.device_sam &= ~(int32_t)MCX_SAM_MD;
     struct MdSwitch { mcx_ctx *c; bool on; MdSwitch(mcx_ctx *ctx, bool o) : c(ctx), on(o) { if (on) mcx_md_set(c, 1); } ~MdSwitch() { if (on) mcx_md_set(c, 0); } } md_switch(c, with_md && opt.device_sam != 0);
+    struct TagSwitch {
+        mcx_ctx *c; bool on; int rc = 0;
+        TagSwitch(mcx_ctx *ctx, bool o, const std::string &id, bool mc) : c(ctx), on(o) { if (on) rc = mcx_tags_set(c, id.data(), (uint32_t)id.size(), mc); }
+        ~TagSwitch() { if (on) (void)mcx_tags_set(c, nullptr, 0, 0); }
+    } tag_switch(c, (with_mc || !rg_id.empty()) && opt.device_sam != 0, rg_id, with_mc);
+    if (tag_switch.rc) return tag_switch.rc;
     Run run(c, fq1, fq2, opt, sam_path, stats);
     run.host_md = with_md && opt.device_sam == 0;
+    run.rg_line = rg_line;
+    if (opt.device_sam == 0) { run.rg_id = rg_id; run.host_mate_tags = with_mc; }
     if (int e = run.open_input()) return e;
     if (int e = run.open_output()) return e;
     run.begin();

@@ -61,7 +61,10 @@ int mcx_sam_part(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, uint3
                  const uint8_t *qual, uint64_t qual_bytes, const mcx_aln *d_aln, const uint32_t *d_cigar, uint8_t **text, uint64_t *text_cap, uint64_t at, uint64_t *n_bytes, mcx_sam_bgzf *bgzf);
 // -bam (mcx_bam.hip): mcx_bam_format_dev for sam_part's input — the records of a part into d_out[0 .. cap), *n_bytes their exact size (MCX_ERR_CAPACITY, nothing
 // written, when cap is smaller), *n_dropped the lines that made none; the context's device is current
-int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, uint8_t *d_out, uint64_t cap, uint64_t *n_bytes, uint64_t *n_dropped);
+int mcx_bam_part_dev(mcx_ctx *, const mcx_sam_in *d_in, const mcx_sam_tags *tags, uint8_t *d_out, uint64_t cap, uint64_t *n_bytes, uint64_t *n_dropped);
+// -rg / -mc (mcx_sam.hip): the read group's ID goes to HBM once per run; the context's following mcx_sam_part[_dev] calls hand it, and the mate-tag switch, to their
+// formatter.  (nullptr, 0, 0) at the end of the run: both off, the ID's bytes freed.
+int mcx_tags_set(mcx_ctx *, const char *id, uint32_t id_len, int mate_tags);
 // -md (mcx_md.hip).  set: the context's following mcx_sam_part[_dev] calls make their part's MD strings first and hand them to the formatter.  part_dev: the
 // strings of `in`'s lines (n_extras: the context's extras of the part) into the formatter state's own pool, which in->md / in->md_off then point at.  part_host:
 // the same for a part still in its slot whose text the host makes: the strings and their offsets (n_reads + extras + 1 entries) come back with the part.

@@ -66,6 +66,10 @@ static void usage(const char *prog)
             "                       memory a record and 24 a pair until the merge; no optical distance, one library; not with -m\n"
             "         -md           an MD:Z tag behind XS on every mapped line (what samtools calmd adds), its strings made on the GPU behind each batch's mapping; with -sam,\n"
             "                       -gpu_sam, -bgzf, -bam and its -sort / -markdup / -index, and -m; not with -gpus N / -devices\n"
+            "         -rg STR       read group, bwa mem -R's form ('@RG\\tID:lane1\\tSM:na12878': \\t or a real TAB between the fields, exactly one ID): the line ends the header,\n"
+            "                       RG:Z:<ID> goes on every line (what samtools addreplacerg adds); with every output and -m; not with -gpus N / -devices\n"
+            "         -mc           MC:Z (the mate's CIGAR) and MQ:i (its MAPQ) on the lines of pairs whose mate is mapped and whose FLAG has 0x8 clear (what samtools\n"
+            "                       fixmate -m adds), made on the GPU with the line; with every output; not with -m, not with -gpus N / -devices\n"
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
@@ -119,6 +123,8 @@ int main(int argc, char **argv)
     bool want_sort = false; // -sort: ... in coordinate order
     bool want_index = false; // -index: ... with its .bai beside it
     bool want_markdup = false; // -markdup: ... and flag bit 0x400 on its duplicates
+    bool want_rg = false;      // -rg: an @RG header line and RG:Z on every line
+    std::string rg_arg, rg_line;
     std::string vcf = "output.vcf", cmdline = argv[0];
     mcx_vcf_opts vo;
     mcx_vcf_defaults(&vo);
@@ -179,6 +185,8 @@ int main(int argc, char **argv)
         else if (p == "-index") want_index = true;
         else if (p == "-markdup") want_markdup = true;
         else if (p == "-md") fo.device_sam |= MCX_SAM_MD;
+        else if (p == "-rg" && i + 1 < argc) { rg_arg = argv[++i]; want_rg = true; }
+        else if (p == "-mc") fo.device_sam |= MCX_SAM_MC;
         else if (p == "-gpu_inflate") fo.device_inflate = 1;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
@@ -200,6 +208,14 @@ int main(int argc, char **argv)
     if (want_markdup) fo.device_sam |= MCX_SAM_MARKDUP;
     if (n_gpus > 1 && bam) { fprintf(stderr, "Error! -bam writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BAM writer does not exist yet)\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_MD)) { fprintf(stderr, "Error! -md makes its MD tags on one GPU: it cannot be combined with -gpus N / -devices\n"); return 1; }
+    if (want_rg) { // checked before anything is opened
+        char line[4096];
+        uint64_t n = 0;
+        if (mcx_rg_parse(rg_arg.c_str(), line, sizeof line, &n, nullptr, nullptr)) { fprintf(stderr, "Error! %s\n", mcx_last_error()); return 1; }
+        rg_line.assign(line, (size_t)n);
+    }
+    if ((fo.device_sam & MCX_SAM_MC) && multi) { fprintf(stderr, "Error! -mc cannot be combined with -m: an extra line is paired with another candidate of the mate than the one whose CIGAR is held\n"); return 1; }
+    if (n_gpus > 1 && (want_rg || (fo.device_sam & MCX_SAM_MC))) { fprintf(stderr, "Error! -rg and -mc make their tags on one GPU: they cannot be combined with -gpus N / -devices\n"); return 1; }
     if (n_gpus > 1 && (fo.device_sam & MCX_SAM_BGZF)) { fprintf(stderr, "Error! -bgzf writes one BGZF stream from one GPU: it cannot be combined with -gpus N / -devices (a sharded BGZF writer does not exist yet)\n"); return 1; }
     // -r ref.fa: the index is built for this run and removed again (main.cpp:344-349, :385-391) — on every way out, also the
     // early ones (a failed build leaves partial files behind it)
@@ -286,7 +302,7 @@ int main(int argc, char **argv)
                 for (int32_t v : all) if (v) stop = true;
                 if (stop) { if (!sh.rc) { sh.rc = MCX_ERR_DEVICE; sh.err = "another shard failed"; } break; }
             } else if (sh.rc) break;
-            rc = mcx_map_files_ex(sh.cx, f1[k].c_str(), f2.empty() ? nullptr : f2[k].c_str(), &my, out.empty() ? nullptr : out.c_str(), &sh.st);
+            rc = mcx_map_files_rg(sh.cx, f1[k].c_str(), f2.empty() ? nullptr : f2[k].c_str(), &my, want_rg ? rg_line.c_str() : nullptr, out.empty() ? nullptr : out.c_str(), &sh.st);
             if (rc) bad(rc);
             if (n_gpus > 1) { // every part of this library is complete before shard 0 merges them
                 int32_t mine = sh.rc;

@@ -65,13 +65,29 @@ static inline MCX_HD uint8_t *sam_num(uint8_t *o, int64_t v)
 }
 static inline MCX_HD uint8_t *sam_lit(uint8_t *o, const char *s) { while (*s) *o++ = (uint8_t)*s++; return o; }
 
+// a CIGAR as column 6 prints it (and MC:Z: the mate's, through the same code)
+static inline MCX_HD uint32_t sam_cigar_len(const uint32_t *cigar, int n)
+{
+    uint32_t len = 0;
+    for (int k = 0; k < n; k++) len += sam_num_len((int64_t)(cigar[k] >> 4)) + 1;
+    return len;
+}
+static inline MCX_HD uint8_t *sam_cigar_put(uint8_t *o, const uint32_t *cigar, int n)
+{
+    for (int k = 0; k < n; k++) {
+        const uint32_t w = cigar[k];
+        o = sam_num(o, (int64_t)(w >> 4)); *o++ = (uint8_t)"MIDNSHP="[w & 7];
+    }
+    return o;
+}
+
 // the fields between QNAME and SEQ, with the tabs around them
 static inline MCX_HD uint32_t sam_head_len(const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn)
 {
     uint32_t n = 1 + sam_num_len(rec.flag) + 1;
     if (rec.chr < 0) return n + 14;
     n += cn.off[rec.chr + 1] - cn.off[rec.chr] + 1 + sam_num_len(rec.pos) + 1 + sam_num_len(rec.mapq) + 1;
-    for (int k = 0; k < rec.n_cigar; k++) n += sam_num_len((int64_t)(cigar[k] >> 4)) + 1;
+    n += sam_cigar_len(cigar, rec.n_cigar);
     return n + (rec.has_mate ? 3 + sam_num_len(rec.mate_pos) + 1 + sam_num_len(rec.tlen) + 1 : 7);
 }
 static inline MCX_HD uint8_t *sam_head_put(const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o)
@@ -80,10 +96,7 @@ static inline MCX_HD uint8_t *sam_head_put(const mcx_aln &rec, const uint32_t *c
     if (rec.chr < 0) return sam_lit(o, "*\t0\t0\t*\t*\t0\t0\t");
     for (uint32_t k = cn.off[rec.chr]; k < cn.off[rec.chr + 1]; k++) *o++ = (uint8_t)cn.text[k];
     *o++ = '\t'; o = sam_num(o, rec.pos); *o++ = '\t'; o = sam_num(o, rec.mapq); *o++ = '\t';
-    for (int k = 0; k < rec.n_cigar; k++) {
-        const uint32_t w = cigar[k];
-        o = sam_num(o, (int64_t)(w >> 4)); *o++ = (uint8_t)"MIDNSHP="[w & 7];
-    }
+    o = sam_cigar_put(o, cigar, rec.n_cigar);
     if (!rec.has_mate) return sam_lit(o, "\t*\t0\t0\t");
     o = sam_lit(o, "\t=\t"); o = sam_num(o, rec.mate_pos); *o++ = '\t'; o = sam_num(o, rec.tlen); *o++ = '\t';
     return o;
@@ -129,7 +142,7 @@ static inline MCX_HD uint8_t sam_qual_byte(const SamRead &d, const SamTurn &t, u
 }
 
 // A line's MD string in the batch's pool (mcx_md.h makes it; include/mcx.h: entry r is read r's own record, n_reads + i the -m extra i): its bytes, 0 without
-// a pool or a tag.  The tag goes behind XS — "\tMD:Z:" and the string, copied — ahead of the newline.
+// a pool or a tag.
 static inline MCX_HD uint32_t sam_md_of(const mcx_sam_in &in, uint32_t entry, const uint8_t *&md)
 {
     md = nullptr;
@@ -137,23 +150,56 @@ static inline MCX_HD uint32_t sam_md_of(const mcx_sam_in &in, uint32_t entry, co
     md = in.md + in.md_off[entry];
     return in.md_off[entry + 1] - in.md_off[entry];
 }
-static inline MCX_HD uint32_t sam_md_len(uint32_t md_len) { return md_len ? 6 + md_len : 0; }
-static inline MCX_HD uint8_t *sam_md_lit(uint8_t *o) { return sam_lit(o, "\tMD:Z:"); } // (over the newline sam_tags_put ended the line with)
 
-// one line: its bytes; the same written at o (returns the end)
-static inline MCX_HD uint64_t sam_one_len(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint32_t md_len = 0)
+// What a line carries behind XS, in this order (include/mcx.h at mcx_sam_tags): "\tMD:Z:" and the pool's string, copied; "\tMC:Z:" the mate's CIGAR and "\tMQ:i:" its
+// MAPQ; "\tRG:Z:" the read group's ID.  The first of them goes over the newline sam_tags_put ended the line with, a newline ends the last.
+struct SamTail {
+    const uint8_t *md; uint32_t md_len;   // 0: no MD
+    const uint32_t *mc; int32_t mc_n, mq; // the mate's CIGAR words and MAPQ; mc_n 0: neither MC nor MQ
+    const uint8_t *rg; uint32_t rg_len;   // 0: no RG
+};
+// read r's own line (extra = false; entry = r) or its -m extra (entry = n_reads + i).  The mate of read r of a batch mapped as pairs is r ^ 1: its record is
+// fetched once, here, and only with mate_tags on.  Both tags iff the mate's record is mapped and the line's own FLAG has 0x8 clear; never on an extra.
+static inline MCX_HD SamTail sam_tail_of(const mcx_sam_in &in, const mcx_sam_tags &tg, uint32_t entry, uint32_t r, const mcx_aln &own, bool extra)
 {
-    return (uint64_t)d.name_len + sam_head_len(rec, cigar, cn) + d.rlen + 1 + sam_qual_len(d, sam_turn(d, rec)) + sam_tags_len(rec) + sam_md_len(md_len);
+    SamTail t;
+    t.md_len = sam_md_of(in, entry, t.md);
+    t.mc = nullptr; t.mc_n = 0; t.mq = 0;
+    if (tg.mate_tags && in.paired && !extra && (r ^ 1u) < in.n_reads && !(own.flag & 8)) {
+        const mcx_aln m = in.aln[r ^ 1u];
+        if (m.chr >= 0 && m.n_cigar > 0) { t.mc = in.cigar + (uint32_t)m.cigar_off; t.mc_n = m.n_cigar; t.mq = m.mapq; }
+    }
+    t.rg = tg.rg_len ? tg.rg : nullptr; t.rg_len = t.rg ? tg.rg_len : 0;
+    return t;
 }
-static inline MCX_HD uint8_t *sam_md_put(uint8_t *o, const uint8_t *md, uint32_t md_len) // o: behind the line's newline
+static inline MCX_HD uint32_t sam_md_len(uint32_t md_len) { return md_len ? 6 + md_len : 0; }
+static inline MCX_HD uint32_t sam_mc_len(const SamTail &t) { return t.mc_n ? 6 + sam_cigar_len(t.mc, t.mc_n) + 6 + sam_num_len(t.mq) : 0; }
+static inline MCX_HD uint32_t sam_rg_len(uint32_t rg_len) { return rg_len ? 6 + rg_len : 0; }
+static inline MCX_HD uint32_t sam_tail_len(const SamTail &t) { return sam_md_len(t.md_len) + sam_mc_len(t) + sam_rg_len(t.rg_len); }
+static inline MCX_HD uint8_t *sam_md_lit(uint8_t *o) { return sam_lit(o, "\tMD:Z:"); }
+static inline MCX_HD uint8_t *sam_rg_lit(uint8_t *o) { return sam_lit(o, "\tRG:Z:"); }
+static inline MCX_HD uint8_t *sam_mc_put(uint8_t *o, const SamTail &t) // "\tMC:Z:" CIGAR "\tMQ:i:" MAPQ (mc_n > 0)
 {
-    if (!md_len) return o;
-    o = sam_md_lit(o - 1);
-    for (uint32_t k = 0; k < md_len; k++) *o++ = md[k];
+    o = sam_cigar_put(sam_lit(o, "\tMC:Z:"), t.mc, t.mc_n);
+    return sam_num(sam_lit(o, "\tMQ:i:"), t.mq);
+}
+static inline MCX_HD uint8_t *sam_tail_put(uint8_t *o, const SamTail &t) // o: behind the line's newline
+{
+    if (!sam_tail_len(t)) return o;
+    o--;
+    if (t.md_len) { o = sam_md_lit(o); for (uint32_t k = 0; k < t.md_len; k++) *o++ = t.md[k]; }
+    if (t.mc_n) o = sam_mc_put(o, t);
+    if (t.rg_len) { o = sam_rg_lit(o); for (uint32_t k = 0; k < t.rg_len; k++) *o++ = t.rg[k]; }
     *o++ = '\n';
     return o;
 }
-static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o, const uint8_t *md = nullptr, uint32_t md_len = 0)
+
+// one line: its bytes; the same written at o (returns the end)
+static inline MCX_HD uint64_t sam_one_len(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, const SamTail &tail)
+{
+    return (uint64_t)d.name_len + sam_head_len(rec, cigar, cn) + d.rlen + 1 + sam_qual_len(d, sam_turn(d, rec)) + sam_tags_len(rec) + sam_tail_len(tail);
+}
+static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, const uint32_t *cigar, const SamContigs &cn, uint8_t *o, const SamTail &tail)
 {
     for (uint32_t k = 0; k < d.name_len; k++) *o++ = d.name[k];
     o = sam_head_put(rec, cigar, cn, o);
@@ -162,7 +208,7 @@ static inline MCX_HD uint8_t *sam_one_put(const SamRead &d, const mcx_aln &rec, 
     *o++ = '\t';
     const uint32_t ql = sam_qual_len(d, t);
     for (uint32_t k = 0; k < ql; k++) *o++ = sam_qual_byte(d, t, k);
-    return sam_md_put(sam_tags_put(rec, o), md, md_len);
+    return sam_tail_put(sam_tags_put(rec, o), tail);
 }
 
 // -m: read r's extra lines (SamReport.cpp:364-488: every further candidate with the best score), none without x_index
@@ -173,27 +219,24 @@ static inline MCX_HD void sam_extras_of(const mcx_sam_in &in, uint32_t r, uint32
 }
 
 // read r's line(s): the record of unique mode, then its extras with the same name, bases and quality
-static inline MCX_HD uint64_t sam_line_len(const mcx_sam_in &in, const SamContigs &cn, uint32_t r)
+static inline MCX_HD uint64_t sam_line_len(const mcx_sam_in &in, const SamContigs &cn, uint32_t r, const mcx_sam_tags &tg = mcx_sam_tags())
 {
     const SamRead d = sam_read_of(in, r);
     const mcx_aln rec = in.aln[r];
-    const uint8_t *md;
-    uint64_t n = sam_one_len(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, sam_md_of(in, r, md));
+    uint64_t n = sam_one_len(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, sam_tail_of(in, tg, r, r, rec, false));
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; n += sam_one_len(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, sam_md_of(in, in.n_reads + i, md)); }
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; n += sam_one_len(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, sam_tail_of(in, tg, in.n_reads + i, r, x, true)); }
     return n;
 }
-static inline MCX_HD uint64_t sam_line_put(const mcx_sam_in &in, const SamContigs &cn, uint32_t r, uint8_t *out)
+static inline MCX_HD uint64_t sam_line_put(const mcx_sam_in &in, const SamContigs &cn, uint32_t r, uint8_t *out, const mcx_sam_tags &tg = mcx_sam_tags())
 {
     const SamRead d = sam_read_of(in, r);
     const mcx_aln rec = in.aln[r];
-    const uint8_t *md;
-    uint32_t ml = sam_md_of(in, r, md);
-    uint8_t *o = sam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, out, md, ml);
+    uint8_t *o = sam_one_put(d, rec, in.cigar + (uint32_t)rec.cigar_off, cn, out, sam_tail_of(in, tg, r, r, rec, false));
     uint32_t lo, hi;
     sam_extras_of(in, r, lo, hi);
-    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; ml = sam_md_of(in, in.n_reads + i, md); o = sam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, o, md, ml); }
+    for (uint32_t i = lo; i < hi; i++) { const mcx_aln x = in.x_recs[i]; o = sam_one_put(d, x, in.x_cigar + (uint32_t)x.cigar_off, cn, o, sam_tail_of(in, tg, in.n_reads + i, r, x, true)); }
     return (uint64_t)(o - out);
 }
 

@@ -91,12 +91,13 @@ struct SamState {
     uint8_t *d_md = nullptr; uint32_t *d_md_off = nullptr; uint64_t cap_md = 0, cap_md_off = 0; // -md (mcx_md.hip): a batch part's MD strings and their offsets
     bool want_md = false;                                                                        // the file front end's -md is on (mcx_md_set)
     float md_ms[3] = {0, 0, 0};                                                                 // the last mcx_md[_dev]'s length kernel, scan, write kernel
+    uint8_t *d_rg = nullptr; mcx_sam_tags tags = mcx_sam_tags();                                // -rg / -mc (mcx_tags_set): the read group's ID in HBM and what the front end's formatter calls get
     SortBufs sort;
     BaiBufs bai;
     DupBufs dup;
     ~SamState()
     {
-        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf, d_md, d_md_off};
+        void *p[] = {d_cn_text, d_cn_off, d_len, d_off, d_tmp, d_dropped, d_names, d_qual, d_text, d_name_off, d_bgzf, d_md, d_md_off, d_rg};
         for (void *q : p) if (q) (void)hipFree(q);
         if (h_total) (void)hipHostFree(h_total);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -133,6 +134,10 @@ static inline int sam_state_of(mcx_ctx *c, SamState **out)
     *out = st;
     return 0;
 }
+
+// mate_tags with -m extras: an extra is paired with another candidate of the mate than the one whose CIGAR the batch holds
+static inline bool tags_ok(const mcx_sam_in *in, const mcx_sam_tags *tags) { return !(tags && tags->mate_tags && in->x_index); }
+static constexpr const char *kTagsWithExtras = ": MC and MQ cannot be made for -m lines (mate_tags with x_index): an extra line is paired with another candidate of the mate";
 
 template <class T> int sam_grow(T **p, uint64_t *cap, uint64_t need, const char *what)
 {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MapCaller's command line on one or several MI355X of a node.
 
-    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort [-markdup] [-index]]] [-md] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
+    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort [-markdup] [-index]]] [-md] [-rg LINE] [-mc] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 -m mapcaller_amd.run -i idx -f r1.fq -f2 r2.fq -sam out.sam -vcf out.vcf
 
 One process per GPU.  The input stream is cut into batches that are dealt to the ranks in turn
@@ -45,6 +45,8 @@ def parse(argv):
     ap.set_defaults(bam=False)
     ap.add_argument("-sort", dest="sort", action="store_true", help="with -bam: a coordinate-sorted BAM file, sorted and merged on the GPU (temporary disk of the file's size beside it, 12 bytes of host memory a record; one library, one process; -index writes its .bai)")
     ap.add_argument("-md", dest="md", action="store_true", help="an MD:Z tag behind XS on every mapped line (what samtools calmd adds), made on the GPU behind each batch's mapping; with every SAM / BAM output; not on several GPUs")
+    ap.add_argument("-rg", dest="rg", default=None, metavar="LINE", help="read group, bwa mem -R's form ('@RG\\tID:lane1\\tSM:x'): the line ends the header, RG:Z:<ID> goes on every line; with every SAM / BAM output; not on several GPUs")
+    ap.add_argument("-mc", dest="mc", action="store_true", help="MC:Z and MQ:i (the mate's CIGAR and MAPQ) on the lines of pairs whose mate is mapped and whose FLAG has 0x8 clear (what samtools fixmate -m adds); not with -m, not on several GPUs")
     ap.add_argument("-markdup", dest="markdup", action="store_true", help="with -bam -sort: set flag bit 0x400 on duplicate records (pairs by both unclipped 5' ends, single reads by one; the best by base qualities stays), decided on the GPU; 4 more bytes of host memory a record and 24 a pair until the merge; not with -m")
     ap.add_argument("-index", dest="bai", action="store_true", help="with -bam -sort: write the file's index beside it (FILE.bai, what samtools index makes), built on the GPU while the merge writes the file")
     ap.add_argument("-vcf", default="output.vcf")
@@ -112,6 +114,10 @@ def main(argv=None):
         sys.exit("-index writes the .bai of a coordinate-sorted BAM file: it needs -bam -sort")
     if a.md and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         sys.exit("-md makes its MD tags on one GPU: it cannot be combined with a run on several")
+    if (a.rg is not None or a.mc) and world > 1:
+        sys.exit("-rg and -mc make their tags on one GPU: they cannot be combined with a run on several")
+    if a.mc and a.multi:
+        sys.exit("-mc cannot be combined with -m: an extra line is paired with another candidate of the mate than the one whose CIGAR is held")
     if a.markdup and not a.sort:
         sys.exit("-markdup flags the duplicates of a coordinate-sorted BAM file: it needs -bam -sort")
     if a.markdup and getattr(a, "multi", False):
@@ -149,7 +155,7 @@ def main(argv=None):
         f2 = a.f2[k] if a.f2 else None
         # (the ranks write into the one SAM file, every batch's lines at their final place: mcx_map_files_ex)
         st = mapper.map_files(f1, f2, a.sam or None, interleaved=a.interleaved, threads=a.threads,
-                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort, index=a.bai, markdup=a.markdup, md=a.md)
+                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort, index=a.bai, markdup=a.markdup, md=a.md, read_group=a.rg, mate_tags=a.mc)
         for key in totals:
             totals[key] += st[key]
         if td:
