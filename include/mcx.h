@@ -644,6 +644,50 @@ int  mcx_inflate(mcx_inflater *, const uint8_t *src, uint64_t src_bytes, const m
 /* the BGZF reader by itself, the twin of mcx_gz_inflate: whole length of the text, -1 unreadable / first bytes are no BGZF member, -2 a damaged member (*n_out: bytes delivered before it) */
 int64_t mcx_bgzf_inflate(const char *path, int device, uint8_t *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- ordinary gzip streams inflated on the device ---------------------------------------------------
+ * A gzip member that is not BGZF is ONE deflate stream: a block starts at any bit, and a match reaches 32 KB back into text that is not there yet.  A
+ * gunzipper does on the device what mcx_gz_inflate does with host threads (mcx_pgz.h's method; mcx_gz_dev.h, mcx_gz_dev.hip): the compressed bytes of a ROUND
+ * are cut into stretches of stretch_bytes; a wavefront per stretch looks for a block start in its own bytes (dynamic block, complete codes, first symbols
+ * decode to text); a wavefront per stretch with a start inflates from there into 16-bit symbols (below 256 a byte, 256 + p "byte p of the 32 KB before my
+ * start") until it ends on a later stretch's start (or has passed 4 later stretches in which no start was found); the host walks the chain stretch 0 -> whichever stretch begins where the last one stopped (a false start
+ * is never met and costs time only); one workgroup resolves the chain's 32 KB windows in sequence; all symbols become bytes in parallel, a CRC-32 per piece.
+ * The call is in two halves so that the caller knows text_bytes before it makes room: mcx_gunzip_round_dev runs search, inflate, chain and windows and says where
+ * the round ended; mcx_gunzip_text_dev writes the round's text to d_dst[0 .. text_bytes) and takes its CRC-32.  A round with text_bytes > 0 must be fetched before
+ * the next round is run (the symbols lie in the object's arena).  The next round starts at end_bit: pass src + (end_bit >> 3) and start_bit = end_bit & 7.
+ * The object keeps the last 32 KB of text as the next round's window; mcx_gunzipper_reset at the start of a member.  It knows nothing of gzip headers and
+ * trailers: final = 1 says the member's final block ended at end_bit, and the caller compares CRC-32 (zlib's crc32_combine over the rounds) and ISIZE.
+ * status: MCX_GZ_OK — text_bytes may still be 0: a stretch ran out of room in the arena (overflowed), the chain ends in front of it and the next round takes half
+ * as many stretches (down to one, which has the whole arena; back to the full number after a round whose chain no overflow ended); call again.  MCX_GZ_MORE: only
+ * with src_is_end = 0 — not even the first stretch reached a block end inside src_bytes: pass more bytes.  MCX_GZ_DAMAGED / MCX_GZ_INPUT / MCX_GZ_CAPACITY (one
+ * stretch with the whole arena is out of room: mcx_last_error says so in words): the stream ends here, the calls return 0 and the status says why.
+ * One host thread per object; a non-blocking stream of its own.  HBM: 2 bytes a symbol of the arena + 64 KB a stretch (the window prefixes) + 32 KB a stretch
+ * (the resolved windows). */
+enum mcx_gz_status { MCX_GZ_OK = 0, MCX_GZ_DAMAGED = 1, MCX_GZ_INPUT = 2 /* the stream ends inside a block */, MCX_GZ_CAPACITY = 3, MCX_GZ_MORE = 4 /* not the file's end: pass more bytes */ };
+typedef struct mcx_gz_round {
+    uint64_t end_bit;     /* where the next round starts, relative to src[0] */
+    uint64_t text_bytes;  /* what mcx_gunzip_text_dev will write */
+    uint32_t crc32;       /* of this round's text alone (valid after mcx_gunzip_text_dev) */
+    uint32_t final;       /* 1: the member's final block ended the round at end_bit */
+    uint32_t status;      /* mcx_gz_status */
+    uint32_t stretches, starts, chain, overflowed; /* cut, found by the search, in the chain (stretch 0 included), out of room */
+    float ms[4];          /* search, inflate, windows, text + CRC: events on the object's stream */
+} mcx_gz_round;
+typedef struct mcx_gunzipper mcx_gunzipper;
+int  mcx_gunzipper_create(int device, uint64_t stretch_bytes /* 0: 64 KB; at least 4096 */, uint32_t max_stretches /* 0: 2048 */, uint64_t arena_symbols /* 0: 8 per compressed byte of a full round */, mcx_gunzipper **out);
+void mcx_gunzipper_free(mcx_gunzipper *);
+void mcx_gunzipper_reset(mcx_gunzipper *);  /* a new member begins: no window */
+/* d_src[0 .. src_bytes) in HBM, readable 8 bytes further; start_bit 0..7; src_is_end: the bytes end with the file */
+int  mcx_gunzip_round_dev(mcx_gunzipper *, const uint8_t *d_src, uint64_t src_bytes, uint32_t start_bit, int src_is_end, mcx_gz_round *info);
+int  mcx_gunzip_text_dev(mcx_gunzipper *, uint8_t *d_dst, uint64_t dst_cap, mcx_gz_round *info);
+/* the reader by itself, the twin of mcx_gz_inflate and mcx_bgzf_inflate: same return values (-1 no gzip file, -2 damaged, *n_out bytes delivered before).
+ * Members are walked by their RFC 1952 headers, every trailer's CRC-32 and ISIZE are compared, concatenated members are followed and garbage behind a
+ * complete member ends the input quietly; a round's bytes go to HBM through page-locked memory, the next round's while this one is on the device.
+ * round_stretches 0: 2048. */
+int64_t mcx_gz_inflate_dev(const char *path, int device, uint64_t stretch_bytes, uint32_t round_stretches, uint8_t *out, uint64_t cap, uint64_t *n_out);
+/* of the calling thread's last mcx_gz_inflate_dev: rounds begun, and rounds whose compressed bytes were already in HBM when they began (staged while the round
+ * before ran: every round but a member's first, unless a block is longer than the slack of four stretches) */
+void mcx_gz_inflate_dev_last(uint64_t stats[2]);
+
 /* ---- text compressed to BGZF on the device --------------------------------------------------------------
  * The way back: text that lies in HBM — the SAM text of mcx_sam_format_dev — becomes a row of BGZF blocks, each an independent gzip member of at most
  * 65 280 bytes of text (bgzip's cut; mcx_deflater_set_block: fewer), which samtools, bgzip -d, zcat and Python's gzip read.  A wavefront per block: LZ77
@@ -763,7 +807,7 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * pool of formatter threads has nothing to do.  Same bytes in the file; buffers of about 0.6 KB per read of a batch are taken only then.
  * device_inflate (mapcaller-mi355x -gpu_inflate): a read file that is BGZF is inflated by an mcx_inflater of its own on the context's device, a stretch of
  * 8 MB of text per call, the next stretch's bytes staged meanwhile; the reader's pool of inflate threads is not created.  Same reads, same end of
- * the input at a damaged member.  Ordinary .gz and plain files are read as before.
+ * the input at a damaged member.  Ordinary .gz and plain files are read as before (ordinary .gz: see bit 2 below).
  * device_parse (mapcaller-mi355x -gpu_parse): where the input is plain FASTQ that the front end maps into memory, the byte range of each of this shard's batches goes
  * through page-locked staging to an mcx_fastq_parser of its own on the context's device — about 0.3 KB of HBM per read of a batch, taken after the context's —, and
  * records, 2-bit rows, lengths and odd bytes come back: the reader's threads only copy.  Same reads, same end of the input, same error texts.  Plain FASTA (a
@@ -780,6 +824,20 @@ int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_p
  * kernels from the same buffers.  Only the records, or the SAM text, come back.  Same reads, same end of the input (a damaged stretch, garbage behind a member,
  * a header that is none, an empty or too long read, file 2 shorter or longer), same error texts.  HBM, taken after the context's: see DESIGN §5b.  Any other
  * combination runs exactly as without the route; mcx_files_route says which stages ran on the device.
+ * device_inflate is a bit set: bit 1 (MCX_INFLATE_BGZF) is all of the above.  Bit 2 (MCX_INFLATE_GZ; mapcaller-mi355x -gpu_gz) opens the resident route to read files that are
+ * ORDINARY gzip streams (gzip, pigz, a sequencer's writer): with device_parse and the route's other conditions, a file named .gz that begins with a gzip header and is not
+ * BGZF is inflated by an mcx_gunzipper of its own — a round of MCX_GZ_ROUND_STRETCHES stretches at a time, its bytes staged through page-locked memory while the round
+ * before is on the device, the text left behind what the file's buffer in HBM holds — and parsed under the GZ rule like a BGZF file's.  The route applies per file: a BGZF
+ * file needs bit 1, an ordinary one bit 2, and a pair may mix the two kinds (route: MCX_ROUTE_GZ in place of MCX_ROUTE_INFLATE).  The first round of each ordinary file is
+ * run when the files are opened: where its chain holds fewer than half of its stretches, or it has fewer than two (not text, stored blocks only, blocks longer than a
+ * stretch, a small file), the route does not apply to the call, which runs as without the switch.  Bit 2 without device_parse, in a sharded run, with -p or with the host
+ * formatter runs exactly as without it: the host readers, no route bit.  A round whose stream is damaged, or whose trailer's CRC-32 or ISIZE does not match, hands on
+ * nothing and ends the file's input there; the rounds before it count, one line on stderr names the file and the bytes of text delivered, and the call returns what the
+ * host route returns (the end of a file's input is no error).  How many reads precede a damaged place depends on the round size, here as with the host reader's rounds:
+ * the two routes deliver whole rounds, and theirs differ.  HBM per ordinary file, taken after the context's: 2 bytes a symbol of a round (8 symbols a compressed byte),
+ * 96 KB a stretch, the staging twins of a round's compressed bytes, and the file's text (MCX_ALLOC_LOG=1 itemises it).
+ * Debug overrides (no result depends on them): MCX_GZ_STRETCH=bytes (default 65536, at least 4096), MCX_GZ_ROUND_STRETCHES=n (default 512) — the tests put many stretches
+ * and rounds into small files with them.
  * device_sam is a bit set: bit 1 (MCX_SAM_DEVICE) is the above, bit 2 (MCX_SAM_BGZF; mapcaller-mi355x -bgzf) writes the SAM file as BGZF and implies bit 1, because the text
  * has to be in HBM: every part's text is compressed where it lies by an mcx_deflater of the run's own (each part starts a fresh block) and only the blocks come back for
  * the one writer; the header goes out as blocks of its own, and the 28-byte EOF block ends the file.  A library appended with append_sam starts over the previous EOF
@@ -830,12 +888,16 @@ typedef struct mcx_file_opts {
     int32_t device_sam; /* bits of mcx_sam_bits.  1: the SAM text is made on the device (mcx_sam_format_dev's kernels) instead of by host threads; 0: as before */
     int64_t *avg_state; /* int64_t[4], see mcx_avg_init */
     int32_t shard_rank, shard_count; /* 0, 0: the whole input */
-    int32_t device_inflate; /* 1: BGZF input is inflated and CRC-checked on the device (mcx_inflate's kernel) instead of by a pool of host threads; 0: as before */
+    int32_t device_inflate; /* bits of mcx_inflate_bits.  1: BGZF input is inflated and CRC-checked on the device (mcx_inflate's kernel) instead of by a pool of host threads; 2: ordinary gzip streams take the resident route (with device_parse); 0: as before */
     int32_t device_parse; /* 1: plain FASTQ input is parsed and packed to 2-bit rows on the device (mcx_fastq_parse's kernels) instead of by the reader's pool of host threads; 0: as before */
     const mcx_exchange *exchange;    /* required when shard_count > 1: the shards walk ONE insert-size trajectory and
                                         decide the duplicate cap over ONE input order, so that SAM and profile equal the
                                         single-stream run's (rank/size must equal shard_rank/shard_count) */
 } mcx_file_opts;
+enum mcx_inflate_bits {
+    MCX_INFLATE_BGZF = 1, /* mapcaller-mi355x -gpu_inflate: BGZF read files are inflated on the device */
+    MCX_INFLATE_GZ = 2    /* mapcaller-mi355x -gpu_gz: ordinary gzip streams are, on the resident route (needs device_parse; alone it changes nothing) */
+};
 enum mcx_sam_bits {
     MCX_SAM_DEVICE = 1, /* the SAM text is made on the device */
     MCX_SAM_BGZF = 2,   /* ... and leaves it as BGZF blocks (implies MCX_SAM_DEVICE) */
@@ -862,7 +924,8 @@ enum mcx_route {
     MCX_ROUTE_BAM = 32,    /* ... as BAM records, not text */
     MCX_ROUTE_SORT = 64,   /* ... sorted by coordinate and merged on the device */
     MCX_ROUTE_INDEX = 128, /* ... and indexed there: the .bai is made of what the merge's chunks say of their records */
-    MCX_ROUTE_MARKDUP = 256 /* ... their duplicates decided and flagged there */
+    MCX_ROUTE_MARKDUP = 256, /* ... their duplicates decided and flagged there */
+    MCX_ROUTE_GZ = 512     /* the file's gzip stream was inflated on the device */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 /* What the context's last mcx_map_files* call with MCX_SAM_SORT did: runs, chunks of the merge, slices, slices that start inside a BGZF block, bytes read back from

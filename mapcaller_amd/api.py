@@ -71,6 +71,7 @@ SYMBOLS = [
     "mcx_ctx_set_multi", "mcx_multi_lines", "mcx_multi_copy", "mcx_stream_multi",
     "mcx_sam_format_dev", "mcx_sam_format", "mcx_sam_header",
     "mcx_inflater_create", "mcx_inflater_free", "mcx_inflate_dev", "mcx_inflate", "mcx_bgzf_inflate",
+    "mcx_gunzipper_create", "mcx_gunzipper_free", "mcx_gunzipper_reset", "mcx_gunzip_round_dev", "mcx_gunzip_text_dev", "mcx_gz_inflate_dev", "mcx_gz_inflate_dev_last",
     "mcx_fastq_parser_create", "mcx_fastq_parser_free", "mcx_fastq_parse_dev", "mcx_fastq_parse",
     "mcx_fastq_parser_set_rule", "mcx_stream_submit_dev", "mcx_files_route", "mcx_fastq_parser_set_format",
     "mcx_deflater_create", "mcx_deflater_free", "mcx_deflater_set_block", "mcx_bgzf_bound", "mcx_bgzf_deflate_dev", "mcx_bgzf_deflate", "mcx_bgzf_eof",
@@ -277,6 +278,15 @@ ROUTE_BAM = 32
 ROUTE_SORT = 64
 ROUTE_INDEX = 128
 ROUTE_MARKDUP = 256
+ROUTE_GZ = 512  # the file's ordinary gzip stream was inflated on the device
+INFLATE_BGZF, INFLATE_GZ = 1, 2  # bits of mcx_file_opts.device_inflate
+GZ_OK, GZ_DAMAGED, GZ_INPUT, GZ_CAPACITY, GZ_MORE = 0, 1, 2, 3, 4  # mcx_gz_status
+
+
+class GzRound(C.Structure):
+    """mcx_gz_round: what a round of a Gunzipper did."""
+    _fields_ = [("end_bit", C.c_uint64), ("text_bytes", C.c_uint64), ("crc32", C.c_uint32), ("final", C.c_uint32), ("status", C.c_uint32),
+                ("stretches", C.c_uint32), ("starts", C.c_uint32), ("chain", C.c_uint32), ("overflowed", C.c_uint32), ("ms", C.c_float * 4)]
 SAM_MARKDUP = 32  # (mcx_sam_bits, below)
 DUP_NONE, DUP_FRAGMENT, DUP_PAIR, DUP_SECOND_MATE = 0, 1, 2, 4  # mcx_dup_unit.kind: bits 0-1 the kind, bit 2 a paired input's fragment is the second read
 DUP_UNIT_DTYPE = np.dtype([("end0", "<u8"), ("end1", "<u8"), ("score", "<u4"), ("kind", "<u4")])  # mcx_dup_unit, 24 bytes
@@ -562,6 +572,20 @@ def lib() -> C.CDLL:
     L.mcx_inflate_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mcx_bgzf_inflate.restype = C.c_int64
     L.mcx_bgzf_inflate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_gunzipper_create.restype = C.c_int
+    L.mcx_gunzipper_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mcx_gunzipper_free.restype = None
+    L.mcx_gunzipper_free.argtypes = [C.c_void_p]
+    L.mcx_gunzipper_reset.restype = None
+    L.mcx_gunzipper_reset.argtypes = [C.c_void_p]
+    L.mcx_gunzip_round_dev.restype = C.c_int
+    L.mcx_gunzip_round_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(GzRound)]
+    L.mcx_gunzip_text_dev.restype = C.c_int
+    L.mcx_gunzip_text_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(GzRound)]
+    L.mcx_gz_inflate_dev.restype = C.c_int64
+    L.mcx_gz_inflate_dev.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mcx_gz_inflate_dev_last.restype = None
+    L.mcx_gz_inflate_dev_last.argtypes = [C.POINTER(C.c_uint64 * 2)]
     L.mcx_deflater_create.restype = C.c_int
     L.mcx_deflater_create.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
     L.mcx_deflater_free.restype = None
@@ -736,7 +760,7 @@ class Mapper:
     # ---- whole path ---------------------------------------------------------------------
     def map_files(self, fq1: str, fq2: Optional[str], sam: Optional[str], interleaved: bool = False, threads: int = 0,
                   shard: Optional[Tuple[int, int]] = None, exchange: Optional[Exchange] = None, append_sam: bool = False,
-                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
+                  device_sam: bool = False, device_inflate: bool = False, device_parse: bool = False, device_gz: bool = False, bgzf_sam: bool = False, bam: bool = False, sort: bool = False,
                   index: bool = False, markdup: bool = False, md: bool = False, read_group: Optional[str] = None, mate_tags: bool = False) -> dict:
         """Files in, SAM out (mcx_map_files_ex).  ``interleaved`` = -p, ``threads`` = -t; ``shard`` =
         (rank, count) with ``exchange``: map every count-th batch of the input stream while the shards
@@ -748,7 +772,8 @@ class Mapper:
         device (the same reads; other input is read as before); ``device_parse`` = -gpu_parse: plain FASTQ files, and plain FASTA files (one, or two as pairs; not sharded, not
         interleaved), are parsed and packed to 2-bit rows on the device (the same reads, the same end of the input; other input is read as before).
         ``device_inflate`` and ``device_parse`` together, on BGZF FASTQ or FASTA files (one, or two as pairs; not sharded, not interleaved, and with ``device_sam`` when a SAM file is written): the resident route — inflate,
-        parse, pack, map and SAM text all in HBM.  ``bgzf_sam`` = -bgzf: the SAM file is written as BGZF, its blocks deflated on the device (implies ``device_sam``; gzip -d of the
+        parse, pack, map and SAM text all in HBM.  ``device_gz`` = -gpu_gz: the same route for read files that are ORDINARY gzip streams (``device_gz`` and ``device_parse``; a pair may mix the two
+        kinds when both switches are set); without ``device_parse``, and on files the block-start search cannot cut, the call runs as without it.  ``bgzf_sam`` = -bgzf: the SAM file is written as BGZF, its blocks deflated on the device (implies ``device_sam``; gzip -d of the
         file is the SAM file; not sharded: ERR_UNSUPPORTED).  ``bam`` = -bam: ``sam`` is written as BAM — the records made on the device, framed by the same BGZF path (implies both;
         unsorted, no index; not sharded).  ``sort`` = -sort, only with ``bam``: the file is coordinate-sorted (samtools sort's order, ties in input order) — every part's records sorted
         on the device into a run of a temporary file beside ``sam`` (removed again), the runs merged chunk by chunk on the device behind the last batch; ERR_UNSUPPORTED without ``bam``,
@@ -768,7 +793,7 @@ class Mapper:
         fo.interleaved_pairs, fo.host_threads = int(interleaved), threads
         fo.append_sam = int(append_sam)
         fo.device_sam = (SAM_DEVICE if device_sam or bgzf_sam or bam else 0) | (SAM_BGZF if bgzf_sam or bam else 0) | (SAM_BAM if bam else 0) | (SAM_SORT if sort else 0) | (SAM_INDEX if index else 0) | (SAM_MARKDUP if markdup else 0) | (SAM_MD if md else 0) | (SAM_MC if mate_tags else 0)
-        fo.device_inflate = int(device_inflate)
+        fo.device_inflate = (INFLATE_BGZF if device_inflate else 0) | (INFLATE_GZ if device_gz else 0)
         fo.device_parse = int(device_parse)
         if self.avg[3] % 200:
             self.avg[3] += 200 - self.avg[3] % 200
@@ -785,7 +810,7 @@ class Mapper:
 
     def last_route(self) -> Tuple[int, int]:
         """mcx_files_route: per read file of the last map_files call, the stages that ran on the device as a sum of ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS
-        (the batches entered their slots from HBM), ROUTE_SAM, ROUTE_BGZF (the SAM text left the device as BGZF blocks) and ROUTE_BAM (... of BAM records); the second entry is 0 for one file."""
+        (the batches entered their slots from HBM), ROUTE_SAM, ROUTE_BGZF (the SAM text left the device as BGZF blocks), ROUTE_BAM (... of BAM records) and ROUTE_GZ (the file's ordinary gzip stream was inflated on the device); the second entry is 0 for one file."""
         r = (C.c_uint32 * 2)()
         _check(lib().mcx_files_route(self._h, r), "mcx_files_route")
         return int(r[0]), int(r[1])
@@ -1295,6 +1320,43 @@ class Inflater:
         return float(ms.value)
 
 
+class Gunzipper:
+    """mcx_gunzipper: an ordinary gzip member's deflate stream inflated on the device a round at a time — block starts searched for in stretches of
+    ``stretch_bytes`` compressed bytes (0: 64 KB), a wavefront per stretch inflating into 16-bit symbols, the 32 KB windows resolved along the chain, the
+    text and its CRC-32 made in parallel (mcx.h).  ``max_stretches`` (0: 2048) a round; ``arena_symbols`` (0: 8 per compressed byte of a full round)."""
+
+    def __init__(self, device: int = 0, stretch_bytes: int = 0, max_stretches: int = 0, arena_symbols: int = 0):
+        self._h = C.c_void_p()
+        _check(lib().mcx_gunzipper_create(device, stretch_bytes, max_stretches, arena_symbols, C.byref(self._h)), "mcx_gunzipper_create")
+
+    def close(self):
+        if self._h:
+            lib().mcx_gunzipper_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self):
+        """a new member begins: no window"""
+        lib().mcx_gunzipper_reset(self._h)
+
+    def round_dev(self, d_src, at: int, src_bytes: int, start_bit: int, src_is_end: bool) -> GzRound:
+        """mcx_gunzip_round_dev over d_src[at .. at + src_bytes), a uint8 torch tensor on the object's device that holds 8 bytes more behind them."""
+        assert at + src_bytes + 8 <= d_src.numel()
+        info = GzRound()
+        _check(lib().mcx_gunzip_round_dev(self._h, d_src.data_ptr() + at, src_bytes, start_bit, int(src_is_end), C.byref(info)), "mcx_gunzip_round_dev")
+        return info
+
+    def text_dev(self, d_dst, info: GzRound) -> GzRound:
+        """mcx_gunzip_text_dev: the last round's text into d_dst[0 .. info.text_bytes) (a uint8 torch tensor); info.crc32 and info.ms[3] are filled in."""
+        _check(lib().mcx_gunzip_text_dev(self._h, d_dst.data_ptr(), d_dst.numel(), C.byref(info)), "mcx_gunzip_text_dev")
+        return info
+
+
 class FastqParser:
     """mcx_fastq_parser: FASTQ text parsed on the device (set_rule: the plain rule — getline's lines, the default — or the .gz readers', FASTQ_RULE_GZ) — record boundaries, names, bases, NUL-padded qualities, 2-bit rows and the list of
     bytes that are not ACGT — on a stream of the object's own.  max_text_bytes / max_records size the first scratch (0: defaults); it grows on demand.
@@ -1462,6 +1524,21 @@ def bgzf_inflate(path: str, device: int = 0, cap: int = 0):
     n = C.c_uint64()
     total = int(lib().mcx_bgzf_inflate(path.encode(), device, out.ctypes.data, cap, C.byref(n)))
     return total, out[:min(cap, n.value)].tobytes()
+
+
+def gz_inflate_dev(path: str, device: int = 0, stretch_bytes: int = 0, round_stretches: int = 0, cap: int = 0):
+    """mcx_gz_inflate_dev: (the text's whole length | -1 no gzip file | -2 a damaged stream, the first min(cap, delivered) bytes of the text)."""
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_uint64()
+    total = int(lib().mcx_gz_inflate_dev(path.encode(), device, stretch_bytes, round_stretches, out.ctypes.data, cap, C.byref(n)))
+    return total, out[:min(cap, n.value)].tobytes()
+
+
+def gz_inflate_dev_last() -> Tuple[int, int]:
+    """mcx_gz_inflate_dev_last: (rounds begun, rounds whose bytes were staged while the round before ran) of this thread's last gz_inflate_dev"""
+    st = (C.c_uint64 * 2)()
+    lib().mcx_gz_inflate_dev_last(C.byref(st))
+    return int(st[0]), int(st[1])
 
 
 def _pool_of(aln: np.ndarray, cigars):

@@ -169,7 +169,7 @@ struct Timing {
 
 // where a run's reads come from, chosen once (open_input)
 enum Route {
-    kResident,   // BGZF FASTQ or FASTA with -gpu_inflate -gpu_parse: inflated, cut and packed in HBM (mcx_resident.hip)
+    kResident,   // BGZF (-gpu_inflate) or ordinary .gz (-gpu_gz) FASTQ or FASTA with -gpu_parse: inflated, cut and packed in HBM (mcx_resident.hip)
     kFastaDev,   // plain FASTA with -gpu_parse: the files' bytes go to HBM in chunks, a batch's records, bases, names, rows and odd bytes come back
     kMappedDev,  // plain FASTQ, mapped; -gpu_parse: a batch's text is parsed and packed on the device
     kMapped,     // plain FASTQ, mapped, parsed and packed by the pool
@@ -307,11 +307,11 @@ struct Run {
     int open_input()
     {
         const bool plain = plain_fastq(fq1) && (!two || plain_fastq(fq2));
-        if (!plain && opt.device_inflate && opt.device_parse && !sharded && !opt.interleaved_pairs && (!wants_sam || opt.device_sam)) {
+        if (!plain && (opt.device_inflate & (MCX_INFLATE_BGZF | MCX_INFLATE_GZ)) && opt.device_parse && !sharded && !opt.interleaved_pairs && (!wants_sam || opt.device_sam)) {
             const char *paths[2] = {fq1, two ? fq2 : nullptr};
             mcx_resident *r = nullptr;
-            if (int e = mcx_resident_open(idx->device, paths, nf, &r)) return e;
-            resident.reset(r); // (null: a file is no BGZF file, or the files differ in format — the route does not apply and the files are read as without it)
+            if (int e = mcx_resident_open(idx->device, paths, nf, (uint32_t)opt.device_inflate, &r)) return e;
+            resident.reset(r); // (null: a file is of a kind device_inflate has no bit for, the search cannot cut it, or the files differ in format — the route does not apply and the files are read as without it)
         }
         if (!plain && !resident && opt.device_parse && !sharded && !opt.interleaved_pairs && plain_fasta(fq1) && (!two || plain_fasta(fq2))) {
             const char *paths[2] = {fq1, two ? fq2 : nullptr};
@@ -326,7 +326,7 @@ struct Run {
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
         const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u) | (index ? (uint32_t)MCX_ROUTE_INDEX : 0u) | (markdup ? (uint32_t)MCX_ROUTE_MARKDUP : 0u);
         for (int f = 0; f < nf; f++)
-            route_bits[f] = sam_bit | (route == kResident ? (uint32_t)(MCX_ROUTE_INFLATE | MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
+            route_bits[f] = sam_bit | (route == kResident ? mcx_resident_inflate_bit(resident.get(), f) | (uint32_t)(MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
         return 0;
     }
@@ -373,7 +373,7 @@ struct Run {
     {
         int e = 0;
         std::string err;
-        const int inflate_device = opt.device_inflate ? idx->device : -1; // -gpu_inflate: BGZF files are inflated on the context's device
+        const int inflate_device = (opt.device_inflate & MCX_INFLATE_BGZF) ? idx->device : -1; // -gpu_inflate: BGZF files are inflated on the context's device
         if (!ps[0].open(fq1, err, inflate_device)) e = mcx_set_error(MCX_ERR_IO, err);
         if (e == 0 && two && !ps[1].open(fq2, err, inflate_device)) e = mcx_set_error(MCX_ERR_IO, err);
         if (e == 0 && two && ps[0].fastq() != ps[1].fastq()) e = mcx_set_error(MCX_ERR_IO, std::string(fq1) + " and " + fq2 + " are with different format");
@@ -1390,7 +1390,7 @@ struct Run {
         std::string e;
         for (size_t k = 0; k < t.each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(t.each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
-        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks, 32 BAM records): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
+        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks, 32 BAM records, 512 gunzip): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
         if (dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t.m_sam);
         if (bgzf) fprintf(stderr, "[mcx_map_files] bgzf: %llu bytes of text -> %llu bytes of blocks (%u bytes of text a block), the deflater took %.3f s of them\n",
                           (unsigned long long)zs.text_bytes, (unsigned long long)zs.out_bytes, zs.block, zs.seconds);

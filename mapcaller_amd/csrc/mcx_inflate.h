@@ -182,6 +182,13 @@ static MCX_INF_HD void bits_refill(Bits &b)
     b.p += (63 - b.cnt) >> 3; // (as many whole bytes as fit are kept, the rest is fetched again next time; behind src_len the position only counts)
     b.cnt |= 56;
 }
+// the reader set at bit `bit` of src, anywhere in it (a stretch of an ordinary gzip stream begins at any bit: mcx_gz_dev.h)
+static MCX_INF_HD void bits_start(Bits &b, const uint8_t *src, uint32_t src_len, uint32_t readable, uint64_t bit)
+{
+    b.src = src; b.src_len = src_len; b.readable = readable < src_len ? src_len : readable; b.p = (uint32_t)(bit >> 3); b.buf = 0; b.cnt = 0;
+    bits_refill(b);
+    b.buf >>= (uint32_t)(bit & 7u); b.cnt -= (uint32_t)(bit & 7u);
+}
 static MCX_INF_HD uint32_t bits_peek(const Bits &b, uint32_t n) { return (uint32_t)(b.buf & ((1ull << n) - 1)); }
 static MCX_INF_HD void bits_drop(Bits &b, uint32_t n) { b.buf >>= n; b.cnt -= n; }
 static MCX_INF_HD uint32_t bits_take(Bits &b, uint32_t n) { const uint32_t v = bits_peek(b, n); bits_drop(b, n); return v; }

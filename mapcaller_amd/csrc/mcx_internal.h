@@ -141,7 +141,8 @@ static inline size_t mcx_bgzf_member_at(const uint8_t *p, size_t n, size_t &xlen
     }
     return 0;
 }
-// The resident route (mcx_resident.hip; -gpu_inflate -gpu_parse on BGZF FASTQ): one or two read files whose text never leaves HBM.  open: *out stays null (and
+// The resident route (mcx_resident.hip; -gpu_inflate / -gpu_gz with -gpu_parse): one or two read files whose text never leaves HBM.  kinds: mcx_file_opts.device_inflate's bits — a BGZF file
+// needs MCX_INFLATE_BGZF, an ordinary gzip stream MCX_INFLATE_GZ (and a first round whose chain holds at least half of its stretches).  open: *out stays null (and
 // the call returns 0) when a file is no BGZF file named .gz, has no text, or the files are not all FASTQ (first text byte '@') or all FASTA — the route does not apply.  next: the next batch of up to
 // per_file records a file — more members inflated as needed, the records found under the GZ rule, rows / lengths / odd bytes (and, want_sam, names, their
 // offsets and NUL-padded qualities) written to *bufs, device buffers that belong to the caller's batch object (made on first use, grown on demand, freed with
@@ -158,7 +159,9 @@ struct mcx_resident_batch {
     const uint8_t *names, *qual; const uint32_t *name_off;                              // mcx_sam_part_dev's (qual null: FASTA)
     uint64_t n_bases, n_name_bytes;                                                     // (plain) what mcx_resident_host_out's bases and names groups hold
 };
-int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_resident **out);
+int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, mcx_resident **out);
+// MCX_ROUTE_INFLATE or MCX_ROUTE_GZ: how file f's text came to be in HBM
+uint32_t mcx_resident_inflate_bit(const mcx_resident *, int f);
 // The same object over plain FASTA files (-gpu_parse): the files' bytes go to HBM a launch at a time, the records are plain-rule FASTA's, and next leaves the
 // batch on the device (bufs: unused): host_out brings the groups of `out` (HOST pointers; rows with row_words 0 come ceil(longest / 16) words wide) back, any
 // number of times until the next batch is asked for.  fasta: the files are FASTA (either open).
@@ -168,6 +171,21 @@ bool mcx_resident_fasta(const mcx_resident *);
 void mcx_resident_close(mcx_resident *);
 int mcx_resident_next(mcx_resident *, mcx_resident_bufs **bufs, uint32_t per_file, int32_t max_read_len, bool want_sam, mcx_resident_batch *out);
 void mcx_resident_bufs_free(mcx_resident_bufs *);
+// -gpu_gz (mcx_gz_dev.hip): mcx_gunzip_round_dev in two halves — begin queues the search, the inflate and the copy of the stretches' records and returns at once, end
+// waits, walks the chain and runs the windows — and an ordinary .gz file as a whole: the one walker of members, trailers and staging (mcx_gz_dev.h's Reader), for
+// mcx_gz_inflate_dev and the resident route.  open: data[0 .. size) is the whole file and outlives the object; *out stays null (the call returns 0) when it does
+// not begin with a gzip header.  next: 1 — a round whose info->text_bytes of text (0 is possible) mcx_gz_file_text fetches into d_dst —, 0 at the input's end
+// (failed: where the stream is damaged), or an error.  text: *counts false — the member's trailer does not match: nothing of the round is handed on, the input ends.
+struct mcx_gz_file;
+int mcx_gunzip_round_begin(mcx_gunzipper *, const uint8_t *d_src, uint64_t src_bytes, uint32_t start_bit, int src_is_end);
+int mcx_gunzip_round_end(mcx_gunzipper *, mcx_gz_round *info);
+int mcx_gz_file_open(int device, const uint8_t *data, size_t size, uint64_t stretch_bytes, uint32_t round_stretches, mcx_gz_file **out);
+int mcx_gz_file_next(mcx_gz_file *, mcx_gz_round *info);
+int mcx_gz_file_text(mcx_gz_file *, uint8_t *d_dst, uint64_t dst_cap, mcx_gz_round *info, bool *counts);
+bool mcx_gz_file_failed(const mcx_gz_file *);
+uint64_t mcx_gz_file_delivered(const mcx_gz_file *);
+void mcx_gz_file_staging(const mcx_gz_file *, uint64_t *rounds, uint64_t *staged_hits); // rounds begun, and those whose bytes the prefetch had staged
+void mcx_gz_file_free(mcx_gz_file *);
 void *mcx_pinned_alloc(size_t bytes); // page-locked host memory (null on failure); mcx_pinned_free accepts null
 void mcx_pinned_free(void *);
 

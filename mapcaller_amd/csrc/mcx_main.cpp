@@ -73,6 +73,9 @@ static void usage(const char *prog)
             "         -gpu_inflate  inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads; other input is read as before)\n"
             "                       with -gpu_parse on BGZF FASTQ or FASTA (one file, or two as pairs; not -p, not -gpus N; -gpu_sam where a SAM file is written):\n"
             "                       inflate, parse, pack, map and SAM text all stay on the GPU, only records or SAM text come back\n"
+            "         -gpu_gz       with -gpu_parse: ordinary .gz read files (gzip, pigz; not bgzip's container) are inflated on the GPU too — block starts searched for in\n"
+            "                       stretches of the stream, a wavefront a stretch — and take the same road as -gpu_inflate -gpu_parse (same reads; same conditions; a pair may\n"
+            "                       mix BGZF and ordinary files with both switches); files the search cannot cut, and -gpu_gz without -gpu_parse, are read as before\n"
             "         -gpu_parse    parse plain FASTQ and plain FASTA read files and pack their reads on the GPU instead of with host threads (same reads; FASTA: one file, or two\n"
             "                       as pairs, not -p, not -gpus N; other input is read as before)\n"
             "         -gvcf         GVCF mode\n"
@@ -187,7 +190,8 @@ int main(int argc, char **argv)
         else if (p == "-md") fo.device_sam |= MCX_SAM_MD;
         else if (p == "-rg" && i + 1 < argc) { rg_arg = argv[++i]; want_rg = true; }
         else if (p == "-mc") fo.device_sam |= MCX_SAM_MC;
-        else if (p == "-gpu_inflate") fo.device_inflate = 1;
+        else if (p == "-gpu_inflate") fo.device_inflate |= MCX_INFLATE_BGZF;
+        else if (p == "-gpu_gz") fo.device_inflate |= MCX_INFLATE_GZ;
         else if (p == "-gpu_parse") fo.device_parse = 1;
         else { fprintf(stderr, "Warning! Unknow parameter: %s\n", argv[i]); usage(argv[0]); return 0; }
     }

@@ -1,4 +1,4 @@
-// mapcaller_amd/csrc/mcx_resident.hip — the file front end's resident route (-gpu_inflate -gpu_parse on BGZF FASTQ): read files whose text stays in HBM from
+// mapcaller_amd/csrc/mcx_resident.hip — the file front end's resident route (-gpu_inflate -gpu_parse on BGZF FASTQ; -gpu_gz -gpu_parse on ordinary .gz): read files whose text stays in HBM from
 // the compressed bytes to the batch's 2-bit rows (mcx_resident_open / _next / _close, mcx_resident_bufs_free; reached from mcx_files.cpp's reader thread alone).
 //
 // Replaces, for such files, Parser::feed_bgzf + Parser::entry + pack_row of mcx_files.cpp — whose rules it keeps: the members are walked into stretches of at
@@ -13,6 +13,9 @@
 // PLAIN FASTA under -gpu_parse alone (mcx_resident_open_plain): the same object over plain files — `more` sends the next bytes of the mapped file to HBM instead
 // of inflating members, the parser runs under plain-rule FASTA, and the batch's arrays come back to host buffers (mcx_resident_host_out): the counting, the carry
 // and the ends of the input are this file's for both.
+// ORDINARY .gz under -gpu_gz -gpu_parse: a third kind of File — `more` runs one round of the file's gzip stream through mcx_gz_file_next / _text (mcx_gz_dev.hip: members,
+// trailers and staging are that file's), making room between the two halves, and the text lands behind `have`; the parser runs under the GZ rule as for BGZF.  The
+// first round is run by mcx_resident_open: a chain of fewer than half of its stretches, and the route does not apply to the call.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -29,6 +32,7 @@
 #include "../../include/mcx.h"
 #include "mcx_fastq.h"
 #include "mcx_internal.h"
+// (mcx_gz_file_*: an ordinary .gz file's rounds, mcx_gz_dev.hip)
 
 #define HIP_TRY(expr)                                                                                  \
     do {                                                                                               \
@@ -67,6 +71,11 @@ struct File {
     bool walk_end = false;   // no member follows: the file's end, something that is no member, or a damaged stretch
     bool eof = false;        // ... and everything before that is in the text
     bool plain = false;      // a plain file: its bytes are the text
+    mcx_gz_file *gz = nullptr; // an ordinary gzip stream (-gpu_gz): its rounds go through a gunzipper of the file's own (mcx_gz_dev.hip)
+    uint32_t gz_rounds = 0;  // ... rounds run so far
+    bool gz_taken = false;   // ... the route applies to the call (mcx_resident_open has returned the object)
+    bool gz_uncut = false;   // ... its first round's chain holds fewer than half of its stretches: the route does not apply
+    std::string path;
     uint64_t ask = 0;        // (plain) bytes the next `more` should bring, when more than a launch: what the batch in hand still lacks, by its records so far
     mcx_inflater *inf = nullptr;
     DBuf text[2]; int cur = 0;       // the file's text in HBM: text[cur][start .. have) is not consumed yet
@@ -117,6 +126,27 @@ int ensure_room(mcx_resident *R, File &f, uint64_t need)
 int more(mcx_resident *R, File &f)
 {
     if (f.walk_end) { f.eof = true; return 0; }
+    if (f.gz) { // the next round(s) of the gzip stream: the text grows behind `have`, or the stream is at its end
+        for (;;) {
+            mcx_gz_round info;
+            const int r = mcx_gz_file_next(f.gz, &info);
+            if (r < 0) return r;
+            bool counts = false;
+            if (r > 0) {
+                if (f.gz_rounds++ == 0 && (info.stretches < 2 || info.chain * 2 < info.stretches)) { f.gz_uncut = true; f.walk_end = f.eof = true; return 0; }
+                if (int rc = ensure_room(R, f, info.text_bytes + 64)) return rc;
+                if (int rc = mcx_gz_file_text(f.gz, (uint8_t *)f.text[f.cur].p + f.have, f.text[f.cur].cap - f.have, &info, &counts)) return rc;
+            }
+            if (!counts) { // the input's end, or a round that is not handed on: a damaged stream, a trailer that does not match
+                if (mcx_gz_file_failed(f.gz) && f.gz_taken) // (while the files are opened the route is not taken yet: a first round that fails leaves the call, and the word, to the host reader)
+                    fprintf(stderr, "[mcx_map_files] -gpu_gz: %s: the gzip stream is damaged or ends early; the file's input ends behind %llu bytes of text\n", f.path.c_str(), (unsigned long long)mcx_gz_file_delivered(f.gz));
+                f.walk_end = f.eof = true;
+                return 0;
+            }
+            f.have += info.text_bytes;
+            if (info.text_bytes) return 0;
+        }
+    }
     if (f.plain) { // the next bytes of the file, as they are
         const uint64_t n = std::min<uint64_t>(std::max(R->launch_bytes, f.ask), f.size - f.o);
         if (n) {
@@ -211,6 +241,7 @@ void mcx_resident_close(mcx_resident *R)
     if (R->parser) mcx_fastq_parser_free(R->parser);
     for (File &f : R->f) {
         if (f.inf) mcx_inflater_free(f.inf); // (waits for what is still on the device)
+        if (f.gz) mcx_gz_file_free(f.gz);
         for (DBuf &b : f.text) if (b.p) (void)hipFree(b.p);
         if (f.map) munmap((void *)f.map, f.size);
     }
@@ -229,12 +260,14 @@ void mcx_resident_bufs_free(mcx_resident_bufs *b)
     delete b;
 }
 
-int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_resident **out)
+uint32_t mcx_resident_inflate_bit(const mcx_resident *R, int f) { return R->f[f].gz ? (uint32_t)MCX_ROUTE_GZ : (uint32_t)MCX_ROUTE_INFLATE; }
+
+int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, mcx_resident **out)
 {
     *out = nullptr;
     mcx_resident *R = new mcx_resident();
     R->device = device; R->n_files = n_files;
-    bool applies = true;
+    bool applies = true, is_gz[2] = {false, false};
     for (int i = 0; i < n_files && applies; i++) {
         const std::string path(paths[i]);
         File &f = R->f[i];
@@ -249,7 +282,10 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_r
         }
         close(fd);
         size_t xlen = 0;
-        applies = applies && mcx_bgzf_member_at(f.map, f.size, xlen) != 0; // BGZF
+        if (!applies) break;
+        f.path = path;
+        is_gz[i] = mcx_bgzf_member_at(f.map, f.size, xlen) == 0; // not BGZF: an ordinary gzip stream, or nothing of the kind (mcx_gz_file_open says which)
+        applies = (kinds & (is_gz[i] ? MCX_INFLATE_GZ : MCX_INFLATE_BGZF)) != 0;
     }
     if (!applies) { mcx_resident_close(R); return 0; }
     const char *env = getenv("MCX_RESIDENT_LAUNCH_BYTES");
@@ -258,7 +294,12 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_r
     R->max_members = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(R->launch_bytes / 1024, 64), 1u << 18);
     int rc = 0;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_inflate -gpu_parse: no stream on the context's device"); }
-    for (int i = 0; i < n_files && rc == 0; i++) rc = mcx_inflater_create_dev(device, R->max_src, R->max_members, &R->f[i].inf);
+    const char *gz_s = getenv("MCX_GZ_STRETCH"), *gz_n = getenv("MCX_GZ_ROUND_STRETCHES");
+    for (int i = 0; i < n_files && rc == 0 && applies; i++) {
+        if (!is_gz[i]) { rc = mcx_inflater_create_dev(device, R->max_src, R->max_members, &R->f[i].inf); continue; }
+        rc = mcx_gz_file_open(device, R->f[i].map, R->f[i].size, gz_s && atoll(gz_s) > 0 ? (uint64_t)atoll(gz_s) : 0, gz_n && atoll(gz_n) > 0 ? (uint32_t)atoll(gz_n) : 512, &R->f[i].gz);
+        if (rc == 0 && !R->f[i].gz) applies = false; // (no gzip header)
+    }
     if (rc == 0) rc = mcx_fastq_parser_create(device, 0, 0, &R->parser);
     if (rc == 0) rc = mcx_fastq_parser_set_rule(R->parser, MCX_FASTQ_RULE_GZ);
     // What the host reader judges FASTQ or FASTA by is the first byte of the first stretch it is handed ('@': FASTQ, CheckReadFormat, GetData.cpp:22-31): a first
@@ -269,13 +310,14 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, mcx_r
         while (rc == 0 && f.have == 0 && !f.eof) rc = more(R, f);
         uint8_t first = 0;
         if (rc == 0 && f.have && hipMemcpy(&first, f.text[f.cur].p, 1, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_inflate -gpu_parse: copy from the device failed"); }
-        applies = f.have != 0;
+        applies = f.have != 0 && !f.gz_uncut;
         fastq[i] = first == '@';
     }
     if (n_files == 2 && fastq[0] != fastq[1]) applies = false;
     R->fasta = !fastq[0];
     if (rc == 0 && applies && R->fasta) rc = mcx_fastq_parser_set_format(R->parser, MCX_READS_FASTA);
     if (rc || !applies) { mcx_resident_close(R); return rc; }
+    for (File &f : R->f) f.gz_taken = true;
     *out = R;
     return 0;
 }

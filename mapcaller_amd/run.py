@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MapCaller's command line on one or several MI355X of a node.
 
-    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort [-markdup] [-index]]] [-md] [-rg LINE] [-mc] [-gpu_inflate] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
+    python -m mapcaller_amd.run -i idx -f r1.fq [-f2 r2.fq] [-alg nw|ksw2] [-sam out.sam [-gpu_sam | -bgzf] | -bam out.bam [-sort [-markdup] [-index]]] [-md] [-rg LINE] [-mc] [-gpu_inflate] [-gpu_gz] [-gpu_parse] [-vcf out.vcf | -no_vcf] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 -m mapcaller_amd.run -i idx -f r1.fq -f2 r2.fq -sam out.sam -vcf out.vcf
 
 One process per GPU.  The input stream is cut into batches that are dealt to the ranks in turn
@@ -55,6 +55,7 @@ def parse(argv):
     ap.add_argument("-gpu_sam", dest="gpu_sam", action="store_true", help="make the SAM text on the GPU instead of with host threads (same bytes)")
     ap.add_argument("-bgzf", dest="bgzf", action="store_true", help="write the SAM file as BGZF, its blocks deflated on the GPU (implies -gpu_sam; gzip -d gives the plain file's bytes; one process only)")
     ap.add_argument("-gpu_parse", dest="gpu_parse", action="store_true", help="parse plain FASTQ and plain FASTA read files and pack their reads on the GPU instead of with host threads (same reads)")
+    ap.add_argument("-gpu_gz", dest="gpu_gz", action="store_true", help="with -gpu_parse (and -gpu_sam where a SAM file is written): ordinary .gz read files (gzip, pigz; not BGZF) are inflated on the GPU and the reads stay there from the compressed bytes to the SAM text (same reads); files the block-start search cannot cut, and -gpu_gz without -gpu_parse, are read as before")
     ap.add_argument("-gpu_inflate", dest="gpu_inflate", action="store_true", help="inflate BGZF (bgzip) read files on the GPU instead of with host threads (same reads); with -gpu_parse on BGZF FASTQ or FASTA (and -gpu_sam where a SAM file is written) the reads stay on the GPU from the compressed bytes to the SAM text")
     ap.add_argument("-indel", type=int, default=30, help="maximal indel size (MaxPosDiff), at most 100")
     ap.add_argument("-maxmm", type=float, default=0.05, help="maximal mismatch rate in read alignment (MaxMisMatchRate)")
@@ -155,7 +156,7 @@ def main(argv=None):
         f2 = a.f2[k] if a.f2 else None
         # (the ranks write into the one SAM file, every batch's lines at their final place: mcx_map_files_ex)
         st = mapper.map_files(f1, f2, a.sam or None, interleaved=a.interleaved, threads=a.threads,
-                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort, index=a.bai, markdup=a.markdup, md=a.md, read_group=a.rg, mate_tags=a.mc)
+                              shard=(rank, world) if world > 1 else None, exchange=link, append_sam=k > 0, device_sam=a.gpu_sam, device_inflate=a.gpu_inflate, device_gz=a.gpu_gz, device_parse=a.gpu_parse, bgzf_sam=a.bgzf, bam=a.bam, sort=a.sort, index=a.bai, markdup=a.markdup, md=a.md, read_group=a.rg, mate_tags=a.mc)
         for key in totals:
             totals[key] += st[key]
         if td:
