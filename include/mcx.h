@@ -767,16 +767,19 @@ void mcx_fastq_parser_free(mcx_fastq_parser *);
 enum mcx_fastq_rule { MCX_FASTQ_RULE_PLAIN = 0, MCX_FASTQ_RULE_GZ = 1 };
 int  mcx_fastq_parser_set_rule(mcx_fastq_parser *, int rule); /* the rule of the parser's following calls; MCX_ERR_ARG: no such rule */
 enum mcx_reads_format { MCX_READS_FASTQ = 0, MCX_READS_FASTA = 1 };
+enum mcx_reads_format_bam { MCX_READS_BAM = 2 }; /* a third format: BAM records (below, "BAM read input"), set with mcx_fastq_parser_set_reads */
 int  mcx_fastq_parser_set_format(mcx_fastq_parser *, int format); /* what the parser's following calls take the text for (sticky, like the rule); MCX_ERR_ARG: no such format */
 
 typedef struct mcx_fastq_rec { uint32_t name, name_len, seq, rlen, qual, q_take; } mcx_fastq_rec; /* 24 bytes; offsets into the record's own text */
 enum mcx_fastq_stop { MCX_FASTQ_MORE = 0, MCX_FASTQ_END = 1, MCX_FASTQ_EMPTY = 2, MCX_FASTQ_TOO_LONG = 3 };
+enum mcx_fastq_stop_bam { MCX_FASTQ_DAMAGED = 4, MCX_FASTQ_UNPAIRED = 5 }; /* two more stops, under MCX_READS_BAM alone */
 
 typedef struct mcx_fastq_in {
     const uint8_t *text[2]; uint64_t bytes[2];  /* text[1] NULL: one file.  Two: read 2i is record i of text[0], read 2i+1 record i of text[1]; each < 4 GiB; any alignment */
     uint32_t max_records;                       /* per text */
     int32_t max_read_len;
     int32_t final;                              /* 0: more text follows, only records whose four lines all end in '\n' inside the text are taken */
+    int32_t n_ref;                              /* MCX_READS_BAM alone: the n_ref of the file's header (mcx_bam_reads_header), which a record's refID is held against */
 } mcx_fastq_in;
 typedef struct mcx_fastq_out {                  /* any group may be NULL: not produced */
     mcx_fastq_rec *recs[2];
@@ -788,6 +791,31 @@ typedef struct mcx_fastq_info { uint32_t n_records[2], stop[2]; uint64_t consume
 
 int mcx_fastq_parse_dev(mcx_fastq_parser *, const mcx_fastq_in *d_in, const mcx_fastq_out *d_out, mcx_fastq_info *info); /* structs in host memory, pointers in them device pointers */
 int mcx_fastq_parse(mcx_fastq_parser *, const mcx_fastq_in *in, const mcx_fastq_out *out, mcx_fastq_info *info);         /* host buffers, staged inside */
+
+/* ---- BAM read input (MCX_READS_BAM; mcx_bam_in.hip, the rules in mcx_bam_in.h) ----------------------------------------------------------------
+ * The text is what follows a BAM file's header (mcx_bam_reads_header says where): records back to back, found by the chain o -> o + 4 + block_size from offset 0.
+ * One text only (text[1] != NULL: MCX_ERR_ARG); the rule setting is ignored; mcx_fastq_in.n_ref is the header's.  A record is PLAUSIBLE when
+ * 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size <= 2^28, l_read_name >= 1 with a NUL as the name's last byte, l_seq >= 0 and
+ * -1 <= refID, next_refID < n_ref.  The first record that is not stops the text with MCX_FASTQ_DAMAGED; one whose bytes run past the text with MCX_FASTQ_MORE
+ * (final == 0) or MCX_FASTQ_DAMAGED (final == 1); a text that ends on a record boundary with MCX_FASTQ_END.  The records before a stop count.  TAKEN are the
+ * records with flag & 0x900 == 0 (secondary and supplementary lines are skipped, as `samtools fastq` skips them), and of a taken record come what the plain rule
+ * gives of its FASTQ twin `@read_name\nSEQ\n+\nQUAL\n`: the name by the header rule, rlen = l_seq (0: EMPTY; > max_read_len: TOO_LONG), the bases
+ * "=ACMGRSVTWYHKDBN"[nibble], the qualities min(q, 93) + 33 (none, q_take = 0, when the first quality byte is 0xFF); with flag 0x10 the read as sequenced: bases
+ * reversed and complemented (IUPAC codes included), qualities reversed.  mcx_fastq_rec holds offsets into the text: seq the first packed-base byte, qual the first
+ * quality byte.  consumed[0] is a record boundary: skipped records in front of a stop count as consumed.
+ * mcx_fastq_parser_set_mates(parser, 1) (sticky): taken records count in twos (max_records: its even part) — the first with 0x1 and 0x40, the second with 0x1 and
+ * 0x80, their names equal after the header rule; the first two that are not stop the text with MCX_FASTQ_UNPAIRED, the pairs before count; a single taken record
+ * at the end gives MORE (final == 0) or UNPAIRED (final == 1); consumed[0] lies behind the last taken pair and the skipped records that follow it.
+ * The records are found in chunks of 64 KB (MCX_BAM_CHUNK=bytes, at least 256: a debug override no result depends on): a search for a plausible start per chunk, a
+ * walk per chunk, a join on the device that walks again every chunk the chain does not arrive at where the search said, an exclusive sum and the write.
+ * mcx_bam_reads_header: 0 with *records_at (the first record's offset) and *n_ref; 1 when `bytes` holds too little of the header; -1 when the bytes are no BAM.
+ * mcx_bam_reads_last: of the parser's last call — records walked, taken, skipped for 0x900, the flag of the first taken record, chunks, chunks whose searched
+ * start was not on the chain. */
+int mcx_bam_reads_header(const uint8_t *text, uint64_t bytes, uint64_t *records_at, int32_t *n_ref);
+int mcx_fastq_parser_set_reads(mcx_fastq_parser *, int format); /* mcx_fastq_parser_set_format for all three formats: MCX_READS_FASTQ, MCX_READS_FASTA, MCX_READS_BAM (set_format itself takes its two alone, as before) */
+int mcx_fastq_parser_set_mates(mcx_fastq_parser *, int mates);
+int mcx_bam_reads_last(mcx_fastq_parser *, uint64_t stats[6]);
+int mcx_bam_reads_last_ms(mcx_fastq_parser *, float ms[4]); /* the last call's search, walk, join and unpack on the device, by events on the parser's stream */
 
 /* ---- files: MapCaller -i <prefix> -f A [-f2 B] -alg nw|ksw2 -sam out (src/main.cpp:212-321) */
 int mcx_map_files(mcx_ctx *, const char *fq1, const char *fq2, const char *sam_path, mcx_stats *stats);
@@ -925,7 +953,8 @@ enum mcx_route {
     MCX_ROUTE_SORT = 64,   /* ... sorted by coordinate and merged on the device */
     MCX_ROUTE_INDEX = 128, /* ... and indexed there: the .bai is made of what the merge's chunks say of their records */
     MCX_ROUTE_MARKDUP = 256, /* ... their duplicates decided and flagged there */
-    MCX_ROUTE_GZ = 512     /* the file's gzip stream was inflated on the device */
+    MCX_ROUTE_GZ = 512,    /* the file's gzip stream was inflated on the device */
+    MCX_ROUTE_BAM_IN = 1024 /* the file is BAM: its records were found and unpacked on the device (beside INFLATE | PARSE | ROWS) */
 };
 int mcx_files_route(mcx_ctx *, uint32_t route[2]);
 /* What the context's last mcx_map_files* call with MCX_SAM_SORT did: runs, chunks of the merge, slices, slices that start inside a BGZF block, bytes read back from

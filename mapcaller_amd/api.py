@@ -81,6 +81,7 @@ SYMBOLS = [
     "mcx_pass_last_shape",
     "mcx_md_dev", "mcx_md", "mcx_md_last_ms",
     "mcx_sam_format_tags_dev", "mcx_sam_format_tags", "mcx_bam_format_tags_dev", "mcx_bam_format_tags", "mcx_rg_parse", "mcx_sam_header_rg", "mcx_bam_header_rg", "mcx_map_files_rg",
+    "mcx_bam_reads_header", "mcx_fastq_parser_set_reads", "mcx_fastq_parser_set_mates", "mcx_bam_reads_last", "mcx_bam_reads_last_ms",
 ]
 # include/mcx_comm.h (libmcx_comm.so: the RCCL side, loaded by the native CLI only)
 COMM_LIB_PATH = os.path.join(_HERE, "libmcx_comm.so")
@@ -272,6 +273,8 @@ MEMBER_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u
 # mcx_fastq_rec: one FASTQ record as offsets into its own text; mcx_fastq_stop
 FASTQ_RULE_PLAIN, FASTQ_RULE_GZ = 0, 1  # mcx_fastq_rule
 READS_FASTQ, READS_FASTA = 0, 1  # mcx_reads_format
+READS_BAM = 2  # mcx_reads_format_bam: BAM records, found and unpacked on the device
+ROUTE_BAM_IN = 1024  # the read file is BAM
 ROUTE_INFLATE, ROUTE_PARSE, ROUTE_ROWS, ROUTE_SAM = 1, 2, 4, 8  # mcx_route
 ROUTE_BGZF = 16
 ROUTE_BAM = 32
@@ -298,6 +301,7 @@ SAM_DEVICE, SAM_BGZF, SAM_BAM, SAM_SORT = 1, 2, 4, 8  # mcx_sam_bits (mcx_file_o
 BGZF_BLOCK = 65280  # bytes of text per BGZF block: bgzip's cut
 REC_DTYPE = np.dtype([("name", "<u4"), ("name_len", "<u4"), ("seq", "<u4"), ("rlen", "<u4"), ("qual", "<u4"), ("q_take", "<u4")])
 FASTQ_MORE, FASTQ_END, FASTQ_EMPTY, FASTQ_TOO_LONG = 0, 1, 2, 3
+FASTQ_DAMAGED, FASTQ_UNPAIRED = 4, 5  # mcx_fastq_stop_bam: under READS_BAM alone
 
 
 class BaiRun(C.Structure):
@@ -310,7 +314,7 @@ BAI_RUN_DTYPE = np.dtype([("ref_id", "<i4"), ("bin", "<u4"), ("u", "<u8"), ("n_m
 
 class FastqIn(C.Structure):
     """mcx_fastq_in (pointers as integers: host or device)"""
-    _fields_ = [("text", C.c_void_p * 2), ("bytes", C.c_uint64 * 2), ("max_records", C.c_uint32), ("max_read_len", C.c_int32), ("final", C.c_int32)]
+    _fields_ = [("text", C.c_void_p * 2), ("bytes", C.c_uint64 * 2), ("max_records", C.c_uint32), ("max_read_len", C.c_int32), ("final", C.c_int32), ("n_ref", C.c_int32)]
 
 
 class FastqOut(C.Structure):
@@ -469,6 +473,16 @@ def lib() -> C.CDLL:
     L.mcx_fastq_parser_set_rule.argtypes = [C.c_void_p, C.c_int]
     L.mcx_fastq_parser_set_format.restype = C.c_int
     L.mcx_fastq_parser_set_format.argtypes = [C.c_void_p, C.c_int]
+    L.mcx_fastq_parser_set_reads.restype = C.c_int
+    L.mcx_fastq_parser_set_reads.argtypes = [C.c_void_p, C.c_int]
+    L.mcx_fastq_parser_set_mates.restype = C.c_int
+    L.mcx_fastq_parser_set_mates.argtypes = [C.c_void_p, C.c_int]
+    L.mcx_bam_reads_last.restype = C.c_int
+    L.mcx_bam_reads_last.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mcx_bam_reads_last_ms.restype = C.c_int
+    L.mcx_bam_reads_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mcx_bam_reads_header.restype = C.c_int
+    L.mcx_bam_reads_header.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.mcx_stream_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_map32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.mcx_stream_mapped32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -786,6 +800,9 @@ class Mapper:
         ``read_group`` = -rg: an @RG line in bwa mem -R's form (``\\t`` or real TABs between the fields, exactly one ID; checked by rg_parse: ERR_ARG) that ends the header,
         and RG:Z:<ID> on every line; ``mate_tags`` = -mc: MC:Z and MQ:i on the lines of pairs whose mate is mapped and whose FLAG has 0x8 clear (the rule: mcx.h at
         mcx_sam_tags) — both with every output above and with the host formatter; ERR_UNSUPPORTED in a sharded run, ``mate_tags`` also on a mapper with ``multi``.
+        BAM input: ``fq1`` a BGZF file whose text begins ``BAM\\1`` (any name), ``fq2`` None — the resident route by itself (the three device switches are implied for
+        the call), pairs or single reads by the first taken record's flag 0x1 (``interleaved`` is ignored); ERR_UNSUPPORTED with a second file or in a sharded run,
+        ERR_ARG when the mates are not neighbours; ``last_route()`` shows ROUTE_BAM_IN.
         ``last_route()`` says which stages ran on the device."""
         st = Stats()
         fo = FileOpts()
@@ -1389,13 +1406,34 @@ class FastqParser:
         """mcx_fastq_parser_set_format: READS_FASTQ (the default) or READS_FASTA for the calls that follow (FASTA: no qualities; under the plain rule multi-line records)"""
         _check(lib().mcx_fastq_parser_set_format(self._h, fmt), "mcx_fastq_parser_set_format")
 
+    def set_reads(self, fmt: int) -> None:
+        """mcx_fastq_parser_set_reads: set_format for all three formats — READS_FASTQ, READS_FASTA or READS_BAM (one text, the records behind the file's header; the
+        calls take n_ref=...)"""
+        _check(lib().mcx_fastq_parser_set_reads(self._h, fmt), "mcx_fastq_parser_set_reads")
+
+    def set_mates(self, mates: bool) -> None:
+        """mcx_fastq_parser_set_mates: under READS_BAM, taken records count in twos (0x1 | 0x40, then 0x1 | 0x80, equal names) for the calls that follow"""
+        _check(lib().mcx_fastq_parser_set_mates(self._h, int(mates)), "mcx_fastq_parser_set_mates")
+
+    def bam_last(self) -> dict:
+        """mcx_bam_reads_last: the last READS_BAM call's counters"""
+        st = (C.c_uint64 * 6)()
+        _check(lib().mcx_bam_reads_last(self._h, st), "mcx_bam_reads_last")
+        return dict(zip(("walked", "taken", "skipped", "first_flag", "chunks", "off_chain"), (int(x) for x in st)))
+
+    def bam_last_ms(self) -> tuple:
+        """mcx_bam_reads_last_ms: the last READS_BAM call's (search, walk, join, unpack) on the device, in ms"""
+        ms = (C.c_float * 4)()
+        _check(lib().mcx_bam_reads_last_ms(self._h, ms), "mcx_bam_reads_last_ms")
+        return tuple(float(x) for x in ms)
+
     @staticmethod
     def _structs(ptr, size, texts, max_records, max_read_len, final, o):
         fi, fo = FastqIn(), FastqOut()
         text_bytes = o.get("text_bytes")
         for t, x in enumerate(texts):
             fi.text[t], fi.bytes[t] = ptr(x), size(x) if text_bytes is None else text_bytes[t]
-        fi.max_records, fi.max_read_len, fi.final = max_records, max_read_len, int(final)
+        fi.max_records, fi.max_read_len, fi.final, fi.n_ref = max_records, max_read_len, int(final), o.get("n_ref", 0)
         for t, x in enumerate(o.get("recs") or []):
             fo.recs[t] = ptr(x) if x is not None else None
         for k in ("bases", "off", "qual", "names", "name_off", "rows", "len", "odd"):
@@ -1439,6 +1477,14 @@ class FastqParser:
         n = C.c_uint32()
         _check(lib().mcx_fastq_grown(self._h, C.byref(n)), "mcx_fastq_grown")
         return int(n.value)
+
+
+def bam_reads_header(data) -> tuple:
+    """mcx_bam_reads_header over a BAM file's inflated bytes: (rc, records_at, n_ref) — rc 0, 1 (too few bytes) or -1 (no BAM)"""
+    buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    at, n_ref = C.c_uint64(), C.c_int32()
+    rc = lib().mcx_bam_reads_header(buf.ctypes.data, len(data), C.byref(at), C.byref(n_ref))
+    return rc, int(at.value), int(n_ref.value)
 
 
 class Deflater:

@@ -368,6 +368,8 @@ struct mcx_fastq_parser {
     int device = 0;
     hipStream_t stream = nullptr;
     int rule = MCX_FASTQ_RULE_PLAIN, format = MCX_READS_FASTQ;
+    int mates = 0, host_n_ref = 0; // MCX_READS_BAM: taken records count in twos (set_mates); the n_ref of the host form's call in hand
+    mcx_bam_in *bam = nullptr;     // ... its scratch and counters (mcx_bam_in.hip), made by the first such call
     Buf fp[2], bo[2], fa_bases; // plain FASTA: the lines' payloads and their sums (flags, their sums and the headers' lines share pc, po, ps); the reads' bases back to back
     Buf cnt[2], pre[2], ls[2], pc[2], po[2], ps[2], recs[2], rl, nl, oc, off, noff, ooff, tmp, info;
     DevInfo *h_info = nullptr; // page-locked
@@ -410,6 +412,7 @@ extern "C" void mcx_fastq_parser_free(mcx_fastq_parser *p)
     Buf *all[] = {&p->cnt[0], &p->cnt[1], &p->pre[0], &p->pre[1], &p->ls[0], &p->ls[1], &p->pc[0], &p->pc[1], &p->po[0], &p->po[1], &p->ps[0], &p->ps[1], &p->recs[0], &p->recs[1], &p->rl, &p->nl, &p->oc, &p->off, &p->noff, &p->ooff, &p->tmp, &p->info,
                   &p->fp[0], &p->fp[1], &p->bo[0], &p->bo[1], &p->fa_bases, &p->d_text, &p->o_recs[0], &p->o_recs[1], &p->o_bases, &p->o_qual, &p->o_off, &p->o_names, &p->o_noff, &p->o_rows, &p->o_len, &p->o_odd};
     for (Buf *b : all) if (b->p) (void)hipFree(b->p);
+    mcx_bam_in_free(p->bam);
     mcx_pinned_free(p->h_info); mcx_pinned_free(p->h_text);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -491,6 +494,12 @@ namespace {
 int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info, const char *who)
 {
     memset(info, 0, sizeof *info);
+    if (p->format == MCX_READS_BAM) { // BAM records: kernels of their own (mcx_bam_in.hip) on this parser's stream; the rule setting is ignored
+        memset(&p->job, 0, sizeof p->job);
+        p->job.nt = 1; p->job.max_read_len = in->max_read_len;
+        HIP_TRY(hipEventRecord(p->ev[0], p->stream));
+        return mcx_bam_in_sizes(&p->bam, p->stream, in, p->mates, info, who);
+    }
     const uint32_t nt = in->text[1] ? 2u : 1u;
     for (uint32_t t = 0; t < nt; t++) {
         if (!in->text[t] && in->bytes[t]) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": null text");
@@ -583,6 +592,14 @@ int sizes_pass(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info
 // The groups of `out` (device pointers) from the scratch of the sizes pass; a group whose capacity is too small is left alone and the call says so.
 int output_pass(mcx_fastq_parser *p, const mcx_fastq_out *out, const mcx_fastq_info *info, const char *who)
 {
+    if (p->format == MCX_READS_BAM) {
+        if (!p->bam) return mcx_set_error(MCX_ERR_ARG, std::string(who) + ": no sizes pass went before");
+        const int rc = mcx_bam_in_out(p->bam, p->stream, out, info, who); // (waits for the stream)
+        HIP_TRY(hipEventRecord(p->ev[1], p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        HIP_TRY(hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+        return rc;
+    }
     const Job &job = p->job;
     const uint32_t n = info->n_reads;
     const uint32_t *off = (const uint32_t *)p->off.p, *noff = (const uint32_t *)p->noff.p, *ooff = (const uint32_t *)p->ooff.p;
@@ -650,6 +667,38 @@ extern "C" int mcx_fastq_parser_set_format(mcx_fastq_parser *p, int format)
     return 0;
 }
 
+// set_format with the third format beside its two: MCX_READS_BAM is set here (mcx_fastq_parser_set_format keeps refusing every value but its own two)
+extern "C" int mcx_fastq_parser_set_reads(mcx_fastq_parser *p, int format)
+{
+    if (!p || (format != MCX_READS_FASTQ && format != MCX_READS_FASTA && format != MCX_READS_BAM)) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parser_set_reads: null parser or no such format");
+    p->format = format;
+    return 0;
+}
+
+// MCX_READS_BAM: taken records count in twos for the parser's following calls (sticky, like the rule)
+extern "C" int mcx_fastq_parser_set_mates(mcx_fastq_parser *p, int mates)
+{
+    if (!p || (mates != 0 && mates != 1)) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_parser_set_mates: null parser, or a switch that is neither 0 nor 1");
+    p->mates = mates;
+    return 0;
+}
+
+// MCX_READS_BAM: the last call's records walked, taken, skipped for 0x900, the first taken record's flag, chunks, chunks whose searched start was off the chain
+extern "C" int mcx_bam_reads_last(mcx_fastq_parser *p, uint64_t stats[6])
+{
+    if (!p || !stats) return mcx_set_error(MCX_ERR_ARG, "mcx_bam_reads_last: null argument");
+    mcx_bam_in_last(p->bam, stats, nullptr);
+    return 0;
+}
+
+// ... and its search, walk, join and unpack on the device in ms, by events on the parser's stream (scripts/bam_in_rate.py)
+extern "C" int mcx_bam_reads_last_ms(mcx_fastq_parser *p, float ms[4])
+{
+    if (!p || !ms) return mcx_set_error(MCX_ERR_ARG, "mcx_bam_reads_last_ms: null argument");
+    mcx_bam_in_last(p->bam, nullptr, ms);
+    return 0;
+}
+
 // mcx_fastq_parse_dev in its two halves, for a caller inside the library that sizes its buffers between them (the resident route, mcx_resident.hip): sizes
 // parses and fills *info; out writes the groups of `out` (device pointers) for the texts of the last sizes — a group whose capacity is too small is refused
 int mcx_fastq_dev_sizes(mcx_fastq_parser *p, const mcx_fastq_in *in, mcx_fastq_info *info)
@@ -677,7 +726,7 @@ extern "C" int mcx_fastq_last_ms(mcx_fastq_parser *p, float *ms)
 extern "C" int mcx_fastq_grown(mcx_fastq_parser *p, uint32_t *n)
 {
     if (!p || !n) return mcx_set_error(MCX_ERR_ARG, "mcx_fastq_grown: null argument");
-    *n = p->grown;
+    *n = p->grown + mcx_bam_in_grown(p->bam);
     return 0;
 }
 
@@ -713,7 +762,7 @@ int mcx_fastq_staged_sizes(mcx_fastq_parser *p, const uint64_t bytes[2], int two
     memset(&in, 0, sizeof in);
     in.text[0] = d_text; in.bytes[0] = bytes[0];
     if (two) { in.text[1] = d_text + at1; in.bytes[1] = bytes[1]; }
-    in.max_records = max_records; in.max_read_len = max_read_len; in.final = final;
+    in.max_records = max_records; in.max_read_len = max_read_len; in.final = final; in.n_ref = p->host_n_ref;
     return sizes_pass(p, &in, info, "mcx_fastq_parse");
 }
 
@@ -780,6 +829,7 @@ extern "C" int mcx_fastq_parse(mcx_fastq_parser *p, const mcx_fastq_in *in, cons
     uint8_t *h[2];
     if (int rc = mcx_fastq_stage(p, bytes, h)) return rc;
     for (int t = 0; t < (two ? 2 : 1); t++) if (bytes[t]) memcpy(h[t], in->text[t], bytes[t]);
+    p->host_n_ref = in->n_ref;
     if (int rc = mcx_fastq_staged_sizes(p, bytes, two, in->max_records, in->max_read_len, in->final, info)) return rc;
     return mcx_fastq_staged_out(p, out, info);
 }

@@ -147,6 +147,35 @@ bool plain_fasta(const char *path)
     return ch != EOF && ch != '@';
 }
 
+// a BAM file: BGZF whose text begins "BAM\1", whatever its name — the first member that holds text is inflated here to see
+bool bam_file(const char *path)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) return false;
+    std::vector<uint8_t> head((size_t)1 << 17);
+    head.resize(fread(head.data(), 1, head.size(), f));
+    fclose(f);
+    for (size_t o = 0; o < head.size();) {
+        size_t xlen = 0;
+        const size_t size = mcx_bgzf_member_at(head.data() + o, head.size() - o, xlen);
+        if (!size) return false;
+        const uint8_t *p = head.data() + o;
+        const uint32_t isize = (uint32_t)p[size - 4] | ((uint32_t)p[size - 3] << 8) | ((uint32_t)p[size - 2] << 16) | ((uint32_t)p[size - 1] << 24);
+        if (isize == 0) { o += size; continue; } // (an empty member in front)
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) return false;
+        uint8_t magic[4] = {0, 0, 0, 0};
+        zs.next_in = const_cast<uint8_t *>(p + 12 + xlen); zs.avail_in = (uInt)(size - 12 - xlen - 8);
+        zs.next_out = magic; zs.avail_out = sizeof magic;
+        (void)inflate(&zs, Z_SYNC_FLUSH);
+        const bool is = zs.avail_out == 0 && memcmp(magic, "BAM\1", 4) == 0;
+        inflateEnd(&zs);
+        return is;
+    }
+    return false;
+}
+
 // all n bytes at p: behind what was written before (stream), or at byte `at` of the file
 bool write_all(int fd, const char *p, size_t n, uint64_t at, bool stream)
 {
@@ -187,7 +216,9 @@ struct Run {
     const int max_len;
     Kept *const kept;
     const int nf;               // input files
-    const bool two, paired;
+    const bool two;
+    bool paired; // (a BAM file: its first taken record's flag decides, open_input)
+    bool bam_in = false; // fq1 is a BAM file: the resident route under MCX_READS_BAM, or an error
     const uint64_t shard_count, shard_rank;
     const bool sharded;
     const uint64_t batch_reads;
@@ -310,8 +341,12 @@ struct Run {
         if (!plain && (opt.device_inflate & (MCX_INFLATE_BGZF | MCX_INFLATE_GZ)) && opt.device_parse && !sharded && !opt.interleaved_pairs && (!wants_sam || opt.device_sam)) {
             const char *paths[2] = {fq1, two ? fq2 : nullptr};
             mcx_resident *r = nullptr;
-            if (int e = mcx_resident_open(idx->device, paths, nf, (uint32_t)opt.device_inflate, &r)) return e;
+            if (int e = mcx_resident_open(idx->device, paths, nf, (uint32_t)opt.device_inflate, bam_in, &r)) return e;
             resident.reset(r); // (null: a file is of a kind device_inflate has no bit for, the search cannot cut it, or the files differ in format — the route does not apply and the files are read as without it)
+        }
+        if (bam_in) { // (mcx_map_files_rg has set the switches the route needs: there is no other reader of BAM)
+            if (!resident) return mcx_set_error(MCX_ERR_IO, std::string(fq1) + ": cannot be read as a BAM file");
+            paired = mcx_resident_bam_paired(resident.get());
         }
         if (!plain && !resident && opt.device_parse && !sharded && !opt.interleaved_pairs && plain_fasta(fq1) && (!two || plain_fasta(fq2))) {
             const char *paths[2] = {fq1, two ? fq2 : nullptr};
@@ -326,7 +361,7 @@ struct Run {
         else if (route == kSequential) { if (int e = open_sequential()) return e; } // (the resident route has opened its files itself)
         const uint32_t sam_bit = (dev_sam ? (uint32_t)MCX_ROUTE_SAM : 0u) | (bgzf ? (uint32_t)MCX_ROUTE_BGZF : 0u) | (bam ? (uint32_t)MCX_ROUTE_BAM : 0u) | (sort ? (uint32_t)MCX_ROUTE_SORT : 0u) | (index ? (uint32_t)MCX_ROUTE_INDEX : 0u) | (markdup ? (uint32_t)MCX_ROUTE_MARKDUP : 0u);
         for (int f = 0; f < nf; f++)
-            route_bits[f] = sam_bit | (route == kResident ? mcx_resident_inflate_bit(resident.get(), f) | (uint32_t)(MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
+            route_bits[f] = sam_bit | (bam_in ? (uint32_t)MCX_ROUTE_BAM_IN : 0u) | (route == kResident ? mcx_resident_inflate_bit(resident.get(), f) | (uint32_t)(MCX_ROUTE_PARSE | MCX_ROUTE_ROWS)
                                                           : (ps[f].device_inflated() ? (uint32_t)MCX_ROUTE_INFLATE : 0u) | (route == kMappedDev || route == kFastaDev ? (uint32_t)MCX_ROUTE_PARSE : 0u));
         return 0;
     }
@@ -1390,7 +1425,7 @@ struct Run {
         std::string e;
         for (size_t k = 0; k < t.each_dev.size() && k < 24; k++) e += " " + std::to_string((int)(t.each_dev[k] * 1e4) / 10.0).substr(0, 5);
         fprintf(stderr, "[mcx_map_files] mcx_map_batch_dev, ms per batch:%s\n", e.c_str());
-        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks, 32 BAM records, 512 gunzip): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
+        fprintf(stderr, "[mcx_map_files] on the device (1 inflate, 2 parse, 4 rows from HBM, 8 SAM text, 16 BGZF blocks, 32 BAM records, 512 gunzip, 1024 BAM input): file 1 %u, file 2 %u%s\n", kept->route[0], kept->route[1], route == kResident ? " — the resident route" : "");
         if (dev_sam) fprintf(stderr, "[mcx_map_files] device_sam: names + qualities in, text made and brought back %.3f s of the mapper's time\n", t.m_sam);
         if (bgzf) fprintf(stderr, "[mcx_map_files] bgzf: %llu bytes of text -> %llu bytes of blocks (%u bytes of text a block), the deflater took %.3f s of them\n",
                           (unsigned long long)zs.text_bytes, (unsigned long long)zs.out_bytes, zs.block, zs.seconds);
@@ -1425,6 +1460,16 @@ extern "C" int mcx_map_files_rg(mcx_ctx *c, const char *fq1, const char *fq2, co
     mcx_file_opts_default(&opt);
     if (fo) opt = *fo;
     if (opt.device_sam & MCX_SAM_BAM) opt.device_sam |= MCX_SAM_DEVICE | MCX_SAM_BGZF; // (BAM records are made on the device and framed as BGZF)
+    // BAM read input: refused where it cannot be read, before anything is opened for writing; else it implies the resident route and the device formatter for this call
+    const bool bam_in = bam_file(fq1);
+    if (fq2 && fq2[0] && (bam_in || bam_file(fq2)))
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a BAM read file holds both mates: it is given alone as the first file (-f reads.bam), not with or as a second file");
+    if (bam_in && opt.shard_count > 1)
+        return mcx_set_error(MCX_ERR_UNSUPPORTED, "mcx_map_files_ex: a sharded run does not read BAM input (-f reads.bam with -gpus N / -devices): map on one GPU");
+    if (bam_in) {
+        opt.device_inflate |= MCX_INFLATE_BGZF; opt.device_parse = 1; opt.interleaved_pairs = 0; // (the records' flags say whether they are pairs)
+        if (sam_path && sam_path[0]) opt.device_sam |= MCX_SAM_DEVICE;
+    }
     if (opt.shard_count > 1 && (!opt.exchange || !opt.exchange->allgather || opt.exchange->size != opt.shard_count || opt.exchange->rank != opt.shard_rank))
         return mcx_set_error(MCX_ERR_ARG, "mcx_map_files_ex: a sharded run needs mcx_file_opts.exchange with the shard's rank and count");
     if ((opt.device_sam & MCX_SAM_SORT) && !(opt.device_sam & MCX_SAM_BAM))
@@ -1476,6 +1521,7 @@ extern "C" int mcx_map_files_rg(mcx_ctx *c, const char *fq1, const char *fq2, co
     } tag_switch(c, (with_mc || !rg_id.empty()) && opt.device_sam != 0, rg_id, with_mc);
     if (tag_switch.rc) return tag_switch.rc;
     Run run(c, fq1, fq2, opt, sam_path, stats);
+    run.bam_in = bam_in;
     run.host_md = with_md && opt.device_sam == 0;
     run.rg_line = rg_line;
     if (opt.device_sam == 0) { run.rg_id = rg_id; run.host_mate_tags = with_mc; }

@@ -119,6 +119,14 @@ int mcx_sam_part_dev(mcx_ctx *, const uint8_t *d_bases, const uint32_t *d_off, u
 // mcx_fastq_parse_dev in two halves: the caller sizes its buffers from *info in between
 int mcx_fastq_dev_sizes(mcx_fastq_parser *, const mcx_fastq_in *in, mcx_fastq_info *info);
 int mcx_fastq_dev_out(mcx_fastq_parser *, const mcx_fastq_out *out, const mcx_fastq_info *info);
+// MCX_READS_BAM (mcx_bam_in.hip): the two passes of a parser whose format is BAM, on the parser's stream (a hipStream_t) — *state is made by the first sizes call
+// and freed with the parser; last: mcx_bam_reads_last's counters and the stages' ms (either may be null; a null state gives zeros)
+struct mcx_bam_in;
+int mcx_bam_in_sizes(mcx_bam_in **state, void *stream, const mcx_fastq_in *in, int mates, mcx_fastq_info *info, const char *who);
+int mcx_bam_in_out(mcx_bam_in *, void *stream, const mcx_fastq_out *out, const mcx_fastq_info *info, const char *who);
+void mcx_bam_in_last(const mcx_bam_in *, uint64_t stats[6], float ms[4]);
+uint32_t mcx_bam_in_grown(const mcx_bam_in *);
+void mcx_bam_in_free(mcx_bam_in *);
 // -gpu_parse (mcx_fastq.hip): the host form of mcx_fastq_parse in three steps — stage hands out the parser's page-locked staging for two texts of these sizes
 // (the reader's pool copies the batch's byte ranges into it); staged_sizes sends them to HBM and parses: *info says how many reads, odd bytes, how long the longest;
 // staged_out brings the groups of `out` (HOST pointers, page-locked ones without a further copy) back — rows with row_words 0 come ceil(longest / 16) words wide.
@@ -159,7 +167,13 @@ struct mcx_resident_batch {
     const uint8_t *names, *qual; const uint32_t *name_off;                              // mcx_sam_part_dev's (qual null: FASTA)
     uint64_t n_bases, n_name_bytes;                                                     // (plain) what mcx_resident_host_out's bases and names groups hold
 };
-int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, mcx_resident **out);
+int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, bool bam, mcx_resident **out);
+// bam (the one file is BGZF and its text begins "BAM\1", whatever its name): the header is walked behind the first launch, the records are found and unpacked under
+// MCX_READS_BAM, and the first taken record's flag 0x1 says whether next hands out pairs (bam_paired: an even number of records a batch, mate by mate) or single
+// reads.  A file that cannot be read so is an error, not a fallback.  next: mates that are not neighbours fail with MCX_ERR_ARG; a damaged record ends the input
+// with one line on stderr.
+bool mcx_resident_bam(const mcx_resident *);
+bool mcx_resident_bam_paired(const mcx_resident *);
 // MCX_ROUTE_INFLATE or MCX_ROUTE_GZ: how file f's text came to be in HBM
 uint32_t mcx_resident_inflate_bit(const mcx_resident *, int f);
 // The same object over plain FASTA files (-gpu_parse): the files' bytes go to HBM a launch at a time, the records are plain-rule FASTA's, and next leaves the

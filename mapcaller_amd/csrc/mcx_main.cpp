@@ -15,11 +15,30 @@
 #include <zlib.h>
 
 // longest sequence line among the first records of a read file (FASTQ: every 4th line from the 2nd;
-// FASTA: any non-header line) — sizes the contexts; a longer read further down is an error that names -maxlen
+// FASTA: any non-header line; BAM: l_seq) — sizes the contexts; a longer read further down is an error that names -maxlen
+static int sample_bam_length(gzFile f, std::vector<unsigned char> &t)
+{
+    t.resize((size_t)4 << 20); // the header and the first records: 4 MB of the file's text
+    for (size_t have = 4; have < t.size();) { const int n = gzread(f, t.data() + have, (unsigned)(t.size() - have)); if (n <= 0) { t.resize(have); break; } have += (size_t)n; }
+    uint64_t at = 0; int32_t n_ref = 0;
+    if (mcx_bam_reads_header(t.data(), t.size(), &at, &n_ref) != 0) return 0;
+    int longest = 0;
+    for (uint64_t o = at; o + 36 <= t.size();) {
+        int32_t block_size, l_seq;
+        memcpy(&block_size, &t[o], 4); memcpy(&l_seq, &t[o + 20], 4);
+        if (block_size < 32 || l_seq < 0) break;
+        longest = l_seq > longest ? l_seq : longest;
+        o += 4 + (uint64_t)block_size;
+    }
+    return longest;
+}
 static int sample_read_length(const std::string &path)
 {
     gzFile f = gzopen(path.c_str(), "rb");
     if (!f) return 0;
+    std::vector<unsigned char> head(4);
+    if (gzread(f, head.data(), 4) == 4 && memcmp(head.data(), "BAM\1", 4) == 0) { const int n = sample_bam_length(f, head); gzclose(f); return n; }
+    gzrewind(f);
     static char line[1 << 16];
     int longest = 0, n = 0;
     bool fastq = false;
@@ -41,7 +60,11 @@ static void usage(const char *prog)
             "       %s index ref.fa prefix\n\n"
             "Options: -i STR        BWT_Index_Prefix\n"
             "         -r STR        Reference filename (format:fa); an index is built on the GPU first\n"
-            "         -f            files with #1 mates reads (format:fa, fq, fq.gz)\n"
+            "         -f            files with #1 mates reads (format:fa, fq, fq.gz, bam)\n"
+            "                       BAM input (a BGZF file whose text begins BAM\\1, whatever its name; unaligned or aligned): given alone, without -f2 — the records' flags say\n"
+            "                       whether they are pairs (0x1 on the first record taken: mates must be neighbours, so collate or name-sort a coordinate-sorted file first) or\n"
+            "                       single reads; secondary and supplementary records are skipped and reversed records are read as sequenced, as samtools fastq does; the file is\n"
+            "                       inflated and its records are found and unpacked on the GPU (it implies -gpu_inflate -gpu_parse and, with -sam, -gpu_sam); not with -gpus N\n"
             "         -f2           files with #2 mates reads (format:fa, fq, fq.gz)\n"
             "         -lib STR      file with one 'reads1 [reads2]' pair of filenames per line\n"
             "         -alg STR      gapped alignment algorithm (option: nw|ksw2) [nw]\n"
@@ -342,7 +365,7 @@ int main(int argc, char **argv)
         st.reads += sh.st.reads; st.mapped += sh.st.mapped; st.pairs += sh.st.pairs; st.pair_dist_sum += sh.st.pair_dist_sum; st.pair_len_sum += sh.st.pair_len_sum;
     }
     fprintf(stderr, "All the %lld %s reads have been processed.\n%12lld reads are mapped properly.\n%12lld reads are mapped in pairs.\n",
-            (long long)st.reads, paired_run ? "paired-end" : "single-end", (long long)st.mapped, (long long)st.pairs * 2);
+            (long long)st.reads, paired_run || st.pairs > 0 ? "paired-end" : "single-end", /* (BAM input: the records' flags decide, not the switches) */ (long long)st.mapped, (long long)st.pairs * 2);
     if (want_vcf && rc == 0) { // VariantCalling(), main.cpp:379
         std::vector<mcx_sparse_rec> merged;
         const mcx_sparse_rec *recs = shards[0].recs;

@@ -16,6 +16,10 @@
 // ORDINARY .gz under -gpu_gz -gpu_parse: a third kind of File — `more` runs one round of the file's gzip stream through mcx_gz_file_next / _text (mcx_gz_dev.hip: members,
 // trailers and staging are that file's), making room between the two halves, and the text lands behind `have`; the parser runs under the GZ rule as for BGZF.  The
 // first round is run by mcx_resident_open: a chain of fewer than half of its stretches, and the route does not apply to the call.
+// BAM (one BGZF file whose text begins "BAM\1", whatever its name): the walker, the staging, the launches, the carry and ensure_room are the BGZF file's.  Behind the
+// first launch the header is walked on the host (mcx_bam_reads_header over the text's first bytes, more launches while it asks for them) and `start` moves to the
+// first record; the parser runs under MCX_READS_BAM (mcx_bam_in.hip), and the first taken record's flag decides the library: 0x1 set — pairs, the parser counts
+// mates and a batch takes an even number of records —, else single reads.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -31,6 +35,7 @@
 
 #include "../../include/mcx.h"
 #include "mcx_fastq.h"
+#include "mcx_bam_in.h"
 #include "mcx_internal.h"
 // (mcx_gz_file_*: an ordinary .gz file's rounds, mcx_gz_dev.hip)
 
@@ -97,6 +102,9 @@ struct mcx_resident {
     uint32_t max_members = 0;
     bool fixed_launch = false;         // MCX_RESIDENT_LAUNCH_BYTES is set: every launch is that long
     bool fasta = false, plain = false; // FASTA text (no qualities); plain files (the results go back to the host)
+    bool bam = false, bam_paired = false, bam_damaged_said = false; // a BAM file; its first taken record has flag 0x1: pairs; the line about its damage is out
+    int32_t n_ref = 0;                 // ... the n_ref of its header
+    uint64_t delivered = 0;            // ... reads handed out so far
     mcx_fastq_info all;                // (plain) the last batch's combined call, for mcx_resident_host_out
 };
 struct mcx_resident_bufs {
@@ -228,8 +236,45 @@ int count(mcx_resident *R, const File &f, uint32_t max_records, int32_t max_read
     memset(&in, 0, sizeof in);
     in.bytes[0] = f.have - f.start;
     in.text[0] = in.bytes[0] ? (const uint8_t *)f.text[f.cur].p + f.start : nullptr;
-    in.max_records = max_records; in.max_read_len = max_read_len; in.final = f.eof ? 1 : 0;
+    in.max_records = max_records; in.max_read_len = max_read_len; in.final = f.eof ? 1 : 0; in.n_ref = R->n_ref;
     return mcx_fastq_dev_sizes(R->parser, &in, info);
+}
+
+enum : uint64_t { kBamHeaderMost = 256ull << 20 };
+
+// BAM: the header behind the first launch — the text's first bytes on the host, more launches while they hold too little of it; `start` moves to the first record
+int bam_header(mcx_resident *R, File &f)
+{
+    std::vector<uint8_t> h;
+    for (uint64_t want = 65536;;) {
+        const uint64_t live = f.have - f.start, n = std::min(live, want);
+        h.resize(n);
+        if (n) HIP_TRY(hipMemcpy(h.data(), (const uint8_t *)f.text[f.cur].p + f.start, n, hipMemcpyDeviceToHost));
+        uint64_t at = 0;
+        int32_t n_ref = 0;
+        const int rc = mcx_bam_reads_header(h.data(), n, &at, &n_ref);
+        if (rc == 0) { f.start += at; R->n_ref = n_ref; return 0; }
+        if (rc < 0) return mcx_set_error(MCX_ERR_IO, f.path + ": the BAM header is damaged");
+        if (n < live) { want = live; continue; } // (more of it is in HBM already)
+        if (live > kBamHeaderMost) return mcx_set_error(MCX_ERR_UNSUPPORTED, f.path + ": a BAM header of more than 256 MB is not read");
+        if (f.eof) return mcx_set_error(MCX_ERR_IO, f.path + ": the BAM header is cut short");
+        if (int e = more(R, f)) return e;
+        want = f.have - f.start;
+    }
+}
+
+// BAM: pairs or single reads — the flag of the first taken record, from as many launches as it takes to reach one
+int bam_library(mcx_resident *R, File &f)
+{
+    for (;;) {
+        mcx_fastq_info info;
+        if (int rc = count(R, f, 1, 0x7FFFFFFF, &info)) return rc;
+        uint64_t st[6];
+        if (int rc = mcx_bam_reads_last(R->parser, st)) return rc;
+        if (st[1]) { R->bam_paired = (st[3] & 1u) != 0; return 0; }
+        if (f.eof || info.stop[0] != MCX_FASTQ_MORE) return 0; // no taken record at all: nothing will be mapped
+        if (int rc = more(R, f)) return rc;
+    }
 }
 
 } // namespace
@@ -262,16 +307,19 @@ void mcx_resident_bufs_free(mcx_resident_bufs *b)
 
 uint32_t mcx_resident_inflate_bit(const mcx_resident *R, int f) { return R->f[f].gz ? (uint32_t)MCX_ROUTE_GZ : (uint32_t)MCX_ROUTE_INFLATE; }
 
-int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, mcx_resident **out)
+bool mcx_resident_bam(const mcx_resident *R) { return R->bam; }
+bool mcx_resident_bam_paired(const mcx_resident *R) { return R->bam_paired; }
+
+int mcx_resident_open(int device, const char *const paths[2], int n_files, uint32_t kinds, bool bam, mcx_resident **out)
 {
     *out = nullptr;
     mcx_resident *R = new mcx_resident();
-    R->device = device; R->n_files = n_files;
+    R->device = device; R->n_files = n_files; R->bam = bam;
     bool applies = true, is_gz[2] = {false, false};
     for (int i = 0; i < n_files && applies; i++) {
         const std::string path(paths[i]);
         File &f = R->f[i];
-        applies = path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0; // (the .gz readers' rule goes with the name, ReadMapping.cpp:709)
+        applies = bam || (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0); // (the .gz readers' rule goes with the name, ReadMapping.cpp:709; a BAM file is one whatever its name)
         const int fd = applies ? ::open(paths[i], O_RDONLY) : -1;
         if (fd < 0) { applies = false; break; }
         struct stat st;
@@ -311,11 +359,18 @@ int mcx_resident_open(int device, const char *const paths[2], int n_files, uint3
         uint8_t first = 0;
         if (rc == 0 && f.have && hipMemcpy(&first, f.text[f.cur].p, 1, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = mcx_set_error(MCX_ERR_DEVICE, "-gpu_inflate -gpu_parse: copy from the device failed"); }
         applies = f.have != 0 && !f.gz_uncut;
-        fastq[i] = first == '@';
+        fastq[i] = first == '@' || bam;
     }
     if (n_files == 2 && fastq[0] != fastq[1]) applies = false;
     R->fasta = !fastq[0];
     if (rc == 0 && applies && R->fasta) rc = mcx_fastq_parser_set_format(R->parser, MCX_READS_FASTA);
+    if (rc == 0 && bam) {
+        if (!applies || n_files != 1 || R->f[0].gz) rc = mcx_set_error(MCX_ERR_IO, std::string(paths[0]) + ": the BAM file holds no text that can be inflated");
+        if (rc == 0) rc = bam_header(R, R->f[0]);
+        if (rc == 0) rc = mcx_fastq_parser_set_reads(R->parser, MCX_READS_BAM);
+        if (rc == 0) rc = bam_library(R, R->f[0]);
+        if (rc == 0 && R->bam_paired) rc = mcx_fastq_parser_set_mates(R->parser, 1);
+    }
     if (rc || !applies) { mcx_resident_close(R); return rc; }
     for (File &f : R->f) f.gz_taken = true;
     *out = R;
@@ -381,6 +436,26 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
         }
         out->n_records[i] = info[i].n_records[0];
         out->last[i] = info[i].n_records[0] < per_file;
+        if (R->bam && info[i].stop[0] == MCX_FASTQ_UNPAIRED)
+            return mcx_set_error(MCX_ERR_ARG, f.path + ": the BAM file's mates are not neighbours (behind " + std::to_string(R->delivered + info[i].n_records[0]) +
+                                                  " reads): collate it or sort it by name first (samtools collate, samtools sort -n)");
+        if (R->bam && info[i].stop[0] == MCX_FASTQ_DAMAGED && !R->bam_damaged_said) {
+            R->bam_damaged_said = true;
+            fprintf(stderr, "[mcx_map_files] %s: a damaged BAM record, or one cut short; the file's input ends behind %llu reads\n", f.path.c_str(), (unsigned long long)(R->delivered + info[i].n_records[0]));
+        }
+        if (R->bam && out->last[i] && info[i].stop[0] == MCX_FASTQ_TOO_LONG) { // its name, from the record at the first byte that was not taken
+            uint8_t head[mcx::bamin::kFixed + 256];
+            const uint64_t at = f.start + info[i].consumed[0];
+            const uint32_t len = (uint32_t)std::min<uint64_t>(sizeof head, f.have - at);
+            HIP_TRY(hipMemcpy(head, (const uint8_t *)f.text[f.cur].p + at, len, hipMemcpyDeviceToHost));
+            const uint32_t lrn = len > mcx::bamin::kFixed ? std::min<uint32_t>(head[12], len - mcx::bamin::kFixed) : 0;
+            uint32_t p1 = 1, p2 = 1;
+            if (lrn) mcx::bamin::name_span(head + mcx::bamin::kFixed, lrn, p1, p2);
+            const uint32_t name_len = p2 > p1 ? std::min<uint32_t>(p2 - p1, sizeof out->too_long[i] - 1) : 0;
+            memcpy(out->too_long[i], head + mcx::bamin::kFixed + p1 - 1, name_len);
+            out->too_long[i][name_len] = 0;
+            out->has_too_long[i] = true;
+        } else
         if (out->last[i] && info[i].stop[0] == MCX_FASTQ_TOO_LONG) { // its name, from the header piece at the first byte that was not taken
             uint8_t piece[mcx::fq::kGzPiece];
             const uint64_t at = f.start + info[i].consumed[0];
@@ -413,7 +488,7 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
     mcx_fastq_in in;
     memset(&in, 0, sizeof in);
     for (int i = 0; i < nf; i++) { const File &f = R->f[i]; in.text[i] = (const uint8_t *)f.text[f.cur].p + f.start; in.bytes[i] = consumed[i]; }
-    in.max_records = n_take; in.max_read_len = max_read_len; in.final = 1;
+    in.max_records = n_take; in.max_read_len = max_read_len; in.final = 1; in.n_ref = R->n_ref;
     mcx_fastq_info all;
     if (int rc = mcx_fastq_dev_sizes(R->parser, &in, &all)) return rc;
     const uint32_t n = (uint32_t)nf * n_take;
@@ -443,6 +518,7 @@ int mcx_resident_next(mcx_resident *R, mcx_resident_bufs **bufs, uint32_t per_fi
     }
     if ((rc = mcx_fastq_dev_out(R->parser, &o, &all))) return rc;
     for (int i = 0; i < nf; i++) R->f[i].start += consumed[i];
+    R->delivered += n;
     out->n_reads = n; out->rows = o.rows; out->len = o.len; out->odd = o.odd; out->row_words = row_words; out->n_odd = all.n_odd; out->longest = all.longest;
     out->names = o.names; out->qual = o.qual; out->name_off = o.name_off;
     return 0;

@@ -36,7 +36,7 @@ class _Output(argparse.Action):
 def parse(argv):
     ap = argparse.ArgumentParser(prog="mapcaller_amd.run", add_help=True, prefix_chars="-", allow_abbrev=False)
     ap.add_argument("-i", dest="index", required=True, help="BWT index prefix")
-    ap.add_argument("-f", dest="f1", nargs="+", required=True, help="files with #1 mates reads")
+    ap.add_argument("-f", dest="f1", nargs="+", required=True, help="files with #1 mates reads (fa, fq, fq.gz; or BAM input, given alone without -f2: the records' flags say whether they are pairs — mates must be neighbours — or single reads; secondary and supplementary records are skipped, reversed ones read as sequenced; inflated, found and unpacked on the GPU, which implies -gpu_inflate -gpu_parse and, with -sam, -gpu_sam; not with several GPUs)")
     ap.add_argument("-f2", dest="f2", nargs="*", default=[], help="files with #2 mates reads")
     ap.add_argument("-p", "-pair", dest="interleaved", action="store_true", help="paired-end reads are interlaced in the same file")
     ap.add_argument("-alg", default="nw", choices=["nw", "ksw2"])
@@ -91,6 +91,21 @@ def mapper_kwargs(a):
 def sample_read_length(path, lines=40000):
     """Longest sequence line among the first records of a read file (sizes the contexts)."""
     import gzip
+    import struct
+    with open(path, "rb") as fh:
+        bgzf = fh.read(4) == b"\x1f\x8b\x08\x04"
+    if bgzf:
+        with gzip.open(path, "rb") as fh:
+            t = fh.read(4 << 20)  # a BAM file: the header and the first records
+        if t[:4] == b"BAM\1":
+            rc, o, _ = api.bam_reads_header(t)
+            longest = 0
+            while rc == 0 and o + 36 <= len(t):
+                block_size, l_seq = struct.unpack_from("<i", t, o)[0], struct.unpack_from("<i", t, o + 20)[0]
+                if block_size < 32 or l_seq < 0:
+                    break
+                longest, o = max(longest, l_seq), o + 4 + block_size
+            return longest
     opener = gzip.open if path.endswith(".gz") else open
     longest, fastq = 0, False
     with opener(path, "rb") as fh:
@@ -173,7 +188,7 @@ def main(argv=None):
                                      cmdline=" ".join(["mapcaller_amd.run"] + (sys.argv[1:] if argv is None else list(argv))))
             print(f"\t{vs['n_snv']}(snp); {vs['n_ins']}(ins); {vs['n_del']}(del); {vs['n_tnl'] >> 1}(trans); {vs['n_inv'] >> 1}(inversion)", file=sys.stderr)
     if rank == 0:
-        kind = "paired-end" if (a.f2 or a.interleaved) else "single-end"
+        kind = "paired-end" if (a.f2 or a.interleaved or tot[2] > 0) else "single-end"  # (BAM input: the records' flags decide)
         print(f"All the {tot[0]} {kind} reads have been processed on {world} GPU(s).\n{tot[1]:12d} reads are mapped properly.\n"
               f"{2 * tot[2]:12d} reads are mapped in pairs.", file=sys.stderr)
     mapper.close()
